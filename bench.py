@@ -15,8 +15,8 @@ LOCAL_RANK and --gpus must equal WORLD_SIZE.  No PyTorch in any rank: barriers
 and the max over ranks go through gp_emu_uqsa_amd/rendezvous.py, device
 synchronisation through libgpemu.so.  The headline runs one replica per GPU
 (independent multistart evaluations, no data-path collective; value =
-evaluations by all ranks / the slowest rank's time).  With N > 1 the line also
-carries two row-block legs, each ONE LLH + gradient spread over the N GPUs by the
+evaluations by all ranks / the slowest rank's time).  With N > 1, --full also
+runs two row-block legs, each ONE LLH + gradient spread over the N GPUs by the
 row-block distributed objective over RCCL (include/gpemu_dist.h), with its
 collective time and a rank-0 parity check against the single-GPU objective:
 `extra.rowblock_metric` at the metric's own configuration (n=16384, d=10: the
@@ -25,10 +25,21 @@ BASELINE configs[3] (n=65536, d=20).
 
 Also reported: the roofline of the dominant kernel (the MFMA GEMM: algorithmic
 flops per launch / mean launch time from HIP events on its own stream, recorded
-live on the last timed step), its HBM traffic per launch from the committed
-rocprofv3 PMC pass (profiles/, labelled), and a CPU baseline (the op-for-op
-NumPy restatement of the reference, oracle/gp_oracle.py, on this host's cores;
-rank 0, N=1 only).
+live on the last timed step) and its HBM traffic per launch from the committed
+rocprofv3 PMC pass (profiles/, labelled).
+
+A plain run sets up, warms up, times the --steps steps and prints the line.
+Everything that takes runs of its own is behind --full: the single-evaluation
+and value-only latencies, the informational configs[1] / configs[4] timings,
+the CPU baseline (the op-for-op NumPy restatement of the reference,
+oracle/gp_oracle.py, on this host's cores; rank 0, N=1 only; minutes) and, with
+N > 1, the two row-block legs.  The --no-* options subtract from --full.
+
+--dump-outputs DIR writes what the last timed step returned to its caller, one
+row per try in flight: DIR/llh.npy (K,), DIR/grad.npy (K, d+2), DIR/sigma2.npy
+(K,), float64 (with N > 1 every rank writes its own, `_rank<r>` appended to the
+name).  The inputs are seeded, so two builds run with the same arguments can be
+compared output for output.
 """
 from __future__ import annotations
 
@@ -57,10 +68,17 @@ C4 = (65536, 20)                   # BASELINE.json configs[3]
 def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--steps", type=int, default=10, help="timed steps (at least 1)")
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--n", type=int, default=16384)
     ap.add_argument("--d", type=int, default=10)
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: single-evaluation and value-only "
+                         "latencies, the other configs, the CPU baseline (minutes), with N > 1 the "
+                         "row-block legs; the --no-* options below subtract from it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the (llh, gradient, sigma2) that each try's last "
+                         "timed evaluation returned as DIR/llh.npy, DIR/grad.npy, DIR/sigma2.npy (float64)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-full", action="store_true",
                     help="CPU baseline: 3 op-for-op reps at n=4096 instead of 1 (~2 min more)")
@@ -86,7 +104,10 @@ def parse(argv=None):
     ap.add_argument("--rowblock-timeout", type=float, default=300.0)
     ap.add_argument("--rendezvous-check", action="store_true",
                     help="(test hook) spawn / rendezvous only: no GPU, rank 0 prints the ranks it saw")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 # ---------------------------------------------------------------------------
@@ -443,6 +464,17 @@ def guarded_rowblock(native, synthetic, group, rank, world, local, args, sync_al
     return res
 
 
+def dump_outputs(path, last, rank, world):
+    """What the last timed step handed its caller: (llh, grad, sigma2) of each try."""
+    os.makedirs(path, exist_ok=True)
+    tag = "" if world == 1 else f"_rank{rank}"
+    arrays = {"llh": np.array([r[0] for r in last], dtype=np.float64),
+              "grad": np.array([r[1] for r in last], dtype=np.float64),
+              "sigma2": np.array([r[2] for r in last], dtype=np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(path, f"{name}{tag}.npy"), a)
+
+
 def pmc_traffic(n, d, which="gemm"):
     """HBM bytes per launch of k_gemm (which="gemm") or k_oz_gemm ("ozaki") from the committed
     rocprofv3 PMC summary (tools/pmc_gemm.py)."""
@@ -560,14 +592,18 @@ def main(argv=None):
     llh = last[0][0]
     if group is not None:
         elapsed = group.all_reduce_max(elapsed)
-    # informational, outside the timed region: one eval alone (latency) and value-only
-    t1 = time.perf_counter()
-    ctx.objective(native.GP4ML, native.KERNEL_STD, hps[0])
-    single_s = time.perf_counter() - t1
-    t1 = time.perf_counter()
-    ctx.objective(native.GP4ML, native.KERNEL_STD, hps[0], want_grad=False)
-    value_only_s = time.perf_counter() - t1
-    other = other_configs(native, synthetic, ctx, args) if (rank == 0 and args.other_configs) else None
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last, rank, world)
+    single_s = value_only_s = other = None
+    if args.full:
+        # informational, outside the timed region: one eval alone (latency) and value-only
+        t1 = time.perf_counter()
+        ctx.objective(native.GP4ML, native.KERNEL_STD, hps[0])
+        single_s = time.perf_counter() - t1
+        t1 = time.perf_counter()
+        ctx.objective(native.GP4ML, native.KERNEL_STD, hps[0], want_grad=False)
+        value_only_s = time.perf_counter() - t1
+        other = other_configs(native, synthetic, ctx, args) if (rank == 0 and args.other_configs) else None
     if group is not None:
         group.barrier()
     out = None
@@ -640,11 +676,12 @@ def main(argv=None):
                                                f"{args.steps} (its {K} evals run one at a time)",
                             "eval_tflops_algorithmic": step_tflops,
                             "step_level_frac": step_tflops / FP64_MFMA_PEAK_TFLOPS,
-                            "single_eval_ms": 1000.0 * single_s,
-                            "value_only_ms": 1000.0 * value_only_s,
-                            "other_configs": other,
                             "llh": llh}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full:
+            out.setdefault("extra", {}).update({"single_eval_ms": 1000.0 * single_s,
+                                                "value_only_ms": 1000.0 * value_only_s,
+                                                "other_configs": other})
+        if world == 1 and args.full and not args.no_cpu_baseline:
             cb = cpu_baseline(args.d, args.n, full=args.cpu_full, fast=args.cpu_fast)
             # the headline against each CPU figure (value = the reference's op-order bound)
             ratios = {"vs_ref_op_order_bound": out["value"] / cb["value"]}
@@ -656,7 +693,7 @@ def main(argv=None):
                 ratios["vs_ref_mode_measured_cited"] = out["value"] * cb["ref_mode_measured"]["s_per_eval"]
             cb["gpu_evals_per_s_over_cpu"] = ratios
             out["cpu_baseline"] = cb
-    if world > 1 and args.rowblock:
+    if world > 1 and args.full and args.rowblock:
         for c in ctxs:          # the replica workspaces are not needed by the row-block leg
             c.close()
         ctxs = []

@@ -22,7 +22,7 @@ def test_bench_three_ranks_rowblock_over_rccl():
     env = dict(os.environ, GPEMU_BENCH_ONE_DEVICE="1")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "GPEMU_RDZV_DIR"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "3", "--steps", "2", "--warmup", "1",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "3", "--steps", "2", "--warmup", "1",
            "--n", "2048", "--d", "6", "--no-other-configs", "--rowblock-n", "3000", "--rowblock-d", "8",
            "--rowblock-timeout", "200"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=280, cwd=ROOT)

@@ -3,7 +3,7 @@
 # (dev tool), alternating; then the schedule and concurrency tests.
 set -e
 run() {
-  env $2 timeout -k 10 200 python3 bench.py --no-cpu-baseline --no-other-configs --steps 40 --warmup 3 2>/dev/null | python3 -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); e=d['extra']; print('$1', 'bench', round(d['value'], 3), 'single', round(e['single_eval_ms'], 2), 'chol', round(e['phase_ms']['cholesky'], 2), 'vo', round(e['value_only_ms'], 2), flush=True)"
+  env $2 timeout -k 10 200 python3 bench.py --full --no-cpu-baseline --no-other-configs --steps 40 --warmup 3 2>/dev/null | python3 -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); e=d['extra']; print('$1', 'bench', round(d['value'], 3), 'single', round(e['single_eval_ms'], 2), 'chol', round(e['phase_ms']['cholesky'], 2), 'vo', round(e['value_only_ms'], 2), flush=True)"
 }
 for rep in 1 2 3; do
   run auto "GPEMU_POTRF=auto"

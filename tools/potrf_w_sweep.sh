@@ -4,5 +4,5 @@ mkdir -p gpurun_out
 for W in "4:80,2:40" "4:40,2:20" "4:48,2:24" "8:96,4:48,2:24" "8:64,4:32" "4:24"; do
   echo "== W=$W"
   GPEMU_POTRF_W="$W" timeout -k 10 120 python3 tools/quick_time.py 16384 10 | grep phases
-  GPEMU_POTRF_W="$W" timeout -k 10 200 python3 bench.py --no-cpu-baseline --no-other-configs 2>/dev/null | python3 -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('bench', round(d['value'], 3), 'single', round(d['extra']['single_eval_ms'], 2))"
+  GPEMU_POTRF_W="$W" timeout -k 10 200 python3 bench.py --full --no-cpu-baseline --no-other-configs 2>/dev/null | python3 -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('bench', round(d['value'], 3), 'single', round(d['extra']['single_eval_ms'], 2))"
 done

@@ -7,5 +7,5 @@ ws=("$@")
 for W in "${ws[@]}"; do
   echo "== W=$W"
   GPEMU_POTRF_W="$W" timeout -k 10 120 python3 tools/quick_time.py 16384 10 | grep phases
-  GPEMU_POTRF_W="$W" timeout -k 10 200 python3 bench.py --no-cpu-baseline --no-other-configs 2>/dev/null | python3 -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('bench', round(d['value'], 3), 'single', round(d['extra']['single_eval_ms'], 2))"
+  GPEMU_POTRF_W="$W" timeout -k 10 200 python3 bench.py --full --no-cpu-baseline --no-other-configs 2>/dev/null | python3 -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('bench', round(d['value'], 3), 'single', round(d['extra']['single_eval_ms'], 2))"
 done
