@@ -1,5 +1,5 @@
 """Public API with the reference's signatures (emulatorfunctions.py:13-286):
-setup, train, plot, posterior, posterior_sample."""
+setup, train, plot, posterior, posterior_sample; and loo, which the reference lacks."""
 from __future__ import annotations
 
 import numpy as _np
@@ -88,6 +88,14 @@ def posterior(E, x, predict=True):
     xs = _model.Data(x, None, E.basis, E.par, E.beliefs, E.K)
     p = _model.Posterior(xs, E.training, E.par, E.beliefs, E.K, predict=predict)
     return p.mean, p.var
+
+
+def loo(E):
+    """Leave-one-out validation of E on its own training set with its current
+    hyperparameters: a ``LeaveOneOut`` with mean, var, var_obs, error, score and
+    indiv_standard_error (no counterpart in the reference; one pass over L^-1 on the GPU
+    where the reference would need one refit per training point)."""
+    return _model.LeaveOneOut(E.training, E.par, E.beliefs, E.K)
 
 
 def posterior_sample(E, x, predict=True):

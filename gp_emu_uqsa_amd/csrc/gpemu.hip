@@ -232,6 +232,7 @@ struct gpe_ctx {
   int f_kernel = 0;
   std::vector<double> f_delta;
   double f_nu = 0.0;
+  double f_rscale = 0.0;     // coefficient of diag(r) in the resident A (gpe_loo takes it out again)
 
   // GPEMU_POTRF=group: one launch per column group (Plan::grp); list positions of the
   // chain steps (GPEMU_GROUP_P0, GPEMU_GROUP_STRIDE)
@@ -1356,6 +1357,46 @@ int skinny(gpe_ctx* c, bool transposed, const double* M, long long ldm, int ntr,
   return GPE_OK;
 }
 
+// Y = M^T R as skinny(transposed, lower) over the nt x nt tiles of M, and in the same pass
+// asq(i) = sum_{i <= k < n_valid} M(k, i)^2: the launch of the first 32 columns carries the
+// squares as one more partial column (k_skinny_mfma<., true, true>), so M is read once for
+// both; further column chunks are plain skinny products.  Both outputs are sums in a fixed
+// order (no atomics): repeated calls give the same bits.
+int skinny_t_sq(gpe_ctx* c, const double* M, long long ldm, int nt, long long n_valid, const double* R,
+                long long ldr, int P, double* Y, long long ldy, double* asq) {
+  const int pc = std::min(SK_PMAX, P);
+  const int want = (256 + nt - 1) / nt;   // chunks per output tile for ~256 workgroups (as skinny)
+  const int chk = std::max(1, std::min(SK_CH, (nt + want - 1) / want));
+  const int nch = (nt + chk - 1) / chk;
+  const long long rows = (long long)nt * TILE;
+  if (ldy != rows) return fail(c, GPE_ERR_STATE, "skinny: output ld mismatch");
+  const size_t need = (size_t)nch * rows * (pc + 1);
+  if (need > c->skp_cap) {
+    c->skp_cap = 0;
+    CHK(dalloc(c, &c->dskp, need));
+    c->skp_cap = need;
+  }
+  SkinnyArgs a;
+  a.M = M; a.ldm = ldm; a.R = R; a.ldr = ldr; a.part = c->dskp; a.ldp = rows;
+  a.pstride = rows * (pc + 1); a.P = pc; a.ntr = nt; a.lower = 1; a.nit = nt;
+  a.abort_flag = c->dinfo;
+  a.chk = chk;
+  a.n_valid = (int)n_valid;
+  dim3 grid(nt * nch);
+  if (pc <= 16) hipLaunchKernelGGL((k_skinny_mfma<16, true, true>), grid, dim3(256), 0, c->stream, a);
+  else hipLaunchKernelGGL((k_skinny_mfma<32, true, true>), grid, dim3(256), 0, c->stream, a);
+  HIPCHK(c, hipGetLastError());
+  hipLaunchKernelGGL(k_reduce_chunks, dim3((unsigned)((rows * pc + 255) / 256)), dim3(256), 0, c->stream,
+                     c->dskp, a.pstride, Y, rows, pc, (int)rows, nt, 1, c->dinfo, chk);
+  HIPCHK(c, hipGetLastError());
+  hipLaunchKernelGGL(k_reduce_chunks, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, c->stream,
+                     c->dskp + rows * pc, a.pstride, asq, rows, 1, (int)rows, nt, 1, c->dinfo, chk);
+  HIPCHK(c, hipGetLastError());
+  if (P > pc)
+    CHK(skinny(c, true, M, ldm, nt, nt, true, R + (long long)pc * ldr, ldr, P - pc, Y + (long long)pc * ldy, ldy));
+  return GPE_OK;
+}
+
 // Y = Z T (Z nrows x P, T P x Pout column-major)
 int apply_small(gpe_ctx* c, const double* Z, long long ldz, int P, const double* T, int Pout, double* Y,
                 long long ldy, int nrows, const int* abort_flag) {
@@ -2394,6 +2435,7 @@ int gpe_factor(gpe_ctx* c, int32_t kernel, const double* delta, double nu, doubl
   c->f_kernel = kernel;
   c->f_delta.assign(delta, delta + c->d);
   c->f_nu = nu;
+  c->f_rscale = r_scale;
   return GPE_OK;
 }
 
@@ -2631,6 +2673,48 @@ int gpe_beta(gpe_ctx* c, double* beta_out) {
   SmallAlgebra sa = small_from_gram(G, P);
   if (!sa.ok) return fail(c, GPE_NOT_PD, "H^T A^-1 H not positive definite");
   for (int i = 0; i < c->q; ++i) beta_out[i] = sa.beta[i];
+  return GPE_OK;
+}
+
+// Leave-one-out mean and variance at every training point (include/gpemu.h; derivation in
+// DESIGN.md).  With X = L^-1, Z = X [f H], Kq Kq^T = Z_H^T Z_H and T2 = small_t2(cfac = 1):
+//   X^T (Z T2) = A^-1 [f - H beta, H Kq^-T]   and   (A^-1)_ii = sum_k X(k, i)^2,
+// both from one sweep over L^-1 (skinny_t_sq); k_loo_finish forms P_ii, the mean and the
+// variance on the device.
+int gpe_loo(gpe_ctx* c, double sigma, double* mean_out, double* var_out, double* beta_out) {
+  CHK(check_ready(c));
+  if (!c->factor_valid) return fail(c, GPE_ERR_STATE, "no resident factor (call gpe_factor)");
+  if (!mean_out || !var_out) return fail(c, GPE_ERR_ARG, "bad loo args");
+  const int q = c->q, P = q + 1;
+  const long long np = c->n_pad, n = c->n;
+  if (n < q + 2) return fail(c, GPE_ERR_ARG, "leave-one-out needs n >= q + 2 training points");
+  CHK(ensure_linv(c));
+  CHK(z_from_factor(c));   // dZ is scratch of other entries: re-formed from the factor
+  std::vector<double> G((size_t)P * P);
+  CHK(gram(c, c->dZ, np, P, (int)np, G.data()));
+  SmallAlgebra sa = small_from_gram(G, P);
+  if (!sa.ok) return fail(c, GPE_NOT_PD, "H^T A^-1 H not positive definite");
+  CHK(ensure_pinned(c, (size_t)std::max<long long>(2 * np, (long long)P * P) + 8));
+  const std::vector<double> T2 = small_t2(sa, q, 1.0);
+  std::memcpy(c->hpin, T2.data(), T2.size() * sizeof(double));
+  HIPCHK(c, hipMemcpyAsync(c->dT2, c->hpin, T2.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  CHK(apply_small(c, c->dZ, np, P, c->dT2, P, c->dR2, np, (int)np, c->dinfo));
+  CHK(ensure_small(c, (size_t)3 * np));   // (A^-1)_ii, mean, var (gram's partials are consumed)
+  double* asq = c->dsmall;
+  double* dmean = c->dsmall + np;
+  double* dvar = c->dsmall + 2 * np;
+  CHK(skinny_t_sq(c, c->tr.B, np, c->NB, n, c->dR2, np, P, c->dWa, np, asq));
+  const double* r = (c->has_r && c->f_rscale != 0.0) ? c->dr : nullptr;
+  hipLaunchKernelGGL(k_loo_finish, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, asq, c->dWa, np, q,
+                     c->dF, r, c->f_rscale, sigma * sigma, (int)n, dmean, dvar);
+  HIPCHK(c, hipGetLastError());
+  // mean and var are adjacent: one copy
+  HIPCHK(c, hipMemcpyAsync(c->hpin, dmean, (size_t)2 * np * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  std::memcpy(mean_out, c->hpin, (size_t)n * sizeof(double));
+  std::memcpy(var_out, c->hpin + np, (size_t)n * sizeof(double));
+  if (beta_out)
+    for (int i = 0; i < q; ++i) beta_out[i] = sa.beta[i];
   return GPE_OK;
 }
 

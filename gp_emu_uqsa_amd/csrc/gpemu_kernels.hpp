@@ -1534,6 +1534,7 @@ struct SkinnyArgs {
   int nit;             // output tiles
   const int* abort_flag;
   int chk;             // k tiles per chunk (<= SK_CH; fewer for launches of few output tiles)
+  int n_valid;         // SQ only: rows of M below this count in the column sums of squares
 };
 
 // ---------------------------------------------------------------------------
@@ -1687,6 +1688,12 @@ static __global__ void __launch_bounds__(512) k_trsv_lower(const double* __restr
 // workgroup (32 per wave).  TR: op(M)(k,i) = M(k,i) (k contiguous: LDS image [i][k],
 // pitch 34); else op(M)(k,i) = M(i,k) (i contiguous: image [k][i], pitch 144).
 // 32 k per stage, registers prefetch the next stage.  HBM-bound by design.
+// SQ (TR only; the sweep of gpe_loo): the same walk also gives the column sums of squares
+// sum_k M(k, i)^2 as one more partial column (index P), so M is read once for both.  Each
+// (k, i) of a stage is the MFMA fragment of exactly one lane, which squares it on the VALU;
+// the four lanes that share a column are summed by two fixed shuffles at the end.  Only
+// entries on or below the diagonal and in rows k < n_valid count, whatever the upper part
+// of the diagonal tile and the padding rows hold.
 constexpr int SKM_GK = 32;
 constexpr int SKM_PT = 34;     // [i][k] / [p][k] pitch (doubles)
 constexpr int SKM_PN = 144;    // [k][i] pitch (doubles)
@@ -1739,8 +1746,9 @@ __device__ __forceinline__ void skm_sstore(double* Ms, double* Rs, int tid, cons
   }
 }
 
-template <int PM, bool TR>
+template <int PM, bool TR, bool SQ = false>
 static __global__ void __launch_bounds__(256) k_skinny_mfma(SkinnyArgs a) {
+  static_assert(!SQ || TR, "the column sums of squares belong to the transposed walk");
   constexpr int MIMG = TR ? TILE * SKM_PT : SKM_GK * SKM_PN;
   __shared__ __attribute__((aligned(16))) double Ms[MIMG];
   __shared__ __attribute__((aligned(16))) double Rs[PM * SKM_PT];
@@ -1762,9 +1770,10 @@ static __global__ void __launch_bounds__(256) k_skinny_mfma(SkinnyArgs a) {
   const int P = a.P;
   const double* Mb = TR ? a.M + (long long)(it * TILE) * a.ldm : a.M + (long long)it * TILE;
   constexpr int NPT = PM / 16;
-  d4 acc[NPT][2];
+  d4 acc[NPT + (SQ ? 1 : 0)][2];   // SQ: acc[NPT][j][0] is the lane's sum of squares of fragment j
 #pragma unroll
   for (int u = 0; u < NPT; ++u) acc[u][0] = acc[u][1] = d4{0.0, 0.0, 0.0, 0.0};
+  if constexpr (SQ) acc[NPT][0] = acc[NPT][1] = d4{0.0, 0.0, 0.0, 0.0};
   double mv[16];
   double rv[PM / 8];
   const int kb = kt0 * TILE, ke = kt1 * TILE;
@@ -1782,6 +1791,10 @@ static __global__ void __launch_bounds__(256) k_skinny_mfma(SkinnyArgs a) {
       for (int j = 0; j < 2; ++j) {
         const int i = wave * 32 + j * 16 + (lane & 15);
         bf[j] = TR ? Ms[i * SKM_PT + kk] : Ms[kk * SKM_PN + i];
+        if constexpr (SQ) {
+          const int kg = k0 + kk;
+          if (kg >= it * TILE + i && kg < a.n_valid) acc[NPT][j][0] = fma(bf[j], bf[j], acc[NPT][j][0]);
+        }
       }
 #pragma unroll
       for (int u = 0; u < NPT; ++u) {
@@ -1802,6 +1815,15 @@ static __global__ void __launch_bounds__(256) k_skinny_mfma(SkinnyArgs a) {
         const int i = wave * 32 + j * 16 + (lane & 15);
         if (pp < P) out[i + (long long)pp * a.ldp] = acc[u][j][r];
       }
+  if constexpr (SQ) {
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      double s = acc[NPT][j][0];
+      s += __shfl_xor(s, 16, 64);
+      s += __shfl_xor(s, 32, 64);
+      if (lane < 16) out[wave * 32 + j * 16 + lane + (long long)P * a.ldp] = s;
+    }
+  }
 }
 
 // out[i + p*ldp] = sum_{ch < nch(i)} part[ch][i + p*ldp], fixed order
@@ -1924,6 +1946,25 @@ static __global__ void __launch_bounds__(256) k_colnorm2(const double* V, long l
   for (int i = lane; i < nrows; i += 64) s = fma(col[i], col[i], s);
   for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
   if (lane == 0) out[j] = s;
+}
+
+// Leave-one-out mean and variance (gpe_loo) from the sweep's outputs: asq(i) = (A^-1)_ii and
+// Y = A^-1 [f - H beta, H Kq^-T] (column-major, ld = ldy; Kq Kq^T = H^T A^-1 H), so
+//   P_ii = asq(i) - sum_{p >= 1} Y(i, p)^2,  (P f)_i = Y(i, 0),
+//   mean_i = f_i - (P f)_i / P_ii,  var_i = s2 (1 / P_ii - rscale r_i)   (r NULL: r = 0).
+static __global__ void k_loo_finish(const double* asq, const double* Y, long long ldy, int q, const double* f,
+                                    const double* r, double rscale, double s2, int n, double* mean,
+                                    double* var) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  double yy = 0.0;
+  for (int p = 1; p <= q; ++p) {
+    const double y = Y[i + (long long)p * ldy];
+    yy = fma(y, y, yy);
+  }
+  const double pii = asq[i] - yy;
+  mean[i] = f[i] - Y[i] / pii;
+  var[i] = s2 * (1.0 / pii - (r ? rscale * r[i] : 0.0));
 }
 
 // ---------------------------------------------------------------------------

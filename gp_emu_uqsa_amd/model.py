@@ -442,3 +442,42 @@ class Posterior:
         except OSError:
             print("ERROR: Problem writing to file.")
             raise SystemExit(1)
+
+
+class LeaveOneOut:
+    """Leave-one-out validation of an emulator on its own training set D (gpe_loo; the
+    reference has no counterpart).
+
+    ``mean[i]`` / ``var[i]`` are what ``Posterior`` gives at D's point i when the training
+    set is every other point of D, the hyperparameters are held fixed and beta is
+    re-estimated on those points.  As in ``Posterior`` with a fresh ``Dnew``, ``var`` carries
+    the nugget but not the point's own r; ``var_obs = var + sigma^2 r_scale r`` is the
+    predictive variance of the observation itself, ``error = (f - mean) / sqrt(var_obs)``
+    and ``score`` the mean negative log predictive density.
+    """
+
+    def __init__(self, D, par, beliefs, K):
+        self.D = D
+        self.par = par
+        self.beliefs = beliefs
+        self.K = K
+        self.remake()
+
+    def remake(self):
+        ctx = upload_training(self.D)
+        rs = self.D.r_scale()
+        ctx.ensure_factor(self.K.kind, self.K.d, float(self.K.n), 1.0, rs)
+        s2 = float(self.par.sigma) ** 2
+        self.mean, self.var, self.beta = ctx.loo(float(self.par.sigma))
+        self.var_obs = self.var + s2 * rs * np.asarray(self.D.r, dtype=float) if rs != 0.0 \
+            else self.var.copy()
+        self.error = (self.D.outputs - self.mean) / np.sqrt(self.var_obs)
+        self.score = float(np.mean(0.5 * np.log(2.0 * np.pi * self.var_obs) + 0.5 * self.error ** 2))
+
+    def indiv_standard_error(self, ise=2.0):
+        bad = False
+        for i in range(self.error.size):
+            if np.abs(self.error[i]) >= ise:
+                print("  Bad predictions:", self.D.inputs[i, :], "ise:", np.round(self.error[i], decimals=4))
+                bad = True
+        return bad

@@ -42,6 +42,7 @@ SIGNATURES = {
                                   _ct.c_int32, _D, _D, _D]),
     "gpe_factor": (_ct.c_int, [_VP, _ct.c_int32, _D, _ct.c_double, _ct.c_double, _ct.c_double]),
     "gpe_beta": (_ct.c_int, [_VP, _D]),
+    "gpe_loo": (_ct.c_int, [_VP, _ct.c_double, _D, _D, _D]),
     "gpe_posterior": (_ct.c_int, [_VP, _ct.c_int64, _D, _D, _D, _ct.c_double, _ct.c_int32, _ct.c_int32,
                                   _D, _D]),
     "gpe_noise_sample": (_ct.c_int, [_VP, _ct.c_int64, _D, _D, _D, _ct.c_double, _D, _ct.c_double,
@@ -249,6 +250,16 @@ class Context:
         out = _np.zeros(self.q)
         self._check(self.lib.gpe_beta(self._h, _ptr(out)), "gpe_beta")
         return out
+
+    def loo(self, sigma):
+        """Leave-one-out (mean, var, beta) of the resident factor: the posterior at every
+        training point given the other n - 1, hyperparameters fixed and beta re-estimated
+        without the point; beta is the GLS beta of all n points."""
+        mean = _np.zeros(self.n)
+        var = _np.zeros(self.n)
+        beta = _np.zeros(self.q)
+        self._check(self.lib.gpe_loo(self._h, float(sigma), _ptr(mean), _ptr(var), _ptr(beta)), "gpe_loo")
+        return mean, var, beta
 
     def posterior(self, Xs, Hs, beta, sigma, full_var=True, precision=64):
         """(mean, var): var is m x m when full_var, else its diagonal.  The L^-1 K* product

@@ -35,7 +35,8 @@ extern "C" {
                                 7: gpe_lhc_maximin; 8: gpe_dist_rank_bytes,
                                 gpe_device_synchronize, gpe_build_id;
                                 9: gpe_dist_local_rows takes the basis width q;
-                                10: gpe_ozaki_stats */
+                                10: gpe_ozaki_stats (gpe_loo was added within 10: an
+                                addition, nothing existing changed) */
 
 enum gpe_status {
     GPE_OK = 0,
@@ -109,6 +110,22 @@ int gpe_factor(gpe_ctx* ctx, int32_t kernel, const double* delta, double nu,
  * only L: L^-1 [f H] by forward substitution with the Cholesky's diagonal-tile inverses
  * (no n^3/3 triangular inverse; that runs on demand for the posterior-side entries). */
 int gpe_beta(gpe_ctx* ctx, double* beta_out);
+
+/* Leave-one-out cross-validation of the resident factor (an addition within ABI 10; the
+ * reference has no such entry).  For every training point i, the posterior at x_i given the
+ * other n - 1 points with the hyperparameters held fixed: what n calls of Posterior
+ * (_emulatorclasses.py:607-631) give, each on the n - 1 other points (Dold.A the submatrix
+ * of the resident A), with beta re-estimated on them by Optimize.optimalbeta
+ * (_emulatoroptimise.py:497-504) and Dnew.A = K.var(x_i, predict=True).  In closed form,
+ * with P = A^-1 - A^-1 H (H^T A^-1 H)^-1 H^T A^-1:
+ *   mean_out[i] = f_i - (P f)_i / P_ii,   var_out[i] = sigma^2 (1 / P_ii - r_scale r_i)
+ * (r_scale that of gpe_factor; the r term is zero without r).  One pass over L^-1 (run on
+ * demand, as for gpe_solve) gives diag(A^-1) and A^-1 [f H] together; P_ii, the mean and the
+ * variance are formed on the device.  Repeated calls on one factor return the same bits.
+ * mean_out, var_out: n values; beta_out: q values (the GLS beta of all n points, as gpe_beta)
+ * or NULL.  GPE_ERR_STATE without a resident factor, GPE_ERR_ARG if n < q + 2, GPE_NOT_PD if
+ * H^T A^-1 H is not positive definite. */
+int gpe_loo(gpe_ctx* ctx, double sigma, double* mean_out, double* var_out, double* beta_out);
 
 /* Posterior at m points: replaces Posterior.make_covar/make_mean/make_var
  * (_emulatorclasses.py:607-631) with the resident factor.  Xs m x d, Hs m x q.
