@@ -163,6 +163,7 @@ struct gpe_ctx {
   int oz_on = 1, oz_nmod = OZ_MAXMOD;
   int oz_min_np = 6144;           // OZ_MIN_NP (GPEMU_OZAKI_MIN_NP)
   int oz_np2 = 0, oz_list_len = 0;
+  long long oz_npad = 0;          // the n_pad the cached plan (oz_tri, the lists, oz_c) was made for
   OzConst oz_c{};
   int8_t* dozp = nullptr;         // the N int8 planes of X (lower 256-column panels)
   int8_t* dozr = nullptr;         // the N residue bytes of every lower 256-tile entry
@@ -1074,14 +1075,11 @@ int build_plan(gpe_ctx* c, Fact& F) {
   // --- triangular inverse X = L^-1 in B (diagonal tiles already hold Dinv)
   for (int s = 2; s / 2 < NB; s *= 2) {
     std::vector<GemmProb> pa, pb;
-    std::vector<std::array<int, 3>> prs;
+    const std::vector<std::array<int, 3>> prs = trtri_level_pairs(NB, s);
     double fa = 0.0, fb = 0.0;
-    for (int t0 = 0; t0 < NB; t0 += s) {
-      const int h = t0 + s / 2;
-      if (h >= NB) continue;
-      const int t1 = std::min(t0 + s, NB);
+    for (const auto& pr : prs) {
+      const int t0 = pr[0], h = pr[1], t1 = pr[2];
       const int a = h - t0, b = t1 - h;
-      prs.push_back({t0, h, t1});
       // T^T (a x b tiles, stored in the upper block rows t0:h, cols h:t1 of B)
       //   = X11^T L21^T ;  opA(m,k) = X11(k,m): K-contiguous, upper -> kbeg = ti*128
       pa.push_back(mkprob(tile(B, t0, t0), ld, tile(A, h, t0), ld, tile(B, t0, h), ld, a, b,
@@ -1571,6 +1569,8 @@ int trsv_lower(gpe_ctx* c, Fact& F, const double* R, long long ldr, int P, doubl
 // 2.33 against 2.82 at 8192), the posterior's product from 4096 (GPEMU_OZAKI_MIN_NP lowers
 // both, for tests).
 constexpr int OZ_MIN_NP = 6144, OZ_POST_MIN_NP = 4096, OZ_MAX_NP = 65536, OZ_POST_MAX_NP = 32768;
+// every sum here is at most np2 = n_pad rounded up to 256 long (k_oz_gemm's int32 / fp32 bound)
+static_assert(OZ_MAX_NP % OZ_T == 0 && OZ_MAX_NP <= OZ_MAX_K && OZ_POST_MAX_NP <= OZ_MAX_K, "int8 sums too long");
 bool oz_use(const gpe_ctx* c) { return c->oz_on && c->n_pad >= c->oz_min_np && c->n_pad <= OZ_MAX_NP; }
 
 // the TRTRI levels on the int8 cores: every pair of a level whose blocks have at least
@@ -1584,8 +1584,11 @@ bool oz_tri_level(const gpe_ctx* c, const std::vector<std::array<int, 3>>& prs) 
 // TRTRI pair's) for this n_pad
 int oz_prepare(gpe_ctx* c, Fact& F) {
   const int np2 = (int)(((c->n_pad + OZ_T - 1) / OZ_T) * OZ_T);
-  if (np2 == c->oz_np2 && c->oz_c.nmod == c->oz_nmod) return GPE_OK;
+  // keyed on n_pad, not np2: two n_pad sharing one np2 (1152 and 1280; 8320 and 8448) have
+  // different TRTRI pairs (the last block's t1)
+  if (c->n_pad == c->oz_npad && np2 == c->oz_np2 && c->oz_c.nmod == c->oz_nmod) return GPE_OK;
   c->oz_np2 = 0;
+  c->oz_npad = 0;
   CHK(build_plan(c, F));
   const int NT2 = np2 / OZ_T, N = c->oz_nmod;
   size_t planes = (size_t)oz_plane_bytes(np2) * N;
@@ -1615,6 +1618,7 @@ int oz_prepare(gpe_ctx* c, Fact& F) {
   HIPCHK(c, hipMemcpy(c->dozl, all.data(), all.size() * sizeof(unsigned), hipMemcpyHostToDevice));
   c->oz_c = oz_consts(N, np2);   // (beta for sums of length np2: valid for every product here)
   c->oz_np2 = np2;
+  c->oz_npad = c->n_pad;
   return GPE_OK;
 }
 

@@ -10,7 +10,8 @@
 //
 // The arithmetic, per column j of X (the rows of both operands of X^T X):
 //   e_j     = 52 - ilogb(max_k |X(k,j)|), so X'(k,j) = rint(X(k,j) 2^e_j) is an integer with
-//             |X'| <= 2^53 (beta bits: 53, or fewer for n > 16384, see oz_beta on the host);
+//             |X'| <= 2^53 (beta bits: 53 with 16 moduli for every n_pad up to 131072, fewer
+//             with fewer moduli: oz_consts on the host, checked by tests/host/oz_plan_check.cpp);
 //   C'(i,j) = sum_k X'(k,i) X'(k,j), exact, |C'| <= n 2^(2 beta) < M / 2 (M = prod m_l);
 //   for each modulus m_l (pairwise coprime, <= 256): X'_l = X' mod m_l in [-128, 127]
 //             (int8), C'_l = X'_l^T X'_l on the i8 MFMA (int32, exact: |.| <= n 2^14 < 2^31),
@@ -22,6 +23,13 @@
 // k_oz_gemm (grouped over moduli: 256 x 256 tiles of the lower triangle, K from the tile
 // row's diagonal block), k_oz_crt (N residue bytes per element -> fp64, lower 128-tiles).
 #pragma once
+#include <algorithm>
+#include <array>
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+#include <utility>
+#include <vector>
 
 namespace gpe {
 
@@ -31,6 +39,9 @@ constexpr int OZ_NBUF = 4;                 // stage ring (loads issued 3 stages 
 constexpr int OZ_OPND = OZ_T * OZ_SK;      // one operand's stage image (16 KB)
 constexpr int OZ_LDS = OZ_NBUF * 2 * OZ_OPND;   // 128 KB: one workgroup per CU
 constexpr int OZ_MAXMOD = 16;
+// longest sum of a product: the int32 accumulators hold K 2^14 < 2^31 and k_oz_gemm's epilogue
+// reduces them exactly in fp32 (|t| < 2^23, see there) for K up to this
+constexpr int OZ_MAX_K = (1 << 17) - 128;
 
 // moduli (pairwise coprime; the odd ones <= 253 so a rounded centred residue stays in int8)
 // and the reconstruction constants (host: oz_consts)
@@ -274,8 +285,9 @@ static __global__ void __launch_bounds__(256, 1) k_oz_gemm(OzGemm g, OzConst cst
     }
   }
   // centred residues: t = (acc >> 16) (2^16 mod m) + (acc & 0xffff) is exact in fp32
-  // (|t| < 2^20), q = rint(t / m) to within 3e-4, r = t - q m in [-m/2 - 1, m/2 + 1];
-  // m = 256: the low byte itself
+  // (|t| < 2^23 for K <= OZ_MAX_K < 2^17: |acc| <= K 2^14, so |acc >> 16| <= K / 4, times
+  // 2^16 mod m <= 252, plus 2^16), q = rint(t / m) to within 3e-4, r = t - q m in
+  // [-m/2 - 1, m/2 + 1]; m = 256: the low byte itself
   const int m = cst.m[l], c16 = cst.c16[l];
   const float inv = cst.inv[l];
   int8_t* out = g.res + (long long)l * g.res_bytes +
@@ -602,6 +614,20 @@ std::vector<unsigned> oz_list(int nti, int ntj, bool lower, W work, int ti0 = 0)
   for (int x = 0; x < 8; ++x)
     for (size_t q = 0; q < bins[x].size(); ++q) list[8 * q + x] = bins[x][q];
   return list;
+}
+
+// The block pairs (t0, h, t1) of the TRTRI level of span s tiles (s = 2, 4, ... while
+// s / 2 < NB; tile units of 128): X(t0:h, t0:h) and X(h:t1, h:t1) are inverted, the level fills
+// X(h:t1, t0:h).  The last pair of a level is ragged (t1 = NB) and a block without a lower
+// half has no pair.  One definition for the fp64 schedule (build_plan) and the int8 plans.
+inline std::vector<std::array<int, 3>> trtri_level_pairs(int NB, int s) {
+  std::vector<std::array<int, 3>> prs;
+  for (int t0 = 0; t0 < NB; t0 += s) {
+    const int h = t0 + s / 2;
+    if (h >= NB) continue;
+    prs.push_back({t0, h, std::min(t0 + s, NB)});
+  }
+  return prs;
 }
 
 // ---- one block pair (t0, h, t1) of a TRTRI level (tile units of 128) on the int8 cores:

@@ -76,7 +76,7 @@ def test_ozaki_gradient(oz, fp64, n, d, case):
 
 
 def test_ozaki_fewer_moduli_still_accurate(fp64):
-    """GPEMU_OZAKI_MODULI=12 (beta = 41 bits at n_pad = 4096): the gradient still within
+    """GPEMU_OZAKI_MODULI=12 (beta = 40 bits at n_pad = 4096): the gradient still within
     1e-9 of the fp64 path (the truncated operands' error, not a wrong reconstruction)."""
     mp = pytest.MonkeyPatch()
     mp.setenv("GPEMU_OZAKI_MODULI", "12")
