@@ -27,6 +27,7 @@
 #include "gpemu_tiny.hpp"
 #include "gpemu_snb.hpp"
 #include "gpemu_ozaki.hpp"
+#include "gpemu_pivchol.hpp"
 
 using namespace gpe;
 
@@ -224,6 +225,11 @@ struct gpe_ctx {
   size_t vall_cap = 0, xall_cap = 0, tall_cap = 0;
   double* dNU = nullptr;
   size_t nu_cap = 0;
+  // pivoted Cholesky of the posterior covariance (gpe_posterior_pivchol): the state, pivots,
+  // variances, d, flags and partials in one buffer; the panel W (m_pad x 128), then L (m x k)
+  double* dPc = nullptr;
+  double* dPcL = nullptr;
+  size_t pc_cap = 0, pcl_cap = 0;
 
   // resident factor (gpe_factor)
   bool factor_valid = false;
@@ -1891,7 +1897,7 @@ void gpe_destroy(gpe_ctx* c) {
                     c->aux.logdet, c->dinvdelta, c->dZ,
                     c->dR2, c->dWa, c->dskp, c->dgpart, c->dgram, c->dT2, c->dcpart, c->dcsum,
                     c->dW1, c->dW2, c->dW3, c->dXs, c->dXsw, c->dsmall, c->dtiny, c->dsnb, c->dRn, c->dNU,
-                    c->dVall, c->dXall, c->dTall};
+                    c->dVall, c->dXall, c->dTall, c->dPc, c->dPcL};
   for (double* b : bufs)
     if (b) hipFree(b);
   if (c->dinfo) hipFree(c->dinfo);
@@ -3210,6 +3216,112 @@ int gpe_noise_sample(gpe_ctx* c, int64_t m, const double* Xs, const double* Hs, 
   HIPCHK(c, hipMemcpyAsync(c->hpin, dZs, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   std::memcpy(z_out, c->hpin, (size_t)m * sizeof(double));
+  return GPE_OK;
+}
+
+// Greedy pivoted Cholesky of the posterior covariance (include/gpemu.h).  The
+// covariance is formed in c->dW3 as for gpe_noise_sample, then one k_pc_step launch per pivot
+// (gpemu_pivchol.hpp) works in panels of PC_PANEL columns: after a full panel with steps left,
+// S -= W W^T over the whole m_pad x m_pad matrix (rows and columns already chosen receive
+// values nobody reads), so a step reads at most PC_PANEL earlier columns; with L_out, every
+// panel is then transposed into the row-major device copy of L (k_pc_panel_out).  All k steps
+// are queued without a synchronisation; the stop rule is the device's, and the rank, the
+// pivots and their variances are read once at the end.
+int gpe_posterior_pivchol(gpe_ctx* c, int64_t m, const double* Xs, const double* Hs, const double* beta,
+                          double sigma, const double* r_new, double r_scale, int64_t k, double tol,
+                          double* mean_out, int64_t* piv_out, double* pivvar_out, double* L_out,
+                          int64_t* rank_out) {
+  CHK(check_ready(c));
+  if (!c->factor_valid) return fail(c, GPE_ERR_STATE, "no resident factor (call gpe_factor)");
+  if (m <= 0 || !Xs || !Hs || !beta || !mean_out || !piv_out || !pivvar_out || !rank_out)
+    return fail(c, GPE_ERR_ARG, "bad pivchol args");
+  if (m > 16384)
+    return fail(c, GPE_ERR_UNSUPPORTED, "pivoted Cholesky takes at most 16384 points (one posterior chunk)");
+  if (k < 1 || k > m || !(tol >= 0.0)) return fail(c, GPE_ERR_ARG, "bad pivchol args (1 <= k <= m, tol >= 0)");
+  const long long mp = ((m + TILE - 1) / TILE) * TILE;
+  const int mt = (int)(mp / TILE);
+  const int G = (int)(mp / PC_ROWS);
+  if (c->prof) {
+    for (int i = 0; i < 8; ++i) c->phase_ms[i] = 0.0;
+    HIPCHK(c, hipEventRecord(c->ev[0], c->stream));
+  }
+  CHK(posterior_impl(c, m, Xs, Hs, beta, sigma, 1, 64, mean_out, nullptr, r_new, r_scale, true));
+  // workspace: [state | pivvar (k) | piv (k ints)] (read back in one copy), d (m_pad), the
+  // partial maxima (2 G), then the ints: flags (m_pad) and partial indices (2 G)
+  const size_t kh = (size_t)(k + 1) / 2;
+  const size_t head = 2 + (size_t)k + kh;
+  CHK(grow(c, &c->dPc, &c->pc_cap, head + (size_t)mp + 2 * (size_t)G + (size_t)mp / 2 + (size_t)G));
+  const size_t wsz = (size_t)mp * PC_PANEL;
+  CHK(grow(c, &c->dPcL, &c->pcl_cap, wsz + (L_out ? (size_t)m * (size_t)k : 0)));
+  double* W = c->dPcL;
+  double* Ld = c->dPcL + wsz;
+  PcArgs a;
+  a.S = c->dW3; a.ld = mp; a.m = (int)m; a.G = G;
+  a.st = reinterpret_cast<PcState*>(c->dPc);
+  a.pivvar = c->dPc + 2;
+  a.piv = reinterpret_cast<int*>(c->dPc + 2 + k);
+  a.d = c->dPc + head;
+  a.pmax = a.d + mp;
+  a.chosen = reinterpret_cast<int*>(a.pmax + 2 * (size_t)G);
+  a.pidx = a.chosen + mp;
+  a.tol = tol;
+  static_assert(sizeof(PcState) == 2 * sizeof(double), "PcState");
+  // the trailing update's descriptor: S -= W W^T, every tile, K = PC_PANEL (the same for every panel)
+  std::vector<GemmProb> pv = {mkprob(W, mp, W, mp, c->dW3, mp, mt, mt, PC_PANEL, 0, -1.0, 1.0)};
+  pv[0].tile_begin = 0;
+  pv[0].ntiles = mt * mt;
+  const Launch Lt{0, ADHOC_DESC_BASE + 4, 1, mt * mt, 2.0 * (double)mp * (double)mp * PC_PANEL};
+  if (k > PC_PANEL)
+    HIPCHK(c, hipMemcpyAsync(c->dprobs + ADHOC_DESC_BASE + 4, pv.data(), sizeof(GemmProb), hipMemcpyHostToDevice,
+                             c->stream));
+  hipLaunchKernelGGL(k_pc_init, dim3(G), dim3(PC_ROWS), 0, c->stream, a, (int)k);
+  HIPCHK(c, hipGetLastError());
+  float ms = 0.f;
+  if (c->prof) {
+    HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
+    HIPCHK(c, hipEventSynchronize(c->ev[1]));
+    (void)hipEventElapsedTime(&ms, c->ev[0], c->ev[1]);
+    c->phase_ms[0] = ms;
+  }
+  for (long long t0 = 0; t0 < k; t0 += PC_PANEL) {
+    const int cols = (int)std::min<long long>(PC_PANEL, k - t0);
+    for (int j = 0; j < cols; ++j) {
+      hipLaunchKernelGGL(k_pc_step, dim3(G), dim3(256), 0, c->stream, a, W, (int)(t0 + j), j);
+      HIPCHK(c, hipGetLastError());
+    }
+    if (c->prof) HIPCHK(c, hipEventRecord(c->ev[2], c->stream));
+    if (t0 + cols < k) CHK(launch_gemm_range(c, Lt));
+    if (L_out) {   // the panel into the row-major device copy of L (zeros beyond the rank)
+      hipLaunchKernelGGL(k_pc_panel_out, dim3(G, (cols + 63) / 64), dim3(256), 0, c->stream, W, mp, (int)m, cols,
+                         a.st, Ld, (long long)k, t0);
+      HIPCHK(c, hipGetLastError());
+    }
+    if (c->prof) {   // (profiling only: one synchronisation per panel)
+      HIPCHK(c, hipEventRecord(c->ev[3], c->stream));
+      HIPCHK(c, hipEventSynchronize(c->ev[3]));
+      (void)hipEventElapsedTime(&ms, c->ev[1], c->ev[2]);
+      c->phase_ms[1] += ms;
+      (void)hipEventElapsedTime(&ms, c->ev[2], c->ev[3]);
+      c->phase_ms[2] += ms;
+      HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
+    }
+  }
+  CHK(ensure_pinned(c, head + 8));
+  HIPCHK(c, hipMemcpyAsync(c->hpin, c->dPc, head * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (c->prof) c->phase_ms[6] = c->phase_ms[0] + c->phase_ms[1] + c->phase_ms[2];
+  PcState st;
+  std::memcpy(&st, c->hpin, sizeof(st));
+  const long long rank = st.rank;
+  if (rank < 0 || rank > k) return fail(c, GPE_ERR_HIP, "internal error: pivoted Cholesky rank out of range");
+  const int* pv32 = reinterpret_cast<const int*>(c->hpin + 2 + k);
+  for (long long t = 0; t < k; ++t) {
+    piv_out[t] = t < rank ? pv32[t] : -1;
+    pivvar_out[t] = t < rank ? c->hpin[2 + t] : 0.0;
+  }
+  *rank_out = rank;
+  // the device copy is row-major m x k like L_out, columns >= rank written as zeros
+  if (L_out) HIPCHK(c, hipMemcpy(L_out, Ld, (size_t)m * (size_t)k * sizeof(double), hipMemcpyDeviceToHost));
   return GPE_OK;
 }
 

@@ -14,6 +14,11 @@ The selection statistic, argmin(pdist([x_k; fextra])) over every candidate desig
 computed on the GPU (gpe_lhc_maximin: all N designs batched, the fextra-fextra pairs once)
 with distances bit-identical to pdist's.  The designs are drawn on the host first, in the
 reference's RNG order, in batches of at most _BATCH doubles.
+
+``max_variance_design`` (no counterpart in the reference) asks a trained emulator where the
+next simulator runs would teach it most: the greedy maximum-variance batch among candidate
+points, the first pivots of a pivoted Cholesky of their posterior covariance on the GPU
+(gpe_posterior_pivchol).
 """
 from __future__ import annotations
 
@@ -71,3 +76,33 @@ def optLatinHyperCube(dim=None, n=None, N=None, minmax=None, filename="inputs", 
     _np.savetxt(filename, D, delimiter=" ", fmt='%.8f')
     print("DONE!")
     return None
+
+
+MAX_CANDIDATES = 16384
+
+
+def max_variance_design(E, candidates, k, tol=0.0):
+    """The greedy maximum-variance batch of k points among `candidates` for emulator E.
+
+    Each pick is the candidate with the largest posterior variance given E.training and the
+    candidates picked before it, with E's current hyperparameters (the outputs at the picks
+    are not needed: the variance does not depend on them).  `candidates` are points in the
+    emulator's scaled input space, one row each, with as many columns as E's training inputs.
+    Returns (indices into candidates, their conditional variances at the time of each pick);
+    fewer than k if the largest remaining variance falls to tol * the largest initial one.
+    At most 16384 candidates (one chunk of the posterior): ValueError beyond."""
+    x = _np.asarray(candidates, dtype=float)
+    if x[0].size == 1:
+        x = _np.array([x]).T
+    if x[0, :].size != E.training.inputs[0, :].size:
+        print("ERROR: test points have different number of columns to data in emulator. Exiting.")
+        raise SystemExit(1)
+    if x.shape[0] > MAX_CANDIDATES:
+        raise ValueError(f"max_variance_design takes at most {MAX_CANDIDATES} candidates, got {x.shape[0]}")
+    from . import model as _model
+    xs = _model.Data(x, None, E.basis, E.par, E.beliefs, E.K)
+    ctx = _model.upload_training(E.training)
+    ctx.ensure_factor(E.K.kind, E.K.d, float(E.K.n), 1.0, E.training.r_scale())
+    _, piv, pivvar, _, _ = ctx.posterior_pivchol(xs.inputs, xs.H, E.par.beta, float(E.par.sigma), k=int(k),
+                                                 tol=tol, want_L=False)
+    return piv, pivvar

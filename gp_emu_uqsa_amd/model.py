@@ -351,6 +351,7 @@ class Posterior:
 
     def remake(self):
         self._covar = None
+        self.piv = self.pivvar = self.L_pc = self.rank_pc = None   # pivoted_cholesky() of the old var
         ctx = upload_training(self.Dold)
         ctx.ensure_factor(self.K.kind, self.K.d, float(self.K.n), 1.0, self.Dold.r_scale())
         self.mean, self.var = ctx.posterior(self.Dnew.inputs, self.Dnew.H, self.par.beta,
@@ -411,6 +412,39 @@ class Posterior:
         MD = resid.T.dot(np.linalg.solve(self.var, resid))
         print("calculated Mahalanobis_distance:", MD)
         return True
+
+    def pivoted_cholesky(self, k=None, tol=0.0):
+        """Greedy pivoted Cholesky var = P L L^T P^T of the posterior covariance at Dnew given
+        Dold, on the GPU (gpe_posterior_pivchol; the reference has no counterpart): at most k
+        steps (None: every point), each taking the point with the largest remaining conditional
+        variance, stopping once that is <= tol * the largest prior one.  Stores ``piv`` (the
+        points in the order chosen), ``pivvar`` (their conditional variances), ``L_pc``
+        (m x rank, original point order) and ``rank_pc``; at most 16384 points."""
+        ctx = upload_training(self.Dold)
+        ctx.ensure_factor(self.K.kind, self.K.d, float(self.K.n), 1.0, self.Dold.r_scale())
+        rs = self.Dnew.r_scale()
+        _, self.piv, self.pivvar, self.L_pc, self.rank_pc = ctx.posterior_pivchol(
+            self.Dnew.inputs, self.Dnew.H, self.par.beta, float(self.par.sigma), k=k, tol=tol,
+            r_new=None if rs == 0.0 else self.Dnew.r, r_scale=rs)
+        return self.piv, self.pivvar
+
+    def pivoted_cholesky_errors(self, ise=2.0):
+        """The pivoted-Cholesky errors D_PC = L^-1 P^T (outputs - mean) of Bastos & O'Hagan
+        (2009), in pivot order: uncorrelated, from the most to the least uncertain point given
+        the ones before it, and their squares sum to the Mahalanobis distance when the rank is
+        full.  Runs ``pivoted_cholesky()`` if it has not been run; prints the points with
+        |D_PC| >= ise and their pivot positions."""
+        from scipy.linalg import solve_triangular
+        if getattr(self, "L_pc", None) is None:
+            self.pivoted_cholesky()
+        piv = self.piv
+        resid = (self.Dnew.outputs - self.mean)[piv]
+        e = solve_triangular(self.L_pc[piv], resid, lower=True)
+        for t in range(e.size):
+            if np.abs(e[t]) >= ise:
+                print("  Bad predictions:", self.Dnew.inputs[piv[t], :], "pivot:", t,
+                      "pce:", np.round(e[t], decimals=4))
+        return e
 
     def incVinT(self):
         self.Dold.inputs = np.append(self.Dnew.inputs, self.Dold.inputs, axis=0)

@@ -47,6 +47,9 @@ SIGNATURES = {
                                   _D, _D]),
     "gpe_noise_sample": (_ct.c_int, [_VP, _ct.c_int64, _D, _D, _D, _ct.c_double, _D, _ct.c_double,
                                      _D, _ct.c_int32, _D, _D, _D]),
+    "gpe_posterior_pivchol": (_ct.c_int, [_VP, _ct.c_int64, _D, _D, _D, _ct.c_double, _D, _ct.c_double,
+                                          _ct.c_int64, _ct.c_double, _D, _ct.POINTER(_ct.c_int64), _D, _D,
+                                          _ct.POINTER(_ct.c_int64)]),
     "gpe_solve": (_ct.c_int, [_VP, _ct.c_int32, _D, _D]),
     "gpe_sense_pairs": (_ct.c_int, [_VP, _ct.c_int32, _D, _D, _ct.c_int32, _D, _D, _D]),
     "gpe_gauss_transform": (_ct.c_int, [_VP, _ct.c_int64, _ct.c_int32, _ct.POINTER(_ct.c_int32), _D, _D, _D,
@@ -302,6 +305,35 @@ class Context:
                                               _ptr(rn), float(r_scale), _ptr(t), U.shape[0], _ptr(U),
                                               _ptr(mean), _ptr(z)), "gpe_noise_sample")
         return mean, z
+
+    def posterior_pivchol(self, Xs, Hs, beta, sigma, k=None, tol=0.0, r_new=None, r_scale=0.0, want_L=True):
+        """Greedy pivoted Cholesky of the posterior covariance at Xs (plus sigma^2 r_scale r_new
+        on its diagonal) for the resident factor: up to k steps (None: all m), each taking the
+        point with the largest remaining conditional variance, stopping once that is
+        <= tol * the largest prior one.  Returns (mean, piv, pivvar, L, rank) trimmed to rank:
+        piv (rank,) the points in the order chosen, pivvar their conditional variances, L
+        (m x rank, None without want_L) in the original point order.  At most 16384 points."""
+        Xs = _f64(Xs)
+        if Xs.ndim == 1:
+            Xs = Xs.reshape(-1, 1)
+        m = Xs.shape[0]
+        k = m if k is None else int(k)
+        Hs = _f64(Hs, (m, self.q))
+        beta = _f64(beta).ravel()
+        rn = None if r_new is None else _f64(r_new, (m,))
+        kk = max(k, 1)
+        mean = _np.zeros(m)
+        piv = _np.zeros(kk, dtype=_np.int64)
+        pivvar = _np.zeros(kk)
+        # (not allocated for a call the library refuses)
+        L = _np.zeros((m, kk)) if want_L and 1 <= k <= m <= 16384 else None
+        rank = _ct.c_int64(0)
+        self._check(self.lib.gpe_posterior_pivchol(self._h, m, _ptr(Xs), _ptr(Hs), _ptr(beta), float(sigma),
+                                                   _ptr(rn), float(r_scale), k, float(tol), _ptr(mean),
+                                                   piv.ctypes.data_as(_ct.POINTER(_ct.c_int64)), _ptr(pivvar),
+                                                   _ptr(L), _ct.byref(rank)), "gpe_posterior_pivchol")
+        r = int(rank.value)
+        return mean, piv[:r].copy(), pivvar[:r].copy(), (L[:, :r].copy() if L is not None else None), r
 
     # -- sensitivity building blocks (resident factor)
     def solve(self, B):

@@ -35,8 +35,8 @@ extern "C" {
                                 7: gpe_lhc_maximin; 8: gpe_dist_rank_bytes,
                                 gpe_device_synchronize, gpe_build_id;
                                 9: gpe_dist_local_rows takes the basis width q;
-                                10: gpe_ozaki_stats (gpe_loo was added within 10: an
-                                addition, nothing existing changed) */
+                                10: gpe_ozaki_stats (gpe_loo and gpe_posterior_pivchol were
+                                added within 10: additions, nothing existing changed) */
 
 enum gpe_status {
     GPE_OK = 0,
@@ -236,9 +236,37 @@ int gpe_noise_sample(gpe_ctx* ctx, int64_t m, const double* Xs, const double* Hs
                      const double* t, int32_t s, const double* U, double* mean_out,
                      double* z_out);
 
+/* Greedy pivoted Cholesky S = P L L^T P^T of the posterior covariance at m points (an
+ * addition within ABI 10; the reference has no counterpart).  It extends the seam of
+ * gpe_posterior, Posterior.make_covar/make_mean/make_var (_emulatorclasses.py:607-631): S is
+ * the `var` of that Posterior, exactly what gpe_posterior(full_var = 1, precision = 64)
+ * returns for the same arguments, plus sigma^2 r_scale r_new on its diagonal (r_new m values
+ * or NULL) as gpe_noise_sample forms it; mean_out (m) is its mean.
+ * With d^0 = diag S, step t takes p = argmax of d over the points not yet chosen (lowest
+ * index on ties; a NaN is never greater) and stops before the step if t = k or
+ * d_p <= tol max(d^0); else piv_out[t] = p, pivvar_out[t] = d_p, column
+ * c = S[:, p] - L[:, :t] L[p, :t]^T, L[p, t] = sqrt(d_p), L[i, t] = c_i / sqrt(d_p) for
+ * unchosen i and exactly 0 for rows chosen earlier, d_i -= L[i, t]^2.  *rank_out = steps
+ * taken.  The pivots are the greedy maximum-variance batch (each the point with the largest
+ * posterior variance given the training set and the points picked before it); L^-1 P^T
+ * (y - mean) are the pivoted-Cholesky errors of Bastos & O'Hagan (2009).
+ * L_out (m x k row-major, or NULL) is in the original point order (S = L L^T when
+ * rank = m), columns >= rank zero; piv_out / pivvar_out (k values) are -1 / 0 from rank on.
+ * 1 <= k <= m <= 16384 (one chunk of gpe_posterior): beyond, GPE_ERR_UNSUPPORTED; bad k,
+ * tol < 0 or a NULL output: GPE_ERR_ARG; GPE_ERR_STATE without a resident factor.  Repeated
+ * calls on one factor return the same bits; the resident factor stays usable.
+ * One launch per pivot in panels of 128 columns (gpemu_pivchol.hpp), a grouped MFMA GEMM
+ * S -= W W^T after each full panel; no synchronisation before the end. */
+int gpe_posterior_pivchol(gpe_ctx* ctx, int64_t m, const double* Xs, const double* Hs,
+                          const double* beta, double sigma, const double* r_new, double r_scale,
+                          int64_t k, double tol, double* mean_out, int64_t* piv_out,
+                          double* pivvar_out, double* L_out, int64_t* rank_out);
+
 /* Per-phase device time of the most recent gpe_objective call, in ms:
  * [0] K-build, [1] Cholesky, [2] triangular inverse, [3] A^-1 (L^-T L^-1),
  * [4] skinny solves / small algebra, [5] gradient contraction, [6] total.
+ * After gpe_posterior_pivchol: [0] forming the covariance, [1] the pivot steps, [2] the
+ * trailing updates and panel copies, [6] their sum (one synchronisation per panel is added).
  * Only filled when profiling is on. */
 int gpe_set_profiling(gpe_ctx* ctx, int32_t on);
 int gpe_phase_times(gpe_ctx* ctx, double* ms_out, int32_t n);
