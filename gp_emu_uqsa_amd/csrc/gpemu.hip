@@ -66,6 +66,12 @@ struct Plan {
   // F.flags) beside the previous group's trailing update; width-1 groups as fused.  Per
   // step: the launch to issue, -1 for the later steps of a group
   std::vector<int> grp, grp_aug;
+  // the split sweep (build_plan): tile column h > 0 where the factorisation of the training
+  // matrix is split, its launches per step as fused / fused_aug / grp / grp_aug (columns
+  // [0, h): phase A, [h, NB): the Schur complement's own sweep) and the launch that updates
+  // the augmented row's tiles [h, NB) by the first h columns
+  int split_h = 0, aug_mid = -1;
+  std::vector<int> sfused, sfused_aug, sgrp, sgrp_aug;
   std::vector<Launch> launches;
   std::vector<GemmProb> probs;
   std::vector<unsigned> tiles;   // concatenated tile lists
@@ -76,6 +82,10 @@ struct Plan {
 // diagonal tiles' quadrant counters (G_DQUAD) and the panel tiles' stored-update counters
 // (G_PHALF0)
 constexpr int FACT_FLAG_INTS = 6;
+
+// rows of the Schur complement from which the objective's Cholesky is split and S runs on the
+// int8 cores (GPEMU_OZAKI_CHOL_MIN)
+constexpr int OZ_CHOL_MIN = 8192;
 
 // one TRTRI block pair on the int8 cores (trtri_pair_ozaki): rows of X11 / X22 (Ra / Rb),
 // padded to 256 (Pa / Pb), and its two products' tile lists in dozl
@@ -175,6 +185,20 @@ struct gpe_ctx {
   std::vector<OzTriPair> oz_tri;  // the TRTRI pairs on the int8 cores
   int oz_tri_min = 8192;          // rows of a TRTRI level's blocks from which it runs there
   double oz_lauum_ops = 0.0;      // int8 ops of the LAUUM product (every modulus)
+  // the objective's Cholesky split at tile column h (the top TRTRI pair's), its Schur
+  // complement S = A22 - L21 L21^T one int8 product (chol_schur).  oz_chol: 0 off
+  // (GPEMU_OZAKI_CHOL=0), 1 the gradient evaluations, 2 the value-only ones too, 3 also
+  // gpe_factor's sweep (tests: the only way to read a split sweep's L out again); from
+  // oz_chol_min rows of S (GPEMU_OZAKI_CHOL_MIN)
+  int oz_chol = 1, oz_chol_min = OZ_CHOL_MIN;
+  OzTriPair oz_chol_q{};          // the pair (0, h, NB): L21's planes and exponents as the TRTRI's
+  long long oz_chol_loff = 0;     // the lower tile list of S in dozl
+  int oz_chol_llen = 0;
+  double oz_chol_ops = 0.0;
+  bool oz_chol_ready = false;     // oz_chol_q and the list are planned for this n_pad
+  // dozp / dozx[0, Pb) hold L21's planes and exponents of the resident factor (written by
+  // chol_schur; cleared by everything else that writes them and by gpe_set_data)
+  bool oz_l21_valid = false;
   // profiling (gpe_ozaki_stats): events around the k_oz_gemm launches of the last objective
   std::vector<hipEvent_t> oev;
   size_t oev_used = 0;
@@ -635,6 +659,9 @@ void add_launch_list(Plan& pl, int kind, std::vector<GemmProb> probs, double flo
   pl.launches.push_back(L);
 }
 
+bool oz_use(const gpe_ctx* c);
+int oz_chol_split(const gpe_ctx* c, const Fact& F);
+
 // objective evaluations in flight per device (gpe_objective), for the auto Cholesky schedule
 std::atomic<int> g_inflight[64];
 
@@ -683,6 +710,22 @@ int build_plan(gpe_ctx* c, Fact& F) {
   // --- Cholesky (right-looking, 128-column steps)
   pl.fused.assign(NB, -1);
   pl.fused_aug.assign(NB, -1);
+  if (c->potrf_group) {
+    pl.grp.assign(NB, -1);
+    if (pl.aug) pl.grp_aug.assign(NB, -1);
+  }
+  // One sweep of the schedule: NC tile columns of the sub-matrix whose origin is tile (o, o)
+  // and which has NR tile rows, its launches indexed by global column in ix = {fused,
+  // fused_aug, grp, grp_aug}.  (0, NB, NB) is the whole factorisation.  The split sweep
+  // (Plan::split_h) is (0, h, NB): the first h columns over all rows, every trailing update
+  // clipped to columns < h, so L11 and L21 end final and A22 untouched -- then (h, NB - h,
+  // NB - h), the unsplit schedule of the Schur complement, on its own slices of F.flags,
+  // F.logdet and the diagonal tiles of B, reporting global columns.  t, a, b, g0 below are
+  // local to the sweep; groups and super-blocks go by the rows left (NR - column).
+  auto sweep = [&](const int o, const int NC, const int NR, const std::array<std::vector<int>*, 4>& ix) -> int {
+  auto tile = [&](double* M, int i, int j) { return M + (long long)(o + i) * TILE + (long long)(o + j) * TILE * ld; };
+  auto atile = [&](int j) { return F.Faug + (long long)(o + j) * TILE * TILE; };
+  int* const flags0 = F.flags + o;
   // Fused schedule, one launch per column block t.  Columns are grouped (widths from
   // potrf_groups: wide groups while the trailing matrix is large, width 1 at the end).
   // Launch t, t at position h of group g:
@@ -696,11 +739,11 @@ int build_plan(gpe_ctx* c, Fact& F) {
   // the diagonal tile of step t with K pending columns (from Lp): the pending update runs
   // as DQ_N G_DQUAD workgroups (dquad, pushed before the tile; none for K = 0) and the
   // G_DIAG workgroup waits for them, loads the updated tile and factors it
-  int* cnt_dq = F.flags + 4 * NB;
+  int* cnt_dq = flags0 + 4 * NB;
   auto dquad = [&](int t, const double* Lp, int K, double alpha) {
     GemmProb p = mkprob(Lp, ld, nullptr, 0, tile(A, t, t), ld, DQ_N, 1, K, G_DQUAD, alpha, 1.0);
     p.post = cnt_dq + t;
-    p.diag_col0 = t * TILE;
+    p.diag_col0 = (o + t) * TILE;
     return p;
   };
   auto diagprob = [&](int t, const double* Lp, int K, double alpha) {
@@ -713,9 +756,9 @@ int build_plan(gpe_ctx* c, Fact& F) {
     }
     p.X = tile(B, t, t);
     p.ldx = ld;
-    p.logdet = F.logdet + t;
-    p.diag_col0 = t * TILE;
-    p.flag = F.flags + t;
+    p.logdet = F.logdet + o + t;
+    p.diag_col0 = (o + t) * TILE;
+    p.flag = flags0 + t;
     p.Ld = tile(A, t, t);
     p.ldd = ld;
     return p;
@@ -723,14 +766,14 @@ int build_plan(gpe_ctx* c, Fact& F) {
   // panel tiles: the G_PHALF0 problem (pending update + rows 0-63 of the substitution) and,
   // from it, the G_PHALF1 problem (rows 64-127, after every G_PHALF0 tile of the step
   // stored its update: pc_n of them)
-  int* cnt_pc = F.flags + 5 * NB;
+  int* cnt_pc = flags0 + 5 * NB;
   auto panelprob = [&](int t, const double* Lp, const double* Lt, int K, double alpha) {
-    GemmProb p = mkprob(Lp, ld, Lt, ld, tile(A, t + 1, t), ld, NB - t - 1, 1, K, G_PANEL | G_PHALF0, alpha, 1.0);
+    GemmProb p = mkprob(Lp, ld, Lt, ld, tile(A, t + 1, t), ld, NR - t - 1, 1, K, G_PANEL | G_PHALF0, alpha, 1.0);
     p.cpost = cnt_pc + t;
     p.X = tile(B, t, t);
     p.ldx = ld;
-    p.flag = F.flags + t;
-    p.diag_col0 = t * TILE;   // step index for the GEMM_TRACE dev build
+    p.flag = flags0 + t;
+    p.diag_col0 = (o + t) * TILE;   // step index for the GEMM_TRACE dev build
     p.Ld = tile(A, t, t);
     p.ldd = ld;
     return p;
@@ -742,7 +785,7 @@ int build_plan(gpe_ctx* c, Fact& F) {
     p.cpost = cnt_pc + t;
     p.X = tile(B, t, t);
     p.ldx = ld;
-    p.flag = F.flags + t;
+    p.flag = flags0 + t;
     p.Ld = tile(A, t, t);
     p.ldd = ld;
     p.diag_col0 = -TILE;   // (no GEMM_TRACE slot)
@@ -769,22 +812,22 @@ int build_plan(gpe_ctx* c, Fact& F) {
     fp.push_back(mkprob(tile(A, a, g0), ld, tile(A, a, g0), ld, tile(A, a, a), ld, b - a, b - a, K,
                         G_CLOWER, -1.0, 1.0));
     fl += (double)(b - a) * T * ((double)(b - a) * T + 1.0) * K;
-    if (b < NB) {
-      fp.push_back(mkprob(tile(A, b, g0), ld, tile(A, a, g0), ld, tile(A, b, a), ld, NB - b, b - a, K, 0,
+    if (b < NR) {
+      fp.push_back(mkprob(tile(A, b, g0), ld, tile(A, a, g0), ld, tile(A, b, a), ld, NR - b, b - a, K, 0,
                           -1.0, 1.0));
-      fl += 2.0 * (NB - b) * T * (double)(b - a) * T * K;
+      fl += 2.0 * (NR - b) * T * (double)(b - a) * T * K;
     }
     if (aug) fp.push_back(mkprob(atile(g0), TILE, tile(A, a, g0), ld, atile(a), TILE, 1, b - a, K, 0, -1.0, 1.0));
   };
-  std::vector<int> gs;   // group starts, then NB
-  for (int g = 0; g < NB;) {
+  std::vector<int> gs;   // group starts, then NC
+  for (int g = 0; g < NC;) {
     gs.push_back(g);
     int w = 1;
     for (const auto& r : c->potrf_groups)
-      if (NB - g > r.second) { w = r.first; break; }
-    g += std::max(1, std::min(w, NB - g));
+      if (NR - g > r.second) { w = r.first; break; }
+    g += std::max(1, std::min(w, NC - g));
   }
-  gs.push_back(NB);
+  gs.push_back(NC);
   // Super-blocks (lazy far updates).  Group 0 is a super-block of its own; after it, up to
   // potrf_sb consecutive groups of one width >= 2 form one while more than potrf_sb_min
   // columns remain (later groups, and width-1 groups, stay single: there the longer pending
@@ -795,7 +838,7 @@ int build_plan(gpe_ctx* c, Fact& F) {
   //   its launches carry (bulk segments, balanced over its W launches):
   //     the update by [src0, gb) of its later columns [gb+1, ge) (the column factored next),
   //     the update by [src0, gb) of the rest of its super-block [ge, se),
-  //     a share of the previous super-block's update of the columns beyond [se, NB)
+  //     a share of the previous super-block's update of the columns beyond [se, NC)
   //     (K = 128 x the previous super-block's width: the long-K far update, each far tile
   //     read and written once per super-block instead of once per group).
   // Every column j still receives every earlier column's update before it is factored: a
@@ -807,7 +850,7 @@ int build_plan(gpe_ctx* c, Fact& F) {
     for (int gi = 0; gi < ng; ++gi) {
       const int w = gs[gi + 1] - gs[gi];
       const bool open = gi <= 1 || w < 2 || w != gs[gi] - gs[gi - 1] || cnt >= c->potrf_sb ||
-                        NB - gs[gi] <= c->potrf_sb_min;
+                        NR - gs[gi] <= c->potrf_sb_min;
       if (open) { cur = gs[gi]; cnt = 0; }
       sbs[gi] = cur;
       ++cnt;
@@ -819,7 +862,7 @@ int build_plan(gpe_ctx* c, Fact& F) {
   struct Seg { int a, b, g0, K; };
   std::vector<std::vector<Seg>> segs(ng);
   {
-    auto cost = [&](int j, int K) { return (double)(NB - j) * K; };
+    auto cost = [&](int j, int K) { return (double)(NR - j) * K; };
     for (int gi = 1; gi < ng; ++gi) {   // a super-block's rest: by src0, within the super-block
       const int ge = gs[gi + 1], Kb = (gs[gi] - src0[gi]) * TILE;
       if (ge < sbe[gi]) segs[gi].push_back({ge, sbe[gi], src0[gi], Kb});
@@ -833,7 +876,7 @@ int build_plan(gpe_ctx* c, Fact& F) {
       for (int gj = gi; gj < ng && sbs[gj] == sbs[gi]; ++gj) mem.push_back(gj);
       std::vector<double> fixed(mem.size(), 0.0);
       double F = 0.0, tot = 0.0;
-      for (int j = se; j < NB; ++j) F += cost(j, Kf);
+      for (int j = se; j < NC; ++j) F += cost(j, Kf);
       for (size_t m = 0; m < mem.size(); ++m) {
         const int gj = mem[m], Kb = (gs[gj] - src0[gj]) * TILE;
         for (int j = gs[gj] + 1; j < gs[gj + 1]; ++j) fixed[m] += cost(j, Kb);
@@ -847,14 +890,14 @@ int build_plan(gpe_ctx* c, Fact& F) {
         const double want = std::max(0.0, tot / mem.size() - fixed[m]);
         const int a = j;
         double got = 0.0;
-        while (j < NB && (m + 1 == mem.size() || got + 0.5 * cost(j, Kf) <= want)) got += cost(j++, Kf);
+        while (j < NC && (m + 1 == mem.size() || got + 0.5 * cost(j, Kf) <= want)) got += cost(j++, Kf);
         if (j > a) segs[mem[m]].push_back({a, j, s0, Kf});
       }
     }
   }
   for (int va = 0; va < (pl.aug ? 2 : 1); ++va) {
   aug = va == 1;
-  std::vector<int>& fidx = aug ? pl.fused_aug : pl.fused;
+  std::vector<int>& fidx = *ix[aug ? 1 : 0];
   for (int gi = 0; gi + 1 < (int)gs.size(); ++gi) {
     const int gb = gs[gi], ge = gs[gi + 1], W1 = ge - gb;
     // the group's bulk segments, column by column, split into W1 parts of equal work
@@ -863,14 +906,14 @@ int build_plan(gpe_ctx* c, Fact& F) {
     if (gi > 0) {
       const int Kb = (gb - src0[gi]) * TILE;
       std::vector<double> load(W1, 0.0);
-      for (int h = 0; h + 1 < W1; ++h) load[h] = (double)(NB - (gb + h + 1)) * Kb;
+      for (int h = 0; h + 1 < W1; ++h) load[h] = (double)(NR - (gb + h + 1)) * Kb;
       double tot = 0.0;
       for (int h = 0; h < W1; ++h) tot += load[h];
       std::vector<std::pair<int, int>> cols;   // (column, segment)
       for (int si = 0; si < (int)segs[gi].size(); ++si)
         for (int j = segs[gi][si].a; j < segs[gi][si].b; ++j) {
           cols.push_back({j, si});
-          tot += (double)(NB - j) * segs[gi][si].K;
+          tot += (double)(NR - j) * segs[gi][si].K;
         }
       size_t u = 0;
       double cum = 0.0;
@@ -879,7 +922,7 @@ int build_plan(gpe_ctx* c, Fact& F) {
         const double target = tot * (h + 1) / W1;
         while (u < cols.size()) {
           const Seg& sg = segs[gi][cols[u].second];
-          const double cj = (double)(NB - cols[u].first) * sg.K;
+          const double cj = (double)(NR - cols[u].first) * sg.K;
           if (h < W1 - 1 && cum + 0.5 * cj > target) break;
           cum += cj;
           std::vector<Seg>& ps = part[h];
@@ -894,7 +937,7 @@ int build_plan(gpe_ctx* c, Fact& F) {
       const int p0 = (h == 0) ? src0[gi] : gb;
       const int K = (t - p0) * TILE;
       const double al = K ? -1.0 : 1.0;
-      const int m = NB - t - 1;
+      const int m = NR - t - 1;
       std::vector<GemmProb> fp;
       if (K) fp.push_back(dquad(t, tile(A, t, p0), K, al));
       fp.push_back(diagprob(t, K ? tile(A, t, p0) : nullptr, K, al));
@@ -912,9 +955,9 @@ int build_plan(gpe_ctx* c, Fact& F) {
         if (h + 1 < W1) bulk(fp, fl, t + 1, t + 2, g0, Kb);   // the column factored next
         for (const Seg& sg : part[h]) bulk(fp, fl, sg.a, sg.b, sg.g0, sg.K);
       }
-      fidx[t] = (int)pl.launches.size();
+      fidx[o + t] = (int)pl.launches.size();
       add_launch(pl, 4, fp, fl);
-      pl.launches.back().ticket = F.flags + 3 * NB + t;
+      pl.launches.back().ticket = flags0 + 3 * NB + t;
     }
   }
   // the group schedule: one launch per group of width >= 2.  Its tile list (= dispatch
@@ -926,14 +969,13 @@ int build_plan(gpe_ctx* c, Fact& F) {
   // Step h >= 1 waits for step h-1's panels and its column's update, so every wait points
   // to earlier tiles; one drain per group instead of one per step.
   if (c->potrf_group) {
-    std::vector<int>& gidx = aug ? pl.grp_aug : pl.grp;
-    gidx.assign(NB, -1);
-    int* cnt_col = F.flags + NB;
-    int* cnt_pan = F.flags + 2 * NB;
+    std::vector<int>& gidx = *ix[aug ? 3 : 2];
+    int* cnt_col = flags0 + NB;
+    int* cnt_pan = flags0 + 2 * NB;
     for (int gi = 0; gi + 1 < (int)gs.size(); ++gi) {
       const int gb = gs[gi], ge = gs[gi + 1], W1 = ge - gb;
       if (W1 < 2) {
-        gidx[gb] = fidx[gb];
+        gidx[o + gb] = fidx[o + gb];
         continue;
       }
       const int g0 = src0[gi], Kb = (gb - g0) * TILE;
@@ -964,7 +1006,7 @@ int build_plan(gpe_ctx* c, Fact& F) {
         const int p0 = (h == 0) ? g0 : gb;
         const int K = (t - p0) * TILE;
         const double al = K ? -1.0 : 1.0;
-        const int m = NB - t - 1;
+        const int m = NR - t - 1;
         auto wire = [&](GemmProb& q) {
           if (h == 0) return;
           q.pre0 = cnt_pan + t - 1;
@@ -1072,12 +1114,15 @@ int build_plan(gpe_ctx* c, Fact& F) {
           if (!ok) return fail(c, GPE_ERR_HIP, "internal error: group schedule waits on a later tile");
         }
       }
-      gidx[gb] = (int)pl.launches.size();
+      gidx[o + gb] = (int)pl.launches.size();
       add_launch_list(pl, 4, fp, fl, order);
-      pl.launches.back().ticket = F.flags + 3 * NB + gb;
+      pl.launches.back().ticket = flags0 + 3 * NB + gb;
     }
   }
   }
+  return GPE_OK;
+  };
+  CHK(sweep(0, NB, NB, {&pl.fused, &pl.fused_aug, &pl.grp, &pl.grp_aug}));
   // --- triangular inverse X = L^-1 in B (diagonal tiles already hold Dinv)
   for (int s = 2; s / 2 < NB; s *= 2) {
     std::vector<GemmProb> pa, pb;
@@ -1114,6 +1159,35 @@ int build_plan(gpe_ctx* c, Fact& F) {
     add_launch(pl, 2, lp, N * N * N / 3.0);
   }
   const int limit = (F.desc_base == 0) ? AUX_DESC_BASE : ADHOC_DESC_BASE - AUX_DESC_BASE;
+  // --- the split sweep of the training matrix (potrf with split): columns [0, h), the Schur
+  // complement S = A22 - L21 L21^T on the int8 cores (chol_schur), then chol(S); between the
+  // phases the augmented row's trailing part takes the first h columns' update in one launch.
+  // Left out (the sweep stays whole) when its descriptors would not fit
+  if (const int h = (&F == &c->tr) ? oz_chol_split(c, F) : 0) {
+    const size_t nl = pl.launches.size(), np = pl.probs.size(), nt = pl.tiles.size();
+    pl.sfused.assign(NB, -1);
+    pl.sfused_aug.assign(NB, -1);
+    if (c->potrf_group) {
+      pl.sgrp.assign(NB, -1);
+      if (pl.aug) pl.sgrp_aug.assign(NB, -1);
+    }
+    const std::array<std::vector<int>*, 4> ix = {&pl.sfused, &pl.sfused_aug, &pl.sgrp, &pl.sgrp_aug};
+    CHK(sweep(0, h, NB, ix));
+    CHK(sweep(h, NB - h, NB - h, ix));
+    if (pl.aug) {
+      pl.aug_mid = (int)pl.launches.size();
+      add_launch(pl, 0, {mkprob(F.Faug, TILE, tile(A, h, 0), ld, F.Faug + (long long)h * TILE * TILE, TILE, 1, NB - h,
+                                h * TILE, 0, -1.0, 1.0)}, 0.0);
+    }
+    pl.split_h = h;
+    if ((int)pl.probs.size() > limit) {
+      pl.launches.resize(nl);
+      pl.probs.resize(np);
+      pl.tiles.resize(nt);
+      pl.split_h = 0;
+      pl.aug_mid = -1;
+    }
+  }
   if ((int)pl.probs.size() > limit) return fail(c, GPE_ERR_UNSUPPORTED, "GEMM schedule too large");
   for (auto& L : pl.launches) L.first += F.desc_base;
   HIPCHK(c, hipMemcpy(c->dprobs + F.desc_base, pl.probs.data(), pl.probs.size() * sizeof(GemmProb),
@@ -1225,9 +1299,17 @@ int grow_buf(gpe_ctx* c, T** p, size_t* cap, size_t need) {
   return GPE_OK;
 }
 
-int potrf(gpe_ctx* c, Fact& F, bool with_aug = false) {
+int oz_prepare(gpe_ctx* c, Fact& F);
+int chol_schur(gpe_ctx* c, Fact& F, hipStream_t st, bool with_aug);
+
+// split: the objective's sweep of the training matrix, in two phases around the int8 Schur
+// complement where the plan has them (Plan::split_h, chol_schur)
+int potrf(gpe_ctx* c, Fact& F, bool with_aug = false, bool split = false) {
   CHK(build_plan(c, F));
+  const int hs = split ? F.plan.split_h : 0;
+  if (hs) CHK(oz_prepare(c, F));   // (may rebuild the plan: before pl is taken)
   const Plan& pl = F.plan;
+  if (hs != (split ? pl.split_h : 0)) return fail(c, GPE_ERR_STATE, "internal error: split plan changed");
   const int NB = F.NB;
   // flags, the group schedule's counters and the launches' list tickets start at zero
   HIPCHK(c, hipMemsetAsync(F.flags, 0, FACT_FLAG_INTS * (size_t)NB * sizeof(int), c->stream));
@@ -1235,14 +1317,17 @@ int potrf(gpe_ctx* c, Fact& F, bool with_aug = false) {
   const bool wa = with_aug && pl.aug;
   const bool grp = c->potrf_group &&
                    (c->potrf_mode == 1 || (c->potrf_mode == 0 && g_inflight[c->device & 63].load() <= 1));
-  const std::vector<int>& fidx = grp ? (wa ? pl.grp_aug : pl.grp) : (wa ? pl.fused_aug : pl.fused);
+  const std::vector<int>& fidx = hs ? (grp ? (wa ? pl.sgrp_aug : pl.sgrp) : (wa ? pl.sfused_aug : pl.sfused))
+                                    : (grp ? (wa ? pl.grp_aug : pl.grp) : (wa ? pl.fused_aug : pl.fused));
   if (c->chol_prio) {
     // the whole sweep on the context's high-priority stream: with two tries in flight
     // its chain workgroups are dispatched ahead of the other try's inverse tiles
     HIPCHK(c, hipEventRecord(c->ev_fork, c->stream));
     HIPCHK(c, hipStreamWaitEvent(c->stream2, c->ev_fork, 0));
-    for (int t = 0; t < NB; ++t)
+    for (int t = 0; t < NB; ++t) {
+      if (hs && t == hs) CHK(chol_schur(c, F, c->stream2, wa));
       if (fidx[t] >= 0) CHK(launch_gemm_range(c, pl.launches[fidx[t]], c->stream2));
+    }
     HIPCHK(c, hipEventRecord(c->ev_join, c->stream2));
     HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_join, 0));
     return GPE_OK;
@@ -1257,8 +1342,10 @@ int potrf(gpe_ctx* c, Fact& F, bool with_aug = false) {
     return fail(c, GPE_ERR_STATE, "debug stop after Cholesky launch " + std::to_string(stop));
   }
 #endif
-  for (int t = 0; t < NB; ++t)
+  for (int t = 0; t < NB; ++t) {
+    if (hs && t == hs) CHK(chol_schur(c, F, c->stream, wa));
     if (fidx[t] >= 0) CHK(launch_gemm_range(c, pl.launches[fidx[t]]));
+  }
   return GPE_OK;
 }
 
@@ -1281,7 +1368,7 @@ int ensure_xdiag(gpe_ctx* c, Fact& F) {
   return GPE_OK;
 }
 
-int trtri_pair_ozaki(gpe_ctx* c, Fact& F, int t0, int h, int t1, bool l21_ready);
+int trtri_pair_ozaki(gpe_ctx* c, Fact& F, int t0, int h, int t1, int l21);
 int oz_l21_ahead(gpe_ctx* c, Fact& F, int t0, int h, int t1);
 bool oz_tri_level(const gpe_ctx* c, const std::vector<std::array<int, 3>>& prs);
 
@@ -1296,15 +1383,18 @@ int trtri(gpe_ctx* c, Fact& F, bool ozaki = false) {
   int first = -1;
   for (size_t lv = 0; lv < pl.tri_pairs.size() && ozaki && first < 0; ++lv)
     if (oz_tri_level(c, pl.tri_pairs[lv])) first = (int)lv;
+  // ... unless the split sweep left them (chol_schur) and no int8 level below wrote over them
+  bool have = false;
   if (first >= 0) {
     const auto& pr = pl.tri_pairs[first][0];
-    CHK(oz_l21_ahead(c, F, pr[0], pr[1], pr[2]));
+    have = c->oz_l21_valid && &F == &c->tr && pl.split_h > 0 && pr[0] == 0 && pr[1] == pl.split_h && pr[2] == F.NB;
+    if (!have) CHK(oz_l21_ahead(c, F, pr[0], pr[1], pr[2]));
   }
   for (size_t lv = 0; lv < pl.tri_pairs.size(); ++lv) {
     if (ozaki && oz_tri_level(c, pl.tri_pairs[lv])) {
       for (size_t i = 0; i < pl.tri_pairs[lv].size(); ++i) {
         const auto& pr = pl.tri_pairs[lv][i];
-        CHK(trtri_pair_ozaki(c, F, pr[0], pr[1], pr[2], (int)lv == first && i == 0));
+        CHK(trtri_pair_ozaki(c, F, pr[0], pr[1], pr[2], ((int)lv == first && i == 0) ? (have ? 2 : 1) : 0));
       }
       continue;
     }
@@ -1486,8 +1576,9 @@ int trsv_lower(gpe_ctx* c, Fact& F, const double* R, long long ldr, int P, doubl
 // substitution (trsv_lower) needs: the value-only objective and gpe_beta skip the n^3/3
 // flops of the inverse, and the posterior-side entries run it on demand (ensure_linv).
 int factor_and_invert(gpe_ctx* c, int kernel, const double* delta, double nu, double s2,
-                      double rscale, bool invert = true) {
+                      double rscale, bool invert = true, bool objective = false) {
   c->linv_valid = false;
+  c->oz_l21_valid = false;
   // a call that failed inside the sweep may have left Cholesky launches on the
   // high-priority stream (the join is recorded only after the last one): drain them
   // before this call's memsets and K-build touch the same buffers
@@ -1510,7 +1601,8 @@ int factor_and_invert(gpe_ctx* c, int kernel, const double* delta, double nu, do
   }
   ev_rec(c, 1);
   CHK(build_plan(c, c->tr));
-  CHK(potrf(c, c->tr, c->zaug_valid));
+  // the objective's sweep may split (its gradient evaluations; the value-only ones when asked)
+  CHK(potrf(c, c->tr, c->zaug_valid, objective && (invert || c->oz_chol >= 2)));
   ev_rec(c, 2);
   if (invert) {
     CHK(trtri(c, c->tr, true));   // (only the objective's gradient inverts here)
@@ -1579,6 +1671,16 @@ constexpr int OZ_MIN_NP = 6144, OZ_POST_MIN_NP = 4096, OZ_MAX_NP = 65536, OZ_POS
 static_assert(OZ_MAX_NP % OZ_T == 0 && OZ_MAX_NP <= OZ_MAX_K && OZ_POST_MAX_NP <= OZ_MAX_K, "int8 sums too long");
 bool oz_use(const gpe_ctx* c) { return c->oz_on && c->n_pad >= c->oz_min_np && c->n_pad <= OZ_MAX_NP; }
 
+// The tile column h at which the objective's Cholesky of the training matrix is split (0:
+// not split): the largest power of two below NB, the top TRTRI pair's (0, h, NB), so L21's
+// planes serve both; only where the int8 path runs at all and S has at least oz_chol_min rows
+int oz_chol_split(const gpe_ctx* c, const Fact& F) {
+  if (!c->oz_chol || !oz_use(c) || F.n_pad != c->n_pad || F.NB < 2) return 0;
+  int h = 1;
+  while (2 * h < F.NB) h *= 2;
+  return (F.NB - h) * TILE >= c->oz_chol_min ? h : 0;
+}
+
 // the TRTRI levels on the int8 cores: every pair of a level whose blocks have at least
 // oz_tri_min rows (GPEMU_OZAKI_TRI_MIN; the levels below stay fp64: their products are a
 // few short tiles)
@@ -1595,6 +1697,8 @@ int oz_prepare(gpe_ctx* c, Fact& F) {
   if (c->n_pad == c->oz_npad && np2 == c->oz_np2 && c->oz_c.nmod == c->oz_nmod) return GPE_OK;
   c->oz_np2 = 0;
   c->oz_npad = 0;
+  c->oz_chol_ready = false;
+  c->oz_l21_valid = false;
   CHK(build_plan(c, F));
   const int NT2 = np2 / OZ_T, N = c->oz_nmod;
   size_t planes = (size_t)oz_plane_bytes(np2) * N;
@@ -1616,6 +1720,25 @@ int oz_prepare(gpe_ctx* c, Fact& F) {
       c->oz_tri.push_back(q);
     }
   }
+  // the split Cholesky's Schur complement (chol_schur): the top TRTRI pair's plan (its own
+  // when that level stays fp64) and the lower tile list of S = L21 L21^T, every sum K = Pa
+  if (const int hs = (&F == &c->tr) ? F.plan.split_h : 0) {
+    const OzTriPair* have = nullptr;
+    for (const OzTriPair& q : c->oz_tri)
+      if (q.t0 == 0 && q.h == hs && q.t1 == F.NB) have = &q;
+    const OzTriPair q = have ? *have : oz_tri_pair_plan(0, hs, F.NB, N, all);
+    const int nts = q.Pb / OZ_T;
+    const std::vector<unsigned> ls = oz_list(nts, nts, true, [&](int, int) { return (double)q.Pa; });
+    c->oz_chol_q = q;
+    c->oz_chol_loff = (long long)all.size();
+    c->oz_chol_llen = (int)ls.size();
+    all.insert(all.end(), ls.begin(), ls.end());
+    c->oz_chol_ops = 2.0 * OZ_T * OZ_T * (double)q.Pa * N * (nts * (nts + 1) / 2);
+    planes = std::max(planes, (size_t)N * q.Pb * q.Pa);
+    resid = std::max(resid, (size_t)N * (nts * (size_t)(nts + 1) / 2) * OZ_T * OZ_T);
+    nex = std::max(nex, (size_t)q.Pb);
+    c->oz_chol_ready = true;
+  }
   CHK(dalloc(c, &c->dozp, planes));
   CHK(dalloc(c, &c->dozr, resid));
   CHK(dalloc(c, &c->dozx, nex));
@@ -1628,7 +1751,9 @@ int oz_prepare(gpe_ctx* c, Fact& F) {
   return GPE_OK;
 }
 
-int oz_gemm_crt(gpe_ctx* c, const OzGemm& g, const OzCrt& r, int nti, double ops, double flops64) {
+int oz_gemm_crt(gpe_ctx* c, const OzGemm& g, const OzCrt& r, int nti, double ops, double flops64,
+                hipStream_t st = nullptr) {
+  if (!st) st = c->stream;
   const OzConst& k = c->oz_c;
   if (c->prof) {
     while (c->oev_used + 2 > c->oev.size()) {
@@ -1636,18 +1761,52 @@ int oz_gemm_crt(gpe_ctx* c, const OzGemm& g, const OzCrt& r, int nti, double ops
       HIPCHK(c, hipEventCreate(&e));
       c->oev.push_back(e);
     }
-    HIPCHK(c, hipEventRecord(c->oev[c->oev_used], c->stream));
+    HIPCHK(c, hipEventRecord(c->oev[c->oev_used], st));
   }
-  hipLaunchKernelGGL(k_oz_gemm, dim3(k.nmod * g.list_len), dim3(256), OZ_LDS, c->stream, g, k);
+  hipLaunchKernelGGL(k_oz_gemm, dim3(k.nmod * g.list_len), dim3(256), OZ_LDS, st, g, k);
   if (c->prof) {
-    HIPCHK(c, hipEventRecord(c->oev[c->oev_used + 1], c->stream));
+    HIPCHK(c, hipEventRecord(c->oev[c->oev_used + 1], st));
     c->oev_used += 2;
     c->oz_launches += 1.0;
     c->oz_ops += ops;
     c->oz_flops64 += flops64;
   }
-  hipLaunchKernelGGL(k_oz_crt, dim3((g.tri ? nti * (nti + 1) / 2 : nti * g.ntj) * 16), dim3(256), 0, c->stream, r, k);
+  hipLaunchKernelGGL(k_oz_crt, dim3((g.tri ? nti * (nti + 1) / 2 : nti * g.ntj) * 16), dim3(256), 0, st, r, k);
   HIPCHK(c, hipGetLastError());
+  return GPE_OK;
+}
+
+// Between the phases of the split sweep (potrf), in its stream order on st: L11 and L21 are
+// final, A22 still holds the training matrix's trailing block.  With the augmented row, its
+// tiles [h, NB) take the first h columns' update (one fp64 launch); L21's rows go to int8
+// planes (as for the top TRTRI pair's first product, which then reuses them: oz_l21_valid);
+// S = A22 - L21 L21^T: one product over the lower 256-tiles, K = Pa, and its reconstruction
+// subtracted from A22's lower 128-tiles in place.
+int chol_schur(gpe_ctx* c, Fact& F, hipStream_t st, bool with_aug) {
+  const Plan& pl = F.plan;
+  const OzTriPair& q = c->oz_chol_q;
+  if (!c->oz_chol_ready || q.h != pl.split_h) return fail(c, GPE_ERR_STATE, "internal error: split Cholesky without an int8 plan");
+  if (with_aug) CHK(launch_gemm_range(c, pl.launches[pl.aug_mid], st));
+  const long long ld = F.n_pad;
+  oz_l21_launch(st, c->oz_c, q, F.A + (long long)q.h * TILE, ld, c->dozp, c->dozx);
+  HIPCHK(c, hipGetLastError());
+  const int nts = q.Pb / OZ_T;
+  const long long pA = (long long)q.Pb * q.Pa, rb = (long long)nts * (nts + 1) / 2 * OZ_T * OZ_T;
+  OzGemm g;
+  g.a = g.b = OzOpnd{c->dozp, pA, q.Pa, 0};
+  g.list = c->dozl + c->oz_chol_loff;
+  g.list_len = c->oz_chol_llen;
+  g.K = q.Pa;
+  g.kbeg = 0;
+  g.kend = 0;
+  g.tri = 1;
+  g.ntj = 0;
+  g.res = c->dozr;
+  g.res_bytes = rb;
+  OzCrt r{c->dozr, rb, 1, 0, c->dozx, c->dozx, F.A + (long long)q.h * TILE * (ld + 1), ld, q.Rb, q.Rb, 1, -1.0};
+  r.acc = 1;
+  CHK(oz_gemm_crt(c, g, r, nts, c->oz_chol_ops, (double)q.Rb * q.Rb * q.Ra, st));
+  c->oz_l21_valid = true;
   return GPE_OK;
 }
 
@@ -1657,6 +1816,7 @@ int lauum_ozaki(gpe_ctx* c, Fact& F) {
   const int np = (int)F.n_pad, np2 = c->oz_np2, NT2 = np2 / OZ_T;
   const OzConst& k = c->oz_c;
   const long long pb = oz_plane_bytes(np2), rb = (long long)NT2 * (NT2 + 1) / 2 * OZ_T * OZ_T;
+  c->oz_l21_valid = false;
   hipLaunchKernelGGL(k_oz_colexp, dim3((np2 + 3) / 4), dim3(256), 0, c->stream, F.B, (long long)F.n_pad, np, np2,
                      k.beta, c->dozx);
   hipLaunchKernelGGL(k_oz_split, dim3(np2, (np2 + 256 * OZ_SPLIT_ROWS - 1) / (256 * OZ_SPLIT_ROWS)), dim3(256), 0,
@@ -1685,6 +1845,7 @@ const OzTriPair* oz_pair(const gpe_ctx* c, int t0, int h, int t1) {
 
 // the first product's L21 side (oz_l21_launch) on stream st
 int oz_l21(gpe_ctx* c, Fact& F, const OzTriPair& q, hipStream_t st) {
+  c->oz_l21_valid = false;
   oz_l21_launch(st, c->oz_c, q, F.A + (long long)q.h * TILE + (long long)q.t0 * TILE * F.n_pad, F.n_pad, c->dozp, c->dozx);
   HIPCHK(c, hipGetLastError());
   return GPE_OK;
@@ -1704,17 +1865,19 @@ int oz_l21_ahead(gpe_ctx* c, Fact& F, int t0, int h, int t1) {
 }
 
 // One pair (t0, h, t1) of a TRTRI level on the int8 cores (oz_tri_pair_launches): L21 from
-// A, X11 / X22 / X21 in B, T in the scratch block.  l21_ready: oz_l21_ahead ran.
-int trtri_pair_ozaki(gpe_ctx* c, Fact& F, int t0, int h, int t1, bool l21_ready) {
+// A, X11 / X22 / X21 in B, T in the scratch block.  l21: 1 oz_l21_ahead ran, 2 the planes
+// are the split sweep's (chol_schur, earlier on this stream), 0 neither.
+int trtri_pair_ozaki(gpe_ctx* c, Fact& F, int t0, int h, int t1, int l21) {
   CHK(oz_prepare(c, F));
   const OzTriPair* qp = oz_pair(c, t0, h, t1);
   if (!qp) return fail(c, GPE_ERR_STATE, "internal error: TRTRI pair without an int8 plan");
   const long long ld = F.n_pad;
   auto tile = [&](double* M, int i, int j) { return M + (long long)i * TILE + (long long)j * TILE * ld; };
-  if (l21_ready) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_oz, 0));
+  if (l21 == 1) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_oz, 0));
+  c->oz_l21_valid = false;   // the second product's planes go over them
   int rc = GPE_OK;
   oz_tri_pair_launches(c->stream, c->oz_c, *qp, c->dozl, tile(F.A, h, t0), tile(F.B, t0, t0), tile(F.B, h, h),
-                       tile(F.B, h, t0), ld, c->dozt, c->dozp, c->dozr, c->dozx, l21_ready,
+                       tile(F.B, h, t0), ld, c->dozt, c->dozp, c->dozr, c->dozx, l21 != 0,
                        [&](const OzGemm& g, const OzCrt& r, int nti, double ops, double fl) {
                          if (rc == GPE_OK) rc = oz_gemm_crt(c, g, r, nti, ops, fl);
                        });
@@ -1821,6 +1984,8 @@ gpe_ctx* gpe_create(int32_t device) {
     if (const char* en = std::getenv("GPEMU_OZAKI_MIN_NP")) c->oz_min_np = std::max(512, std::atoi(en));
     if (const char* em = std::getenv("GPEMU_OZAKI_MODULI")) c->oz_nmod = std::max(8, std::min(OZ_MAXMOD, std::atoi(em)));
     if (const char* et = std::getenv("GPEMU_OZAKI_TRI_MIN")) c->oz_tri_min = std::max(512, std::atoi(et));
+    if (const char* ec = std::getenv("GPEMU_OZAKI_CHOL")) c->oz_chol = std::max(0, std::min(3, std::atoi(ec)));
+    if (const char* ec = std::getenv("GPEMU_OZAKI_CHOL_MIN")) c->oz_chol_min = std::max(256, std::atoi(ec));
     if (const char* es = std::getenv("GPEMU_POTRF_SB")) {
       c->potrf_sb = std::max(1, std::min(8, std::atoi(es)));
       if (const char* colon = std::strchr(es, ':')) c->potrf_sb_min = std::max(0, std::atoi(colon + 1));
@@ -1962,6 +2127,7 @@ int gpe_set_data(gpe_ctx* c, int64_t n, int32_t d, int32_t q, const double* X, c
   c->px_valid = false;
   c->zaug_valid = false;
   c->linv_valid = false;
+  c->oz_l21_valid = false;
   if (resize) {
     CHK(ensure_fact(c, c->tr, n_pad));
     CHK(dalloc(c, &c->dX, (size_t)n_pad * d));
@@ -2301,7 +2467,7 @@ int gpe_objective(gpe_ctx* c, int32_t variant, int32_t kernel, const double* hp,
 
   // z, w = L^-1 [f H] come out of the factorisation (augmented row); value only runs
   // no L^-1 at all
-  CHK(factor_and_invert(c, kernel, hp, nu, s2, rscale, want_grad != 0));
+  CHK(factor_and_invert(c, kernel, hp, nu, s2, rscale, want_grad != 0, true));
   const int P = q + 1;
   const long long np = c->n_pad;
   const int NBt = c->tr.NB;
@@ -2431,7 +2597,7 @@ int gpe_factor(gpe_ctx* c, int32_t kernel, const double* delta, double nu, doubl
   c->ainv_valid = false;
   c->x32_valid = false;
   c->px_valid = false;
-  CHK(factor_and_invert(c, kernel, delta, nu, s2, r_scale, false));   // L^-1 on demand
+  CHK(factor_and_invert(c, kernel, delta, nu, s2, r_scale, false, c->oz_chol == 3));   // L^-1 on demand
   int info = 0;
   double logdet = 0.0;
   CHK(read_info_logdet(c, c->tr, &info, &logdet));

@@ -317,7 +317,8 @@ static __global__ void __launch_bounds__(256, 1) k_oz_gemm(OzGemm g, OzConst cst
 // centred fraction of sum_l c_l y_l / m_l.  Thread u of tile t (16 workgroups per tile) =
 // wave u / 1024, block (u / 64) % 16, lane u % 64 of k_oz_gemm's order, 16 entries; rows
 // < rows and columns < cols only, and with lower128 only the lower 128-tiles.  Tile rows
-// from ti0 (as OzGemm); row gm of the product goes to row gm - 256 ti0 of C.
+// from ti0 (as OzGemm); row gm of the product goes to row gm - 256 ti0 of C.  acc: the entry
+// is added to C's (C = C + alpha ..., one rounding, written once) instead of replacing it.
 struct OzCrt {
   const int8_t* res;
   long long res_bytes;
@@ -329,6 +330,7 @@ struct OzCrt {
   int rows, cols, lower128;
   double alpha;
   int ti0 = 0;
+  int acc = 0;
 };
 static __global__ void __launch_bounds__(256) k_oz_crt(OzCrt g, OzConst cst) {
   const int t = (int)blockIdx.x >> 4;
@@ -370,8 +372,10 @@ static __global__ void __launch_bounds__(256) k_oz_crt(OzCrt g, OzConst cst) {
     if (gn >= g.cols || (g.lower128 && (gm >> 7) < (gn >> 7))) continue;
     const double v = (shi[r] - rint(shi[r])) + slo[r];   // C' / M, centred
     const int en = g.exc[gn];
-    g.C[gm - OZ_T * g.ti0 + (long long)gn * g.ldc] =
-        (em == OZ_EX_NAN || en == OZ_EX_NAN) ? __builtin_nan("") : v * ldexp(sc, -(em + en));
+    double* dst = g.C + (gm - OZ_T * g.ti0 + (long long)gn * g.ldc);
+    const double s = ldexp(sc, -(em + en));
+    if (em == OZ_EX_NAN || en == OZ_EX_NAN) *dst = __builtin_nan("");
+    else *dst = g.acc ? fma(v, s, *dst) : v * s;
   }
 }
 

@@ -1,0 +1,321 @@
+"""The objective's Cholesky split at tile column h (the top TRTRI pair's), its Schur complement
+S = A22 - L21 L21^T one product on the int8 matrix cores (build_plan's split sweep, chol_schur,
+k_oz_crt's accumulate mode).
+
+Contexts: GPEMU_OZAKI_MIN_NP=512, GPEMU_OZAKI_TRI_MIN=512 and GPEMU_OZAKI_CHOL_MIN=256 (the
+floors gpe_create allows), beside a GPEMU_OZAKI=0 context (the fp64 sweep) and the oracle's
+objective_fast.  Shapes (NB tile columns of 128, h the split column, Rb rows of S, Pb those
+rows padded to the int8 tile of 256):
+
+  n     NB  h   Rb   Pb
+  1024   8   4  512  512   2 x 2 int8 tiles, equal halves
+  1400  11   8  384  512   padding past n_pad, the last tile ragged
+  2900  23  16  896 1024   Ra = 2048
+  1100   9   8  128    -   below the floor: unsplit, bit-equal to GPEMU_OZAKI_CHOL=0
+  1600  13   8  640  768   the hard point that splits
+
+The tolerances are the suite's (tests/test_gpu_ozaki_tri.py): LLH within 1e-10 max(1, |LLH|)
+of the oracle, gradient within 1e-10 of scale of the fp64 context's and 1e-7 of the oracle's,
+sigma^2 within 1e-10 relative.  That the split ran is read off gpe_ozaki_stats: one k_oz_gemm
+launch more than the LAUUM's and the TRTRI pairs'.
+
+L itself: the library has no read-out of the factor, and gpe_objective leaves none resident,
+so the test takes gpe_factor through the same split sweep (GPEMU_OZAKI_CHOL=3, a test switch)
+and reads A^-1 B for a few columns B through gpe_solve: the residual max |A X - B| /
+(max |A| max |X|) carries the factor's defect (A - L L^T) X; asserted no larger than 4 x the
+fp64 context's own on the same data, both printed.
+"""
+import functools
+import os
+
+import numpy as np
+import pytest
+
+from gp_emu_uqsa_amd import native
+from oracle import gp_oracle as orc
+
+pytestmark = pytest.mark.gpu
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ozaki_hard.npz")
+FLOORS = dict(GPEMU_OZAKI_MIN_NP="512", GPEMU_OZAKI_TRI_MIN="512", GPEMU_OZAKI_CHOL_MIN="256")
+
+
+def _context(**env):
+    mp = pytest.MonkeyPatch()
+    for k, v in env.items():
+        mp.setenv(k, v)
+    try:
+        return native.Context(0)
+    finally:
+        mp.undo()
+
+
+def _fixture(**env):
+    @pytest.fixture(scope="module")
+    def fx():
+        c = _context(**env)
+        yield c
+        c.close()
+    return fx
+
+
+split = _fixture(**FLOORS)                                       # gradient evaluations split
+unsplit = _fixture(**FLOORS, GPEMU_OZAKI_CHOL="0")               # the int8 path of the parent
+fp64 = _fixture(GPEMU_OZAKI="0")
+# only the top TRTRI level (or none) on the int8 cores: the TRTRI reuses the sweep's L21 planes
+top = _fixture(**{**FLOORS, "GPEMU_OZAKI_TRI_MIN": "2048"})
+splitv = _fixture(**FLOORS, GPEMU_OZAKI_CHOL="2")                # value-only evaluations too
+splitf = _fixture(**FLOORS, GPEMU_OZAKI_CHOL="3")                # and gpe_factor (L itself)
+
+
+def _scale(g):
+    return np.abs(g) + np.max(np.abs(g))
+
+
+CASES = {   # (variant, kernel, fit nugget, r): those of test_gpu_ozaki_tri.py
+    "gp4ml_fit": (orc.GP4ML, orc.STD, True, False),
+    "mucm_fix": (orc.MUCM, orc.STD, False, False),
+    "alt_r": (orc.GP4ML, orc.ALT, True, True),
+}
+DIMS = {1024: 3, 1100: 3, 1400: 5, 2900: 20}
+
+
+@functools.lru_cache(maxsize=None)
+def _problem(n, case):
+    """Data, hyperparameters (test_gpu_ozaki_tri.py's recipe) and the oracle's result, computed
+    once per (n, case) and shared; nothing modifies them."""
+    variant, kind, fitn, use_r = CASES[case]
+    d = DIMS[n]
+    X, f, H = orc.synthetic_problem(n, d, seed=n + d)
+    r = np.random.RandomState(n).uniform(1e-4, 1e-3, size=n) if use_r else None
+    hp = list(np.linspace(0.5, 1.1, d))
+    if fitn:
+        hp.append(3e-2 if kind == orc.ALT else 1e-3)
+    if variant == orc.GP4ML:
+        hp.append(1.1)
+    hp = np.array(hp)
+    nu_fixed = 5e-3 if not fitn else 0.0
+    ref = orc.objective_fast(X, f, H, hp, variant, kind, fitn, r=r, nu_fixed=nu_fixed)
+    return X, f, H, r, hp, nu_fixed, ref
+
+
+def _pairs(NB, min_tiles):
+    """Pairs of the TRTRI levels whose blocks have at least min_tiles tile rows."""
+    pairs, s = 0, 2
+    while s // 2 < NB:
+        if s // 2 >= min_tiles:
+            pairs += sum(1 for t0 in range(0, NB, s) if t0 + s // 2 < NB)
+        s *= 2
+    return pairs
+
+
+def _grad(c, n, case, count=None):
+    """One gradient objective of (n, case) on context c; with count, the k_oz_gemm launches
+    it made must be that many."""
+    variant, kind, _, _ = CASES[case]
+    X, f, H, r, hp, nu_fixed, ref = _problem(n, case)
+    c.set_data(X, f, H, r)
+    if count is None:
+        return c.objective(variant, kind, hp, nu_fixed=nu_fixed)
+    c.set_profiling(True)
+    try:
+        res = c.objective(variant, kind, hp, nu_fixed=nu_fixed)
+        assert c.ozaki_stats()["launches"] == count, (c.ozaki_stats()["launches"], count)
+    finally:
+        c.set_profiling(False)
+    return res
+
+
+def _against(n, case, res, res64, what):
+    _, _, _, _, _, _, ref = _problem(n, case)
+    llh, g, s2 = res
+    err64 = np.max(np.abs(g - res64[1]) / _scale(res64[1]))
+    err = np.max(np.abs(g - ref[1]) / _scale(ref[1]))
+    print(f"{what} n={n} {case}: grad vs fp64 {err64:.2e}, vs oracle {err:.2e}, "
+          f"llh vs fp64 {abs(llh - res64[0]):.2e}, vs oracle {abs(llh - ref[0]):.2e}, "
+          f"sigma2 rel {abs(s2 - ref[2]) / abs(ref[2]):.2e}")
+    assert err64 <= 1e-10, (err64, g, res64[1])
+    assert err <= 1e-7, (err, g, ref[1])
+    assert abs(llh - ref[0]) <= 1e-10 * max(1.0, abs(ref[0])), (llh, ref[0])
+    assert abs(s2 - ref[2]) <= 1e-10 * abs(ref[2]), (s2, ref[2])
+
+
+SHAPES = [(1024, "gp4ml_fit"), (1024, "mucm_fix"), (1400, "gp4ml_fit"), (1400, "mucm_fix"), (1400, "alt_r"),
+          (2900, "gp4ml_fit"), (2900, "mucm_fix")]
+
+
+@pytest.mark.parametrize("n,case", SHAPES, ids=[f"{n}-{k}" for n, k in SHAPES])
+def test_split_objective(split, fp64, n, case):
+    """Gradient objectives with the split sweep (one int8 launch more: S) against the fp64
+    context and the oracle."""
+    NB = (n + 127) // 128
+    res = _grad(split, n, case, count=1 + 2 * _pairs(NB, 4) + 1)
+    _against(n, case, res, _grad(fp64, n, case), "split")
+
+
+@pytest.mark.parametrize("n,case", [(1024, "gp4ml_fit"), (1400, "gp4ml_fit"), (2900, "gp4ml_fit"), (2900, "mucm_fix")])
+def test_split_reuses_l21_planes(top, fp64, n, case):
+    """GPEMU_OZAKI_TRI_MIN=2048: at n = 2900 only the top TRTRI pair (0, 16, 23) runs on the
+    int8 cores and takes L21's planes from the sweep; at 1024 and 1400 no TRTRI level does and
+    the sweep plans the pair for itself."""
+    NB = (n + 127) // 128
+    res = _grad(top, n, case, count=1 + 2 * _pairs(NB, 16) + 1)
+    _against(n, case, res, _grad(fp64, n, case), "top-only")
+
+
+@pytest.mark.parametrize("case", ["gp4ml_fit", "mucm_fix"])
+def test_below_floor_is_the_unsplit_sweep(split, unsplit, fp64, case):
+    """n = 1100: Rb = 128 is below the floor of 256, so the sweep stays whole and the result
+    equals the GPEMU_OZAKI_CHOL=0 context's bit for bit."""
+    n = 1100
+    a = _grad(split, n, case, count=1 + 2 * _pairs(9, 4))
+    b = _grad(unsplit, n, case, count=1 + 2 * _pairs(9, 4))
+    assert a[0] == b[0] and a[2] == b[2] and np.array_equal(a[1], b[1]), (a, b)
+    _against(n, case, a, _grad(fp64, n, case), "below floor")
+
+
+@pytest.mark.parametrize("n,case", [(1024, "gp4ml_fit"), (1400, "mucm_fix"), (1400, "alt_r"), (2900, "gp4ml_fit")])
+def test_value_only_split(splitv, fp64, n, case):
+    """Value-only calls (the augmented row carried through both phases and the launch between
+    them) and gradient calls on one context."""
+    variant, kind, _, _ = CASES[case]
+    X, f, H, r, hp, nu_fixed, ref = _problem(n, case)
+    NB = (n + 127) // 128
+    splitv.set_data(X, f, H, r)
+    splitv.set_profiling(True)
+    try:
+        llh, _, s2 = splitv.objective(variant, kind, hp, nu_fixed=nu_fixed, want_grad=False)
+        assert splitv.ozaki_stats()["launches"] == 1
+    finally:
+        splitv.set_profiling(False)
+    print(f"value-only n={n} {case}: llh vs oracle {abs(llh - ref[0]):.2e}, sigma2 rel {abs(s2 - ref[2]) / abs(ref[2]):.2e}")
+    assert abs(llh - ref[0]) <= 1e-10 * max(1.0, abs(ref[0])), (llh, ref[0])
+    assert abs(s2 - ref[2]) <= 1e-10 * abs(ref[2]), (s2, ref[2])
+    res = _grad(splitv, n, case, count=1 + 2 * _pairs(NB, 4) + 1)
+    _against(n, case, res, _grad(fp64, n, case), "after value-only")
+    llh2, _, _ = splitv.objective(variant, kind, hp, nu_fixed=nu_fixed, want_grad=False)
+    assert llh2 == llh, (llh2, llh)
+
+
+def test_plan_follows_set_data(fp64):
+    """One context through n = 1024 -> 1400 -> 1024: the split column, the plan of S and the
+    validity of L21's planes follow the data (at 1400 the TRTRI levels below the top one write
+    over the planes, so the top pair converts L21 again)."""
+    c = _context(**FLOORS)
+    try:
+        out = []
+        for n in (1024, 1400, 1024):
+            res = _grad(c, n, "gp4ml_fit", count=1 + 2 * _pairs((n + 127) // 128, 4) + 1)
+            _against(n, "gp4ml_fit", res, _grad(fp64, n, "gp4ml_fit"), "plan reuse")
+            out.append(res)
+    finally:
+        c.close()
+    assert out[0][0] == out[2][0] and np.array_equal(out[0][1], out[2][1]), (out[0], out[2])
+
+
+@pytest.mark.parametrize("n", [1024, 1400])
+def test_factor_of_split_sweep(splitf, fp64, n):
+    """See the module docstring (L itself)."""
+    X, f, H, _, hp, _, _ = _problem(n, "gp4ml_fit")
+    d = X.shape[1]
+    delta, nu = hp[:d], hp[d]
+    A, _ = orc.kernel_var_ref(X, delta, nu, orc.STD, True)
+    B = np.random.RandomState(n).standard_normal((n, 4))
+
+    def defect(c):
+        c.set_data(X, f, H)
+        c.factor(native.KERNEL_STD, delta, nu, 1.0, 0.0)
+        Xs = c.solve(B)
+        return float(np.max(np.abs(A @ Xs - B)) / (np.max(np.abs(A)) * np.max(np.abs(Xs)))), c.beta()
+
+    e8, b8 = defect(splitf)
+    e64, b64 = defect(fp64)
+    print(f"factor n={n}: solve residual split {e8:.3e} fp64 {e64:.3e}; beta diff {np.max(np.abs(b8 - b64)):.2e}")
+    assert e8 <= 4.0 * e64, (e8, e64)
+    assert np.max(np.abs(b8 - b64)) <= 1e-10 * (1.0 + np.max(np.abs(b64))), (b8, b64)
+
+
+# ---------------------------------------------------------------- hard hyperparameter points
+def _hard_names():
+    return [str(s) for s in np.load(GOLDEN)["names"]]
+
+
+@pytest.mark.parametrize("name", _hard_names())
+def test_hard_points_split(split, fp64, name):
+    """tests/golden/ozaki_hard.npz at n = 1100 (Rb = 128: unsplit) and n = 1600 (Rb = 640:
+    split), the assertion of test_gpu_ozaki_tri.py::test_hard_points:
+    E(int8 with split) <= 4 max(E(fp64 GPU), E(float64 CPU), n 2^-53)."""
+    z = np.load(GOLDEN)
+    rc = {k: z[f"{name}/{k}"] for k in ("n", "d", "seed", "hp", "variant", "kernel", "fit_nugget", "r_seed",
+                                        "nu_fixed")}
+    n, d, variant, kind = int(rc["n"]), int(rc["d"]), int(rc["variant"]), int(rc["kernel"])
+    hp, fitn, nu_fixed = rc["hp"], bool(rc["fit_nugget"]), float(rc["nu_fixed"])
+    X, f, H = orc.synthetic_problem(n, d, seed=int(rc["seed"]))
+    r = np.random.RandomState(int(rc["r_seed"])).uniform(1e-4, 1e-3, size=n) if int(rc["r_seed"]) >= 0 else None
+    llh_ref, g_ref = float(z[f"{name}/llh_ref"]), z[f"{name}/grad_ref"]
+
+    def E(res):
+        return (float(np.max(np.abs(res[1] - g_ref) / _scale(g_ref))),
+                abs(res[0] - llh_ref) / max(1.0, abs(llh_ref)))
+
+    NB = (n + 127) // 128
+    h = 1
+    while 2 * h < NB:
+        h *= 2
+    splits = 128 * (NB - h) >= 256
+    split.set_data(X, f, H, r)
+    fp64.set_data(X, f, H, r)
+    split.set_profiling(True)
+    try:
+        e8 = E(split.objective(variant, kind, hp, nu_fixed=nu_fixed))
+        assert split.ozaki_stats()["launches"] == 1 + 2 * _pairs(NB, 4) + (1 if splits else 0)
+    finally:
+        split.set_profiling(False)
+    e64 = E(fp64.objective(variant, kind, hp, nu_fixed=nu_fixed))
+    ecpu = E(orc.objective_fast(X, f, H, hp, variant, kind, fitn, r=r, nu_fixed=nu_fixed))
+    floor = n * 2.0 ** -53
+    print(f"HARD {name} n={n} split={splits} grad E: int8 {e8[0]:.2e} fp64 {e64[0]:.2e} cpu {ecpu[0]:.2e} | "
+          f"llh E: int8 {e8[1]:.2e} fp64 {e64[1]:.2e} cpu {ecpu[1]:.2e} | floor {floor:.2e}")
+    assert e8[0] <= 4.0 * max(e64[0], ecpu[0], floor), (e8, e64, ecpu)
+    assert e8[1] <= 4.0 * max(e64[1], ecpu[1], floor), (e8, e64, ecpu)
+
+
+# ---------------------------------------------------------------- not positive definite
+def _non_pd_problem(bad):
+    """n = 1024 (h 128 = 512), d = 10, gp4ml with the alt-nugget kernel and per-point variances
+    r: length scales of 0.05 make C = I to rounding, so A = sigma^2 (1 + nu^2) I + diag(r), and
+    r[bad] = -(sigma^2 (1 + nu^2) + 1) puts a pivot of -1 at row `bad` and leaves every other
+    one near 1.2."""
+    n, d = 1024, 10
+    X, f, H = orc.synthetic_problem(n, d, seed=7)
+    hp = np.array([0.05] * d + [3e-2, 1.1])
+    r = np.full(n, 1e-3)
+    r[bad] = -(1.1 ** 2 * (1.0 + 3e-2 ** 2) + 1.0)
+    return X, f, H, r, hp
+
+
+@pytest.mark.parametrize("bad", [100, 800], ids=["leading", "schur"])
+def test_not_positive_definite(split, unsplit, fp64, bad):
+    """(a) the failing pivot inside the leading 512 rows; (b) the leading block comfortably
+    positive definite and the failing pivot in the Schur complement.  Both decided by a wide
+    margin (checked here in float64 on the CPU); every context raises, and gives the oracle's
+    result on the next well-posed call."""
+    X, f, H, r, hp = _non_pd_problem(bad)
+    A, _ = orc.kernel_var_ref(X, hp[:10], hp[10], orc.ALT, True)
+    A = 1.1 ** 2 * A + np.diag(r)
+    L11 = np.linalg.cholesky(A[:bad, :bad])          # positive definite up to the bad row ...
+    assert np.min(np.diag(L11)) ** 2 >= 0.1
+    w = np.linalg.solve(L11, A[:bad, bad])
+    assert A[bad, bad] - w @ w <= -0.1                # ... and its pivot clearly negative
+    if bad >= 512:
+        assert np.min(np.diag(np.linalg.cholesky(A[:512, :512]))) ** 2 >= 0.1
+    assert orc.objective_fast(X, f, H, hp, orc.GP4ML, orc.ALT, True, r=r) is None
+    for c in (split, unsplit, fp64):
+        c.set_data(X, f, H, r)
+        with pytest.raises(native.NotPositiveDefinite):
+            c.objective(orc.GP4ML, orc.ALT, hp)
+        with pytest.raises(native.NotPositiveDefinite):
+            c.objective(orc.GP4ML, orc.ALT, hp, want_grad=False)
+    res64 = _grad(fp64, 1024, "gp4ml_fit")
+    _against(1024, "gp4ml_fit", _grad(split, 1024, "gp4ml_fit"), res64, "after non-PD")
+    _against(1024, "gp4ml_fit", _grad(unsplit, 1024, "gp4ml_fit"), res64, "after non-PD (unsplit)")
