@@ -22,11 +22,12 @@ def setup(config_file, datashuffle=True, scaleinputs=True):
     tv_conf = _model.TV_config(*config.tv_config)
     all_data = _model.All_Data(config.inputs, config.outputs, tv_conf, beliefs, par,
                                datashuffle, scaleinputs)
-    if beliefs.alt_nugget != "T":
-        K = _kernels.kernel(all_data.x_full.shape[1], par)
-    else:
+    alt = beliefs.alt_nugget == "T"
+    if alt:
         print("\n*** Using alternative nugget ***")
-        K = _kernels.kernel_alt_nug(all_data.x_full.shape[1], par)
+    if beliefs.kernel != "gaussian":
+        print("\n*** Using kernel", beliefs.kernel, "***")
+    K = _kernels.for_beliefs(beliefs.kernel, alt)(all_data.x_full.shape[1], par)
     x_T, y_T = all_data.choose_T()
     x_V, y_V = all_data.choose_V()
     training = _model.Data(x_T, y_T, basis, par, beliefs, K)

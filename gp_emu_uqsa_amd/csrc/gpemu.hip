@@ -18,6 +18,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <string>
 #include <vector>
 
@@ -387,9 +388,33 @@ int ensure_small(gpe_ctx* c, size_t doubles) {
 }
 
 // ------------------------------------------------------------------ launches
+// k_pairs<DMAX, FAM> for the padded width dm (one of launch_pairs' widths)
+template <int FAM>
+static void launch_pairs_fam(int dm, dim3 g, dim3 b, hipStream_t st, const PairArgs& a2) {
+  switch (dm) {
+    case 2: hipLaunchKernelGGL((k_pairs<2, FAM>), g, b, 0, st, a2); break;
+    case 4: hipLaunchKernelGGL((k_pairs<4, FAM>), g, b, 0, st, a2); break;
+    case 6: hipLaunchKernelGGL((k_pairs<6, FAM>), g, b, 0, st, a2); break;
+    case 8: hipLaunchKernelGGL((k_pairs<8, FAM>), g, b, 0, st, a2); break;
+    case 10: hipLaunchKernelGGL((k_pairs<10, FAM>), g, b, 0, st, a2); break;
+    case 12: hipLaunchKernelGGL((k_pairs<12, FAM>), g, b, 0, st, a2); break;
+    case 16: hipLaunchKernelGGL((k_pairs<16, FAM>), g, b, 0, st, a2); break;
+    case 20: hipLaunchKernelGGL((k_pairs<20, FAM>), g, b, 0, st, a2); break;
+    case 24: hipLaunchKernelGGL((k_pairs<24, FAM>), g, b, 0, st, a2); break;
+    default: hipLaunchKernelGGL((k_pairs<32, FAM>), g, b, 0, st, a2); break;
+  }
+}
+
+// The correlation family a.fam selects the instantiation (FAM_GAUSS: the kernels as they
+// were before the Matern families).
 int launch_pairs(gpe_ctx* c, const PairArgs& a, int nblocks) {
+  if (a.fam != FAM_GAUSS && a.fam != FAM_MATERN32 && a.fam != FAM_MATERN52)
+    return fail(c, GPE_ERR_ARG, "internal error: bad correlation family");
   if (a.d > 32) {   // any d: coordinates staged through LDS in chunks of 32
-    hipLaunchKernelGGL(k_pairs_wide, dim3(nblocks), dim3(256), 0, c->stream, a);
+    const dim3 g(nblocks), b(256);
+    if (a.fam == FAM_MATERN32) hipLaunchKernelGGL(k_pairs_wide<FAM_MATERN32>, g, b, 0, c->stream, a);
+    else if (a.fam == FAM_MATERN52) hipLaunchKernelGGL(k_pairs_wide<FAM_MATERN52>, g, b, 0, c->stream, a);
+    else hipLaunchKernelGGL(k_pairs_wide<FAM_GAUSS>, g, b, 0, c->stream, a);
     HIPCHK(c, hipGetLastError());
     return GPE_OK;
   }
@@ -403,20 +428,30 @@ int launch_pairs(gpe_ctx* c, const PairArgs& a, int nblocks) {
   PairArgs a2 = a;
   while (a2.csplit < 4 && nblocks * a2.csplit * 2 <= 512) a2.csplit *= 2;
   const dim3 g(nblocks * a2.csplit), b(256);
-  switch (dm) {
-    case 2: hipLaunchKernelGGL(k_pairs<2>, g, b, 0, c->stream, a2); break;
-    case 4: hipLaunchKernelGGL(k_pairs<4>, g, b, 0, c->stream, a2); break;
-    case 6: hipLaunchKernelGGL(k_pairs<6>, g, b, 0, c->stream, a2); break;
-    case 8: hipLaunchKernelGGL(k_pairs<8>, g, b, 0, c->stream, a2); break;
-    case 10: hipLaunchKernelGGL(k_pairs<10>, g, b, 0, c->stream, a2); break;
-    case 12: hipLaunchKernelGGL(k_pairs<12>, g, b, 0, c->stream, a2); break;
-    case 16: hipLaunchKernelGGL(k_pairs<16>, g, b, 0, c->stream, a2); break;
-    case 20: hipLaunchKernelGGL(k_pairs<20>, g, b, 0, c->stream, a2); break;
-    case 24: hipLaunchKernelGGL(k_pairs<24>, g, b, 0, c->stream, a2); break;
-    default: hipLaunchKernelGGL(k_pairs<32>, g, b, 0, c->stream, a2); break;
-  }
+  if (a.fam == FAM_MATERN32) launch_pairs_fam<FAM_MATERN32>(dm, g, b, c->stream, a2);
+  else if (a.fam == FAM_MATERN52) launch_pairs_fam<FAM_MATERN52>(dm, g, b, c->stream, a2);
+  else launch_pairs_fam<FAM_GAUSS>(dm, g, b, c->stream, a2);
   HIPCHK(c, hipGetLastError());
   return GPE_OK;
+}
+
+// The gradient contraction of gpe_objective for one correlation family: k_contract<.., FAM>
+// by bucket of d and P = q + 1, k_contract_wide<FAM> beyond the register-resident sizes.
+template <int FAM>
+static void launch_contract(gpe_ctx* c, int d, int P, dim3 gc, int nblk, const double* rdiag, int cs) {
+  const long long np = c->n_pad;
+  const int bucket = std::max(d, P);
+  if (d > 32 || P > 33) {   // any d and q: staged through LDS in chunks of 32
+    hipLaunchKernelGGL(k_contract_wide<FAM>, dim3(nblk), dim3(256), 0, c->stream, c->tr.A, np, c->dXw, d, c->dWa, np, P, (int)c->n, c->dcpart, c->dinfo, 0, 0ll, rdiag);
+  } else if (d == 10 && P <= 13) {   // the headline configuration: no padded dimensions
+    hipLaunchKernelGGL((k_contract<10, 13, FAM>), gc, dim3(256), 0, c->stream, c->tr.A, np, c->dXw, d, c->dWa, np, P, (int)c->n, c->dcpart, c->dinfo, 0, 0ll, rdiag, cs);
+  } else if (bucket <= 8) {
+    hipLaunchKernelGGL((k_contract<8, 9, FAM>), gc, dim3(256), 0, c->stream, c->tr.A, np, c->dXw, d, c->dWa, np, P, (int)c->n, c->dcpart, c->dinfo, 0, 0ll, rdiag, cs);
+  } else if (bucket <= 16) {
+    hipLaunchKernelGGL((k_contract<16, 17, FAM>), gc, dim3(256), 0, c->stream, c->tr.A, np, c->dXw, d, c->dWa, np, P, (int)c->n, c->dcpart, c->dinfo, 0, 0ll, rdiag, cs);
+  } else {
+    hipLaunchKernelGGL((k_contract<32, 33, FAM>), gc, dim3(256), 0, c->stream, c->tr.A, np, c->dXw, d, c->dWa, np, P, (int)c->n, c->dcpart, c->dinfo, 0, 0ll, rdiag, cs);
+  }
 }
 
 int launch_gemm_range(gpe_ctx* c, const Launch& L, hipStream_t st = nullptr) {
@@ -1260,8 +1295,21 @@ int scale_training(gpe_ctx* c, const double* delta) {
   return GPE_OK;
 }
 
+// A kernel code is the nugget convention (bit 0) OR-ed with the correlation family
+// (GPE_KERNEL_MATERN32 / GPE_KERNEL_MATERN52, 0 = Gaussian).
+constexpr int KERNEL_FAMILY_BITS = GPE_KERNEL_MATERN32 | GPE_KERNEL_MATERN52;
+inline bool kernel_ok(int kernel) {
+  return (kernel & ~(KERNEL_FAMILY_BITS | GPE_KERNEL_ALT_NUG)) == 0 &&
+         (kernel & KERNEL_FAMILY_BITS) != KERNEL_FAMILY_BITS;
+}
+inline bool kernel_alt(int kernel) { return (kernel & GPE_KERNEL_ALT_NUG) != 0; }
+// the device kernels' FAM_* of a valid kernel code
+inline int kernel_fam(int kernel) {
+  return (kernel & GPE_KERNEL_MATERN32) ? FAM_MATERN32 : (kernel & GPE_KERNEL_MATERN52) ? FAM_MATERN52 : FAM_GAUSS;
+}
+
 void kernel_consts(int kernel, double nu, bool predict, double* coff, double* cdiag) {
-  if (kernel == GPE_KERNEL_ALT_NUG) {
+  if (kernel_alt(kernel)) {
     *coff = 1.0;
     *cdiag = predict ? 1.0 + nu * nu : 1.0;
   } else {
@@ -1280,6 +1328,7 @@ int kbuild(gpe_ctx* c, int kernel, double nu, double s2, double rscale) {
   kernel_consts(kernel, nu, true, &coff, &cdiag);
   a.s2 = s2; a.coff = coff; a.cdiag = cdiag;
   a.rscale = rscale; a.r = (c->has_r && rscale != 0.0) ? c->dr : nullptr;
+  a.fam = kernel_fam(kernel);
   return launch_pairs(c, a, c->NB * (c->NB + 1) / 2);
 }
 
@@ -1603,6 +1652,18 @@ int factor_and_invert(gpe_ctx* c, int kernel, const double* delta, double nu, do
   CHK(build_plan(c, c->tr));
   // the objective's sweep may split (its gradient evaluations; the value-only ones when asked)
   CHK(potrf(c, c->tr, c->zaug_valid, objective && (invert || c->oz_chol >= 2)));
+  if (kernel_fam(kernel) != FAM_GAUSS) {
+    // Matern families: a pivot within the factorisation's backward error of zero is not
+    // positive definite (k_pivot_floor).  The Gaussian kernels keep the reference's LAPACK
+    // rule alone, to which their not-PD decisions are pinned.
+    double coff, cdiag;
+    kernel_consts(kernel, nu, true, &coff, &cdiag);
+    const double floor_rel = 4.0 * (double)c->n_pad * std::numeric_limits<double>::epsilon();
+    const double* r = (c->has_r && rscale != 0.0) ? c->dr : nullptr;
+    hipLaunchKernelGGL(k_pivot_floor, dim3((unsigned)((c->n + 255) / 256)), dim3(256), 0, c->stream, c->tr.A,
+                       c->n_pad, (int)c->n, floor_rel, s2 * cdiag, r, rscale, c->dinfo);
+    HIPCHK(c, hipGetLastError());
+  }
   ev_rec(c, 2);
   if (invert) {
     CHK(trtri(c, c->tr, true));   // (only the objective's gradient inverts here)
@@ -2437,7 +2498,7 @@ int gpe_objective(gpe_ctx* c, int32_t variant, int32_t kernel, const double* hp,
   const InflightGuard inflight(c->device);
   if (!hp || !llh_out) return fail(c, GPE_ERR_ARG, "null output");
   if (variant != GPE_GP4ML && variant != GPE_MUCM) return fail(c, GPE_ERR_ARG, "bad variant");
-  if (kernel != GPE_KERNEL_STD && kernel != GPE_KERNEL_ALT_NUG) return fail(c, GPE_ERR_ARG, "bad kernel");
+  if (!kernel_ok(kernel)) return fail(c, GPE_ERR_ARG, "bad kernel");
   const int d = c->d, q = c->q;
   const bool gp4ml = variant == GPE_GP4ML;
   const int base = gp4ml ? d + 1 : d;
@@ -2447,7 +2508,7 @@ int gpe_objective(gpe_ctx* c, int32_t variant, int32_t kernel, const double* hp,
   const double nu = fitnug ? hp[d] : nu_fixed;
   const double sigma = gp4ml ? hp[n_hp - 1] : 1.0;
   const double s2 = gp4ml ? sigma * sigma : 1.0;
-  const double rscale = (gp4ml && kernel == GPE_KERNEL_ALT_NUG) ? 1.0 : 0.0;
+  const double rscale = (gp4ml && kernel_alt(kernel)) ? 1.0 : 0.0;
   c->factor_valid = false;
   c->ainv_valid = false;
   c->x32_valid = false;
@@ -2458,10 +2519,13 @@ int gpe_objective(gpe_ctx* c, int32_t variant, int32_t kernel, const double* hp,
     c->oev_used = 0;
     c->oz_ms = c->oz_launches = c->oz_ops = c->oz_flops64 = 0.0;
   }
-  if (c->tiny && c->NB == 1 && d <= TINY_DM && q + 1 <= TINY_DM)
+  // (the one-launch paths are Gaussian only: a Matern objective takes the general path at
+  // every n, as GPEMU_TINY=0 does)
+  const bool one_launch = c->tiny && kernel_fam(kernel) == FAM_GAUSS;
+  if (one_launch && c->NB == 1 && d <= TINY_DM && q + 1 <= TINY_DM)
     return tiny_objective(c, gp4ml, kernel, hp, n_hp, fitnug, nu, s2, rscale, want_grad != 0, llh_out, grad_out,
                           sigma2_out);
-  if (c->tiny && c->NB >= 2 && c->NB <= SNB_MAXNB && d <= TINY_DM && q + 1 <= TINY_DM)
+  if (one_launch && c->NB >= 2 && c->NB <= SNB_MAXNB && d <= TINY_DM && q + 1 <= TINY_DM)
     return snb_objective(c, gp4ml, kernel, hp, n_hp, fitnug, nu, s2, rscale, want_grad != 0, llh_out, grad_out,
                          sigma2_out);
 
@@ -2529,24 +2593,16 @@ int gpe_objective(gpe_ctx* c, int32_t variant, int32_t kernel, const double* hp,
     CHK(skinny(c, true, c->tr.B, np, c->NB, c->NB, true, c->dR2, np, P, c->dWa, np));
     ev_rec(c, 6);
     // contraction; sum_i M_ii r_i for the std kernel's sigma gradient when r is set
-    const double* rdiag = (gp4ml && kernel == GPE_KERNEL_STD && c->has_r) ? c->dr : nullptr;
+    const double* rdiag = (gp4ml && !kernel_alt(kernel) && c->has_r) ? c->dr : nullptr;
     const int nblk = c->NB * (c->NB + 1) / 2;
-    const int bucket = std::max(d, P);
     int cs = 1;   // few tiles (small n): each tile's columns over up to 4 workgroups
     if (!(d > 32 || P > 33))
       while (cs < 4 && nblk * cs * 2 <= 512) cs *= 2;
     const dim3 gc(nblk * cs);
-    if (d > 32 || P > 33) {   // any d and q: staged through LDS in chunks of 32
-      hipLaunchKernelGGL(k_contract_wide, dim3(nblk), dim3(256), 0, c->stream, c->tr.A, np, c->dXw, d, c->dWa, np, P, (int)c->n, c->dcpart, c->dinfo, 0, 0ll, rdiag);
-    } else if (d == 10 && P <= 13) {   // the headline configuration: no padded dimensions
-      hipLaunchKernelGGL((k_contract<10, 13>), gc, dim3(256), 0, c->stream, c->tr.A, np, c->dXw, d, c->dWa, np, P, (int)c->n, c->dcpart, c->dinfo, 0, 0ll, rdiag, cs);
-    } else if (bucket <= 8) {
-      hipLaunchKernelGGL((k_contract<8, 9>), gc, dim3(256), 0, c->stream, c->tr.A, np, c->dXw, d, c->dWa, np, P, (int)c->n, c->dcpart, c->dinfo, 0, 0ll, rdiag, cs);
-    } else if (bucket <= 16) {
-      hipLaunchKernelGGL((k_contract<16, 17>), gc, dim3(256), 0, c->stream, c->tr.A, np, c->dXw, d, c->dWa, np, P, (int)c->n, c->dcpart, c->dinfo, 0, 0ll, rdiag, cs);
-    } else {
-      hipLaunchKernelGGL((k_contract<32, 33>), gc, dim3(256), 0, c->stream, c->tr.A, np, c->dXw, d, c->dWa, np, P, (int)c->n, c->dcpart, c->dinfo, 0, 0ll, rdiag, cs);
-    }
+    const int fam = kernel_fam(kernel);
+    if (fam == FAM_MATERN32) launch_contract<FAM_MATERN32>(c, d, P, gc, nblk, rdiag, cs);
+    else if (fam == FAM_MATERN52) launch_contract<FAM_MATERN52>(c, d, P, gc, nblk, rdiag, cs);
+    else launch_contract<FAM_GAUSS>(c, d, P, gc, nblk, rdiag, cs);
     HIPCHK(c, hipGetLastError());
     hipLaunchKernelGGL(k_reduce_rows, dim3(d + 3), dim3(256), 0, c->stream, c->dcpart, nblk * cs, d + 3, c->dcsum);
     HIPCHK(c, hipGetLastError());
@@ -2556,7 +2612,7 @@ int gpe_objective(gpe_ctx* c, int32_t variant, int32_t kernel, const double* hp,
     const double* red = c->hpin;
     double coff, cdiag;
     kernel_consts(kernel, nu, true, &coff, &cdiag);
-    small_grad(red, d, kernel == GPE_KERNEL_ALT_NUG, nu, fitnug, gp4ml, gscale, s2, coff, cdiag, n_hp,
+    small_grad(red, d, kernel_alt(kernel), nu, fitnug, gp4ml, gscale, s2, coff, cdiag, n_hp,
                grad_out, rdiag != nullptr);
   }
 done:
@@ -2592,7 +2648,7 @@ done:
 int gpe_factor(gpe_ctx* c, int32_t kernel, const double* delta, double nu, double s2, double r_scale) {
   CHK(check_ready(c));
   if (!delta) return fail(c, GPE_ERR_ARG, "null delta");
-  if (kernel != GPE_KERNEL_STD && kernel != GPE_KERNEL_ALT_NUG) return fail(c, GPE_ERR_ARG, "bad kernel");
+  if (!kernel_ok(kernel)) return fail(c, GPE_ERR_ARG, "bad kernel");
   c->factor_valid = false;
   c->ainv_valid = false;
   c->x32_valid = false;
@@ -2970,6 +3026,7 @@ static int posterior_impl(gpe_ctx* c, int64_t m, const double* Xs, const double*
   std::vector<double> Kinv = small_trinv(Kq, q);
   double coff, cdiag;
   kernel_consts(c->f_kernel, c->f_nu, true, &coff, &cdiag);
+  const int fam = kernel_fam(c->f_kernel);   // the resident factor's correlation family
   const double s2 = sigma * sigma;
 
   // workspace for the largest chunk (the first): K* (np x mp) and V (np x mp), the chunk's
@@ -3020,6 +3077,7 @@ static int posterior_impl(gpe_ctx* c, int64_t m, const double* Xs, const double*
       a.xr = c->dXw; a.xc = c->dXsw; a.out = c->dW1; a.ld = np; a.d = d;
       a.nr_valid = (int)c->n; a.nc_valid = (int)mc; a.mt = c->NB; a.nt = mt; a.mode = 0;
       a.s2 = 1.0; a.coff = coff; a.cdiag = cdiag; a.rscale = 0.0; a.r = nullptr;
+      a.fam = fam;
       CHK(launch_pairs(c, a, c->NB * mt));
     }
     // Y = K*^T [gamma, G]  (mp x P)
@@ -3187,6 +3245,7 @@ static int posterior_impl(gpe_ctx* c, int64_t m, const double* Xs, const double*
         a.xr = c->dXsw; a.xc = c->dXsw; a.out = dC; a.ld = mp; a.d = d;
         a.nr_valid = (int)mc; a.nc_valid = (int)mc; a.mt = mt; a.nt = mt; a.mode = 1 | 2 | 4;
         a.s2 = s2; a.coff = coff; a.cdiag = cdiag; a.rscale = 0.0; a.r = nullptr;
+        a.fam = fam;
         if (rnew) {
           CHK(grow(c, &c->dRn, &c->rn_cap, (size_t)mp));
           // synchronous copy: hpin is about to be reused for T below
@@ -3253,6 +3312,7 @@ static int posterior_impl(gpe_ctx* c, int64_t m, const double* Xs, const double*
           a.xr = c->dXall + b0 * d; a.xc = c->dXall + a0 * d; a.out = dst; a.ld = mtot; a.d = d;
           a.nr_valid = (int)mcb; a.nc_valid = (int)mca; a.mt = mtb; a.nt = mta; a.mode = dg ? (1 | 2 | 4) : 0;
           a.s2 = s2; a.coff = coff; a.cdiag = cdiag; a.rscale = 0.0; a.r = nullptr;
+          a.fam = fam;
           if (dg && rnew) {
             CHK(grow(c, &c->dRn, &c->rn_cap, (size_t)mpa));
             // (synchronous copy; padded rows do not read r)
@@ -3280,6 +3340,7 @@ static int posterior_impl(gpe_ctx* c, int64_t m, const double* Xs, const double*
         a.xr = c->dXall + a0 * d; a.xc = c->dXall + b0 * d; a.out = dC; a.ld = mpa; a.d = d;
         a.nr_valid = (int)mca; a.nc_valid = (int)mcb; a.mt = mta; a.nt = mtb; a.mode = dg ? (1 | 2 | 4) : 0;
         a.s2 = s2; a.coff = coff; a.cdiag = cdiag; a.rscale = 0.0; a.r = nullptr;
+        a.fam = fam;
         if (dg && rnew) {
           CHK(grow(c, &c->dRn, &c->rn_cap, (size_t)mpa));
           HIPCHK(c, hipMemcpy(c->dRn, rnew + a0, (size_t)mca * sizeof(double), hipMemcpyHostToDevice));
@@ -3507,6 +3568,7 @@ int gpe_kernel_var(gpe_ctx* c, int32_t kernel, const double* delta, int32_t d, d
                    double* A_out) {
   if (!c) return GPE_ERR_ARG;
   if (!delta || !X || !A_out || m <= 0 || d <= 0) return fail(c, GPE_ERR_ARG, "bad kernel_var args");
+  if (!kernel_ok(kernel)) return fail(c, GPE_ERR_ARG, "bad kernel");
   HIPCHK(c, hipSetDevice(c->device));
   CHK(ensure_shape_bufs(c, d, 1));
   const long long mp = ((m + TILE - 1) / TILE) * TILE;
@@ -3539,6 +3601,7 @@ int gpe_kernel_var(gpe_ctx* c, int32_t kernel, const double* delta, int32_t d, d
     double coff, cdiag;
     kernel_consts(kernel, nu, predict != 0, &coff, &cdiag);
     a.s2 = 1.0; a.coff = coff; a.cdiag = cdiag; a.rscale = r_scale; a.r = dr;
+    a.fam = kernel_fam(kernel);
     rc = launch_pairs(c, a, mt * (mt + 1) / 2);
     if (rc == GPE_OK) {
       hipError_t e = hipStreamSynchronize(c->stream);
@@ -3556,9 +3619,10 @@ int gpe_kernel_var(gpe_ctx* c, int32_t kernel, const double* delta, int32_t d, d
   return rc;
 }
 
-int gpe_kernel_grad(gpe_ctx* c, const double* delta, int32_t d, int64_t m, const double* X,
-                    const double* col, double col_scale, double pre, double* G_out) {
-  if (!c) return GPE_ERR_ARG;
+// gpe_kernel_grad / gpe_kernel_grad_k for the correlation family fam (FAM_*): with a column
+// the family's derivative factor g is written, without one its correlation rho
+static int kernel_grad_fam(gpe_ctx* c, int fam, const double* delta, int32_t d, int64_t m, const double* X,
+                           const double* col, double col_scale, double pre, double* G_out) {
   if (!delta || !X || !G_out || m <= 0 || d <= 0) return fail(c, GPE_ERR_ARG, "bad kernel_grad args");
   HIPCHK(c, hipSetDevice(c->device));
   CHK(ensure_shape_bufs(c, d, 1));
@@ -3590,6 +3654,7 @@ int gpe_kernel_grad(gpe_ctx* c, const double* delta, int32_t d, int64_t m, const
     a.mt = mt; a.nt = mt; a.mode = 1 | 4 | 8;
     a.s2 = 1.0; a.coff = pre; a.cdiag = 0.0; a.rscale = 0.0; a.r = nullptr;
     a.fcol = dcol; a.fscale = col_scale;
+    a.fam = fam; a.wg = col ? 1 : 0;
     rc = launch_pairs(c, a, mt * (mt + 1) / 2);
     if (rc == GPE_OK) {
       hipError_t e = hipStreamSynchronize(c->stream);
@@ -3605,6 +3670,19 @@ int gpe_kernel_grad(gpe_ctx* c, const double* delta, int32_t d, int64_t m, const
   if (dout) hipFree(dout);
   if (dcol) hipFree(dcol);
   return rc;
+}
+
+int gpe_kernel_grad(gpe_ctx* c, const double* delta, int32_t d, int64_t m, const double* X,
+                    const double* col, double col_scale, double pre, double* G_out) {
+  if (!c) return GPE_ERR_ARG;
+  return kernel_grad_fam(c, FAM_GAUSS, delta, d, m, X, col, col_scale, pre, G_out);
+}
+
+int gpe_kernel_grad_k(gpe_ctx* c, int32_t kernel, const double* delta, int32_t d, int64_t m, const double* X,
+                      const double* col, double col_scale, double pre, double* G_out) {
+  if (!c) return GPE_ERR_ARG;
+  if (!kernel_ok(kernel)) return fail(c, GPE_ERR_ARG, "bad kernel");
+  return kernel_grad_fam(c, kernel_fam(kernel), delta, d, m, X, col, col_scale, pre, G_out);
 }
 
 int gpe_lhc_maximin(gpe_ctx* c, int32_t N, int64_t n, int32_t dim, const double* designs, int64_t ne,
@@ -3674,6 +3752,7 @@ int gpe_kernel_covar(gpe_ctx* c, int32_t kernel, const double* delta, int32_t d,
   if (!c) return GPE_ERR_ARG;
   if (!delta || !XT || !XV || !C_out || n <= 0 || m <= 0 || d <= 0)
     return fail(c, GPE_ERR_ARG, "bad kernel_covar args");
+  if (!kernel_ok(kernel)) return fail(c, GPE_ERR_ARG, "bad kernel");
   HIPCHK(c, hipSetDevice(c->device));
   CHK(ensure_shape_bufs(c, d, 1));
   // compute C^T (m x n, column-major == n x m row-major)
@@ -3705,6 +3784,7 @@ int gpe_kernel_covar(gpe_ctx* c, int32_t kernel, const double* delta, int32_t d,
     double coff, cdiag;
     kernel_consts(kernel, nu, true, &coff, &cdiag);
     a.s2 = 1.0; a.coff = coff; a.cdiag = cdiag; a.rscale = 0.0; a.r = nullptr;
+    a.fam = kernel_fam(kernel);
     rc = launch_pairs(c, a, a.mt * a.nt);
     if (rc == GPE_OK) {
       hipError_t e = hipStreamSynchronize(c->stream);

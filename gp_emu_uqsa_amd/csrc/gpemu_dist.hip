@@ -1604,7 +1604,7 @@ void contract_launch(gpe_dist* h, const double* slab, long long lds, long long r
   const dim3 g(nblk);
   const int nv = (int)h->n;
   if (d > 32 || Pc > 33)
-    hipLaunchKernelGGL(k_contract_wide, g, dim3(256), 0, h->stream, slab, lds, h->dXw, d, wpart, np, q1, nv, h->cpart, h->dinfo, blk0, row0, rdiag);
+    hipLaunchKernelGGL(k_contract_wide<FAM_GAUSS>, g, dim3(256), 0, h->stream, slab, lds, h->dXw, d, wpart, np, q1, nv, h->cpart, h->dinfo, blk0, row0, rdiag);
   else if (d == 10 && Pc <= 13)
     hipLaunchKernelGGL((k_contract<10, 13>), g, dim3(256), 0, h->stream, slab, lds, h->dXw, d, wpart, np, q1, nv, h->cpart, h->dinfo, blk0, row0, rdiag);
   else if (d == 20 && Pc <= 21)   // BASELINE configs[3]
@@ -1839,6 +1839,13 @@ int gpe_dist_objective(gpe_dist* h, int32_t variant, int32_t kernel, const doubl
   if (!hp || !llh_out) return dfail(h, GPE_ERR_ARG, "null argument");
   if (want_grad && !grad_out) return dfail(h, GPE_ERR_ARG, "grad_out is NULL");
   if (variant != GPE_GP4ML && variant != GPE_MUCM) return dfail(h, GPE_ERR_ARG, "bad variant");
+  // a valid Matern code (one family bit, with or without the alt-nugget bit)
+  const int fam_bits = kernel & (GPE_KERNEL_MATERN32 | GPE_KERNEL_MATERN52);
+  if ((kernel & ~(GPE_KERNEL_ALT_NUG | fam_bits)) == 0 &&
+      (fam_bits == GPE_KERNEL_MATERN32 || fam_bits == GPE_KERNEL_MATERN52))
+    return dfail(h, GPE_ERR_UNSUPPORTED,
+                 "the row-block distributed objective has Gaussian correlations only: train a Matern "
+                 "kernel on one GPU or with replicas");
   if (kernel != GPE_KERNEL_STD && kernel != GPE_KERNEL_ALT_NUG) return dfail(h, GPE_ERR_ARG, "bad kernel");
   DCHK_HIP(h, hipSetDevice(h->device));
   // a previous call that failed inside group_sweep may have left chain work queued on the

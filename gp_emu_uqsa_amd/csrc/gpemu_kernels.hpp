@@ -38,6 +38,9 @@ typedef double d4 __attribute__((ext_vector_type(4)));
 // mode bit3: zero diagonal (the reference's dA matrices, _emulatorkernels.py:53-71)
 // fcol: if set, every entry is also multiplied by ((fcol[gi] - fcol[gj]) * fscale)^2
 // (dA/d(2 log delta_i): the per-dimension squared distance, :53-63)
+// fam: correlation family (FAM_*), chosen by launch_pairs as a template argument.
+// wg: write the derivative factor g(s) in place of rho(s) (gpe_kernel_grad_k with a
+// column; for FAM_GAUSS g = rho and the flag is not read).
 // ---------------------------------------------------------------------------
 struct PairArgs {
   const double* xr;   // rows point set, row-major [*, d]
@@ -50,7 +53,33 @@ struct PairArgs {
   const double* fcol = nullptr;
   double fscale = 0.0;
   int csplit = 1;     // k_pairs: workgroups per tile, each a contiguous share of its columns
+  int fam = 0;        // FAM_GAUSS / FAM_MATERN32 / FAM_MATERN52
+  int wg = 0;
 };
+
+// Correlation families, with s = sum_k ((x_k - x'_k) / delta_k)^2 and r = sqrt(s):
+//   FAM_GAUSS     rho = exp(-s),                                  g = rho
+//   FAM_MATERN32  rho = (1 + sqrt3 r) exp(-sqrt3 r),              g = (3/2) exp(-sqrt3 r)
+//   FAM_MATERN52  rho = (1 + sqrt5 r + (5/3) s) exp(-sqrt5 r),    g = (5/6)(1 + sqrt5 r) exp(-sqrt5 r)
+// g is the factor of d rho / d(2 log delta_k) = g u_k^2, u_k = (x_k - x'_k) / delta_k (the
+// part exp_save plays in the reference's grad_delta_A).  One sqrt and one exp, then FMAs;
+// nothing divides by r, so coincident points (s = 0) give rho = 1 and g = 3/2, 5/6.
+enum : int { FAM_GAUSS = 0, FAM_MATERN32 = 1, FAM_MATERN52 = 2 };
+
+template <int FAM>
+__device__ inline void matern_rho_g(double s, double& rho, double& g) {
+  static_assert(FAM == FAM_MATERN32 || FAM == FAM_MATERN52, "Matern families only");
+  const double t = (FAM == FAM_MATERN32 ? 1.7320508075688772 : 2.23606797749979) * sqrt(s);
+  const double e = exp(-t);
+  if (FAM == FAM_MATERN32) {
+    rho = fma(t, e, e);
+    g = 1.5 * e;
+  } else {
+    const double pe = fma(t, e, e);   // (1 + sqrt5 r) exp(-sqrt5 r)
+    rho = fma((5.0 / 3.0) * s, e, pe);
+    g = (5.0 / 6.0) * pe;
+  }
+}
 
 __device__ inline void tri_decode(int e, int& ti, int& tj) {
   int r = (int)((sqrtf(8.0f * (float)e + 1.0f) - 1.0f) * 0.5f);
@@ -64,7 +93,7 @@ __device__ inline void tri_decode(int e, int& ti, int& tj) {
 // no per-dimension branch; the padded terms are fma(0, 0, s) = s, so the sum over
 // k = 0..d-1 is bit-identical to the unpadded one.  Padding, diagonal and zeroed
 // entries are selected after the general formula (no divergent paths per entry).
-template <int DMAX>
+template <int DMAX, int FAM = FAM_GAUSS>
 static __global__ void __launch_bounds__(256) k_pairs(PairArgs a) {
   __shared__ double xs_col[TILE * DMAX];
   int ti, tj;
@@ -100,7 +129,14 @@ static __global__ void __launch_bounds__(256) k_pairs(PairArgs a) {
       const double df = xi[k] - xs_col[c * DMAX + k];
       s = fma(df, df, s);
     }
-    double v = pre * exp(-s);
+    double v;
+    if constexpr (FAM == FAM_GAUSS) {
+      v = pre * exp(-s);
+    } else {
+      double rho, g;
+      matern_rho_g<FAM>(s, rho, g);
+      v = pre * (a.wg ? g : rho);
+    }
     if (a.fcol) {
       const double df = (fi - a.fcol[gj]) * a.fscale;
       v *= df * df;
@@ -120,6 +156,7 @@ static __global__ void __launch_bounds__(256) k_pairs(PairArgs a) {
 // time, each thread keeping the running squared distances of its 64 columns.  The
 // sum over k = 0..d-1 is taken in the same order with the same fma as k_pairs.
 constexpr int PW_CH = 32;
+template <int FAM = FAM_GAUSS>
 static __global__ void __launch_bounds__(256) k_pairs_wide(PairArgs a) {
   __shared__ double xs_col[TILE * PW_CH];
   int ti, tj;
@@ -164,7 +201,14 @@ static __global__ void __launch_bounds__(256) k_pairs_wide(PairArgs a) {
   for (int u = 0; u < TILE / 2; ++u) {
     const int c = h + 2 * u;
     const int gj = tj * TILE + c;
-    double v = pre * exp(-s[u]);
+    double v;
+    if constexpr (FAM == FAM_GAUSS) {
+      v = pre * exp(-s[u]);
+    } else {
+      double rho, g;
+      matern_rho_g<FAM>(s[u], rho, g);
+      v = pre * (a.wg ? g : rho);
+    }
     if (a.fcol) {
       const double df = (fi - a.fcol[gj]) * a.fscale;
       v *= df * df;
@@ -1948,6 +1992,29 @@ static __global__ void __launch_bounds__(256) k_colnorm2(const double* V, long l
   if (lane == 0) out[j] = s;
 }
 
+// Pivot floor of the Matern families.  The Cholesky stops at a pivot <= 0 or
+// NaN, as LAPACK does; a pivot that is zero in exact arithmetic (two coincident points
+// without a nugget) comes out as a rounding residue of either sign, so that rule alone
+// decides by summation order.  After the sweep, pivot j = L(j,j)^2 is held against
+// floor_rel * A(j,j), A(j,j) = dconst + rcoef r_j the diagonal the K-build wrote: at or below
+// it (or NaN) the matrix is not positive definite to within the factorisation's own backward
+// error (|dA_jj| <= (n + 1) eps A_jj), and *info becomes the lowest such j + 1 unless the
+// sweep already stopped at an earlier column.  Values of L are not touched.
+static __global__ void k_pivot_floor(const double* L, long long ld, int n, double floor_rel, double dconst,
+                                     const double* r, double rcoef, int* info) {
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n) return;
+  const double l = L[(long long)j * (ld + 1)];
+  const double ajj = dconst + (r ? rcoef * r[j] : 0.0);
+  if (l * l > floor_rel * ajj) return;
+  int old = *info;
+  while (old != GEMM_WAIT_TIMEOUT && (old == 0 || old > j + 1)) {
+    const int prev = atomicCAS(info, old, j + 1);
+    if (prev == old) break;
+    old = prev;
+  }
+}
+
 // Leave-one-out mean and variance (gpe_loo) from the sweep's outputs: asq(i) = (A^-1)_ii and
 // Y = A^-1 [f - H beta, H Kq^-T] (column-major, ld = ldy; Kq Kq^T = H^T A^-1 H), so
 //   P_ii = asq(i) - sum_{p >= 1} Y(i, p)^2,  (P f)_i = Y(i, 0),
@@ -1974,13 +2041,15 @@ static __global__ void k_loo_finish(const double* asq, const double* Y, long lon
 //   off-diagonal (i>j):  accE += M E,  acc_k += M E (x_ik - x_jk)^2 / delta_k^2
 //   diagonal:            accT += M(i,i)
 // E recomputed from the scaled points (no n x n exp cache, no n x n dA).
+// FAM (a Matern family): accE += M rho, acc_k += M g (x_ik - x_jk)^2 / delta_k^2, rho and g
+// from one sqrt and one exp (matern_rho_g); everything else as for FAM_GAUSS.
 // part[blk][0:d] = acc_k, [d] = accE, [d+1] = accT, [d+2] = accR = sum_i M(i,i) r_i
 // (rdiag non-null: the reference's sigma gradient subtracts diag(r) from A for every
 // kernel, _emulatoroptimise.py:476-478, while make_A adds r only for alt-nugget)
 // Slabs: the launch covers lower tiles blk0 .. blk0 + gridDim.x - 1 (row-major tile
 // order) and Ainv holds global rows row0 .. (A^-1 row gi at Ainv[gi - row0]).
 // ---------------------------------------------------------------------------
-template <int DMAX, int QMAX>
+template <int DMAX, int QMAX, int FAM = FAM_GAUSS>
 static __global__ void __launch_bounds__(256) k_contract(const double* Ainv, long long lda,
                                                   const double* xw, int d,
                                                   const double* Wa, long long ldw, int q1,
@@ -2054,10 +2123,19 @@ static __global__ void __launch_bounds__(256) k_contract(const double* Ainv, lon
         const bool dg = gj == gi;
         accT += dg ? mij : 0.0;
         accR += dg ? mij * ri : 0.0;
-        const double me = dg ? 0.0 : mij * exp(-s);
-        accE += me;
+        if constexpr (FAM == FAM_GAUSS) {
+          const double me = dg ? 0.0 : mij * exp(-s);
+          accE += me;
 #pragma unroll
-        for (int k = 0; k < DMAX; ++k) acc[k] = fma(me, df2[k], acc[k]);
+          for (int k = 0; k < DMAX; ++k) acc[k] = fma(me, df2[k], acc[k]);
+        } else {
+          double rho, g;
+          matern_rho_g<FAM>(s, rho, g);
+          accE += dg ? 0.0 : mij * rho;
+          const double mg = dg ? 0.0 : mij * g;
+#pragma unroll
+          for (int k = 0; k < DMAX; ++k) acc[k] = fma(mg, df2[k], acc[k]);
+        }
       }
     }
   }
@@ -2089,6 +2167,7 @@ static __global__ void __launch_bounds__(256) k_contract(const double* Ainv, lon
 // groups of 16 (distances, M(i,j), then M E times the chunk's squared differences);
 // passes beyond the first recompute E (d / 32 passes in all).
 constexpr int CW_CH = 32;
+template <int FAM = FAM_GAUSS>
 static __global__ void __launch_bounds__(256) k_contract_wide(const double* Ainv, long long lda,
                                                              const double* xw, int d,
                                                              const double* Wa, long long ldw, int q1,
@@ -2172,8 +2251,15 @@ static __global__ void __launch_bounds__(256) k_contract_wide(const double* Ainv
           accT += (valid && dg) ? m[u] : 0.0;
           accR += (valid && dg) ? m[u] * ri : 0.0;
         }
-        sd[u] = (valid && !dg) ? m[u] * exp(-sd[u]) : 0.0;   // now M E
-        if (a0 == 0) accE += sd[u];
+        if constexpr (FAM == FAM_GAUSS) {
+          sd[u] = (valid && !dg) ? m[u] * exp(-sd[u]) : 0.0;   // now M E
+          if (a0 == 0) accE += sd[u];
+        } else {
+          double rho, g;
+          matern_rho_g<FAM>(sd[u], rho, g);
+          if (a0 == 0) accE += (valid && !dg) ? m[u] * rho : 0.0;
+          sd[u] = (valid && !dg) ? m[u] * g : 0.0;   // now M g
+        }
       }
       // this pass's dimensions: acc_k += M E (x_ik - x_jk)^2
       __syncthreads();

@@ -25,6 +25,9 @@ CONFIG_REQUIRED = ("beliefs", "inputs", "outputs", "tv_config", "delta_bounds", 
                    "sigma_bounds", "tries", "constraints")
 BELIEFS_REQUIRED = ("active", "output", "basis_str", "basis_inf", "beta", "delta", "sigma", "nugget",
                     "fix_nugget", "mucm")
+# optional beliefs key `kernel`: the correlation family (absent: gaussian, the reference's
+# only one; the reference ignores the key like any other it does not know)
+KERNEL_FAMILIES = ("gaussian", "matern32", "matern52")
 
 
 def _die(msg):
@@ -193,12 +196,17 @@ class Beliefs:
         self.mucm = str(b["mucm"]).strip().split(" ")[0]
         if self.mucm == "T" and self.alt_nugget == "T":
             _die("WARNING: mucm T cannot be used with alt_nugget T")
+        self.kernel = str(b["kernel"]).strip().split(" ")[0] if "kernel" in b else "gaussian"
+        if self.kernel not in KERNEL_FAMILIES:
+            _die("WARNING: kernel should be one of " + ", ".join(KERNEL_FAMILIES))
         self.input_minmax = literal(b["input_minmax"]) if "input_minmax" in b else []
 
     def final_beliefs(self, E, final=False):
         """Write the updated beliefs '<beliefs>-N[f]' (reference :217-250).
         input_minmax is written with plain floats (the reference's NumPy-2
-        output writes np.float64(...) reprs; both forms are read back)."""
+        output writes np.float64(...) reprs; both forms are read back).  A ``kernel``
+        line is written only for a non-Gaussian family, so the files of every
+        configuration the reference knows stay as they were."""
         suffix = "f" if final else ""
         filename = E.config.beliefs + "-" + str(E.tv_conf.no_of_trains) + suffix
         print("New beliefs to file", filename)
@@ -220,6 +228,8 @@ class Beliefs:
             "mucm " + str(self.mucm),
             "input_minmax " + str([[float(a), float(b)] for a, b in E.all_data.input_minmax]),
         ]
+        if self.kernel != "gaussian":
+            lines.append("kernel " + self.kernel)
         try:
             with open(filename, "w") as fh:
                 fh.write("\n".join(lines) + "\n")

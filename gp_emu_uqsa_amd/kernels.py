@@ -8,6 +8,11 @@
 gpe_kernel_covar / gpe_kernel_grad); the objective never materialises them -- it
 builds the covariance and contracts the gradient inside gpe_objective.  ``kind`` is
 the C-ABI kernel code.
+
+Beyond the reference's Gaussian correlation exp(-s), s = sum(((x-x')/delta)^2), there are
+the Matern 3/2 and 5/2 families (``family``; beliefs key ``kernel``), each with both
+nugget conventions: the same interface, ``kind`` the nugget code OR-ed with the family's,
+the gradients through gpe_kernel_grad_k.  ``for_beliefs`` picks the class.
 """
 from __future__ import annotations
 
@@ -25,6 +30,7 @@ _np.set_printoptions(suppress=True)
 
 class _GaussianBase:
     kind = native.KERNEL_STD
+    family = "gaussian"
 
     def __init__(self, dim, par):
         self.d = _np.asarray(par.delta, dtype=float)
@@ -77,20 +83,22 @@ class _GaussianBase:
         exp_save (alt: no (1-nu)), zero diagonal; X is the input column, exp_save that of
         the preceding var()."""
         Xv, dv = self._exp_state()
-        pre = s2 if self.kind == native.KERNEL_ALT_NUG else (1.0 - self.n) * s2
-        return native.default_context().kernel_grad(dv, Xv, _np.asarray(X, dtype=float).ravel(),
-                                                    1.0 / float(self.d[di]), pre)
+        pre = s2 if self.kind & native.KERNEL_ALT_NUG else (1.0 - self.n) * s2
+        return self._kernel_grad(dv, Xv, _np.asarray(X, dtype=float).ravel(), 1.0 / float(self.d[di]), pre)
 
     def grad_nugget_A(self, X, s2):
         """dA/d(2 log nu) (reference :66-71): -nu s2 / 2 exp_save off the diagonal;
         alt-nugget (:139-144): s2 nu^2 on the diagonal only."""
         X = _np.asarray(X, dtype=float)
-        if self.kind == native.KERNEL_ALT_NUG:
+        if self.kind & native.KERNEL_ALT_NUG:
             f = _np.zeros((X.shape[0], X.shape[0]))
             _np.fill_diagonal(f, (self.n ** 2) * s2)
             return f
         Xv, dv = self._exp_state()
-        return native.default_context().kernel_grad(dv, Xv, None, 0.0, 0.5 * (-self.n) * s2)
+        return self._kernel_grad(dv, Xv, None, 0.0, 0.5 * (-self.n) * s2)
+
+    def _kernel_grad(self, delta, X, col, col_scale, pre):
+        return native.default_context().kernel_grad(delta, X, col, col_scale, pre)
 
     def covar(self, XT, XV):
         return native.default_context().kernel_covar(self.kind, self.d, float(self.n), XT, XV)
@@ -104,3 +112,48 @@ class kernel(_GaussianBase):
 class kernel_alt_nug(_GaussianBase):
     """exp(-sum((x-x')/delta)^2), nugget^2 added on the diagonal."""
     kind = native.KERNEL_ALT_NUG
+
+
+class _MaternBase(_GaussianBase):
+    """The Gaussian classes with exp(-s) replaced by the family's correlation rho(s): the
+    nugget and sigma rules are unchanged, and the delta derivative is
+    pre ((x_k - x_l)/delta_di)^2 g(s) with g the family's derivative factor (gpe_kernel_grad_k)."""
+
+    def _kernel_grad(self, delta, X, col, col_scale, pre):
+        return native.default_context().kernel_grad_k(self.kind, delta, X, col, col_scale, pre)
+
+
+class kernel_matern32(_MaternBase):
+    """(1-nugget) (1 + sqrt(3) r) exp(-sqrt(3) r), r = sqrt(sum(((x-x')/delta)^2)), nugget
+    added back on the diagonal."""
+    kind = native.KERNEL_STD | native.KERNEL_MATERN32
+    family = "matern32"
+
+
+class kernel_matern32_alt_nug(_MaternBase):
+    """(1 + sqrt(3) r) exp(-sqrt(3) r), nugget^2 added on the diagonal."""
+    kind = native.KERNEL_ALT_NUG | native.KERNEL_MATERN32
+    family = "matern32"
+
+
+class kernel_matern52(_MaternBase):
+    """(1-nugget) (1 + sqrt(5) r + (5/3) r^2) exp(-sqrt(5) r), nugget added back on the
+    diagonal."""
+    kind = native.KERNEL_STD | native.KERNEL_MATERN52
+    family = "matern52"
+
+
+class kernel_matern52_alt_nug(_MaternBase):
+    """(1 + sqrt(5) r + (5/3) r^2) exp(-sqrt(5) r), nugget^2 added on the diagonal."""
+    kind = native.KERNEL_ALT_NUG | native.KERNEL_MATERN52
+    family = "matern52"
+
+
+_CLASSES = {("gaussian", False): kernel, ("gaussian", True): kernel_alt_nug,
+            ("matern32", False): kernel_matern32, ("matern32", True): kernel_matern32_alt_nug,
+            ("matern52", False): kernel_matern52, ("matern52", True): kernel_matern52_alt_nug}
+
+
+def for_beliefs(family, alt_nugget):
+    """The kernel class of a beliefs file: its ``kernel`` family x ``alt_nugget``."""
+    return _CLASSES[(family, bool(alt_nugget))]

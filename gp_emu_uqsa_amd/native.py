@@ -22,6 +22,8 @@ GPE_OK = 0
 GPE_NOT_PD = 1
 KERNEL_STD = 0
 KERNEL_ALT_NUG = 1
+KERNEL_MATERN32 = 0x10   # correlation family, OR-ed with the nugget code (0: Gaussian)
+KERNEL_MATERN52 = 0x20
 GP4ML = 0
 MUCM = 1
 
@@ -59,6 +61,8 @@ SIGNATURES = {
     "gpe_kernel_covar": (_ct.c_int, [_VP, _ct.c_int32, _D, _ct.c_int32, _ct.c_double, _ct.c_int64,
                                      _D, _ct.c_int64, _D, _D]),
     "gpe_kernel_grad": (_ct.c_int, [_VP, _D, _ct.c_int32, _ct.c_int64, _D, _D, _ct.c_double, _ct.c_double, _D]),
+    "gpe_kernel_grad_k": (_ct.c_int, [_VP, _ct.c_int32, _D, _ct.c_int32, _ct.c_int64, _D, _D, _ct.c_double,
+                                      _ct.c_double, _D]),
     "gpe_lhc_maximin": (_ct.c_int, [_VP, _ct.c_int32, _ct.c_int64, _ct.c_int32, _D, _ct.c_int64, _D,
                                     _ct.POINTER(_ct.c_int64)]),
     "gpe_cholesky": (_ct.c_int, [_VP, _ct.c_int64, _D, _D, _D, _D, _D]),
@@ -415,6 +419,21 @@ class Context:
         out = _np.zeros((m, m))
         self._check(self.lib.gpe_kernel_grad(self._h, _ptr(delta), d, m, _ptr(X), _ptr(cc),
                                              float(col_scale), float(pre), _ptr(out)), "gpe_kernel_grad")
+        return out
+
+    def kernel_grad_k(self, kernel, delta, X, col, col_scale, pre):
+        """kernel_grad for the correlation family of `kernel`: pre * ((col_k - col_l)
+        col_scale)^2 * g(s) with the family's derivative factor g, or pre * rho(s) without
+        col; zero diagonal, m x m."""
+        X = _f64(X)
+        if X.ndim == 1:
+            X = X.reshape(-1, 1)
+        m, d = X.shape
+        delta = _f64(delta).ravel()
+        cc = None if col is None else _f64(col, (m,))
+        out = _np.zeros((m, m))
+        self._check(self.lib.gpe_kernel_grad_k(self._h, int(kernel), _ptr(delta), d, m, _ptr(X), _ptr(cc),
+                                               float(col_scale), float(pre), _ptr(out)), "gpe_kernel_grad_k")
         return out
 
     def lhc_maximin(self, designs, fextra=None):

@@ -38,13 +38,22 @@ import numpy as np
 
 from .model import upload_training
 
-__all__ = ["setup", "sense_table", "Sensitivity"]
+__all__ = ["setup", "sense_table", "Sensitivity", "NonGaussianKernel"]
+
+
+class NonGaussianKernel(ValueError):
+    """The emulator's correlation family has no closed-form sensitivity integrals here."""
 
 
 def setup(emul, m, v, case="case2"):
     """Sensitivity instance for emulator `emul`, input means m and variances v
     (reference sensitivityfunctions.py:7-54)."""
     print("\n*** Initialising Sensitivity class ***")
+    family = getattr(emul.K, "family", "gaussian")
+    if family != "gaussian":
+        raise NonGaussianKernel(
+            "sensitivity analysis needs a gaussian kernel: its integrals are closed forms of "
+            "exp(-((x-x')/delta)^2), and this emulator's kernel is " + family)
     if not isinstance(m, list) or not isinstance(v, list):
         print("ERROR: 2nd and 3rd arguments must be lists of floats. "
               "Return None.")

@@ -48,8 +48,32 @@ enum gpe_status {
     GPE_ERR_UNSUPPORTED = -5
 };
 
-/* kernel family: _emulatorkernels.py:10 (kernel) and :83 (kernel_alt_nug) */
-enum gpe_kernel { GPE_KERNEL_STD = 0, GPE_KERNEL_ALT_NUG = 1 };
+/* kernel: the nugget convention, _emulatorkernels.py:10 (kernel) and :83 (kernel_alt_nug),
+ * OR-ed with a correlation family (an addition within ABI 10; the reference has only the
+ * Gaussian one, which is family bits 0, so the codes 0 and 1 mean what they always did).
+ * With s = sum_k ((x_k - x'_k) / delta_k)^2 and r = sqrt(s):
+ *   Gaussian    rho = exp(-s)
+ *   MATERN32    rho = (1 + sqrt(3) r) exp(-sqrt(3) r)
+ *   MATERN52    rho = (1 + sqrt(5) r + (5/3) s) exp(-sqrt(5) r)
+ * The off-diagonal is (1 - nu) rho (std) or rho (alt); the diagonal, the r / s2 rules and
+ * the nugget and sigma derivatives are those of the Gaussian kernels with exp(-s) read as
+ * rho.  Accepted by gpe_objective, gpe_factor (and through the resident factor by gpe_beta,
+ * gpe_loo, gpe_solve, gpe_posterior, gpe_noise_sample, gpe_posterior_pivchol),
+ * gpe_kernel_var, gpe_kernel_covar and gpe_kernel_grad_k.  A Matern objective always takes
+ * the general (multi-launch) path.  gpe_dist_objective answers GPE_ERR_UNSUPPORTED to a
+ * Matern code; gpe_sense_pairs / gpe_gauss_transform are Gaussian closed forms.  Any other
+ * bit, or both family bits, is GPE_ERR_ARG.
+ * GPE_NOT_PD for a Matern code: besides a non-positive or NaN pivot, a pivot at or below
+ * 4 n_pad eps times its diagonal entry of A (n_pad = n rounded up to 128), i.e. within the
+ * factorisation's own backward error of zero: a matrix made singular by coincident points
+ * without a nugget is refused whatever the rounding of its zero pivot.  The Gaussian codes keep
+ * the plain rule, whose decisions are pinned to the reference's. */
+enum gpe_kernel {
+    GPE_KERNEL_STD = 0,
+    GPE_KERNEL_ALT_NUG = 1,
+    GPE_KERNEL_MATERN32 = 0x10,
+    GPE_KERNEL_MATERN52 = 0x20
+};
 /* objective: _emulatoroptimise.py:412 (gp4ml) and :305 (mucm) */
 enum gpe_variant { GPE_GP4ML = 0, GPE_MUCM = 1 };
 
@@ -179,6 +203,17 @@ int gpe_kernel_var(gpe_ctx* ctx, int32_t kernel, const double* delta, int32_t d,
  * form, s2 nu^2 I, is diagonal and built by the host.) */
 int gpe_kernel_grad(gpe_ctx* ctx, const double* delta, int32_t d, int64_t m, const double* X,
                     const double* col, double col_scale, double pre, double* G_out);
+
+/* gpe_kernel_grad for any correlation family (an addition within ABI 10); only the family
+ * bits of `kernel` are read.  With col:
+ *   G(k,l) = pre * ((col_k - col_l) * col_scale)^2 * g(s_kl),
+ * g the family's derivative factor, d rho / d(2 log delta_i) = g(s) ((x_i - x'_i) / delta_i)^2:
+ * exp(-s) (Gaussian), (3/2) exp(-sqrt(3) r) (MATERN32), (5/6)(1 + sqrt(5) r) exp(-sqrt(5) r)
+ * (MATERN52).  Without col: G(k,l) = pre * rho(s_kl) (grad_nugget_A).  Zero diagonal.
+ * Family bits 0 return the bits gpe_kernel_grad returns for the same arguments. */
+int gpe_kernel_grad_k(gpe_ctx* ctx, int32_t kernel, const double* delta, int32_t d, int64_t m,
+                      const double* X, const double* col, double col_scale, double pre,
+                      double* G_out);
 
 /* The oLHC generator's selection statistic (design_inputs.py:54-64): for each of the N
  * candidate designs (designs: N x n x dim row-major, design k at k*n*dim),
