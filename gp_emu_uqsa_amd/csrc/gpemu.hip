@@ -29,6 +29,7 @@
 #include "gpemu_snb.hpp"
 #include "gpemu_ozaki.hpp"
 #include "gpemu_pivchol.hpp"
+#include "gpemu_host_alloc.hpp"
 
 using namespace gpe;
 
@@ -39,6 +40,20 @@ thread_local std::string g_create_error;
 constexpr int MAX_PROBS = 1 << 16;
 constexpr int AUX_DESC_BASE = 1 << 15;
 constexpr int ADHOC_DESC_BASE = MAX_PROBS - 64;
+
+// Descriptor slots of the GEMMs outside the cached plans (adhoc_gemm), each named for its
+// owner.  Live within one call: gpe_noise_sample and gpe_posterior_pivchol run the posterior
+// first (ADHOC_POST_V, then the ADHOC_COV pair, re-uploaded per chunk and per block) and then
+// their own slot; ADHOC_PIVCHOL is uploaded once and launched after every panel of that call.
+// The test and bench GEMMs stand alone.
+enum AdhocSlot {
+  ADHOC_POST_V = ADHOC_DESC_BASE + 0,     // posterior: V = L^-1 K* of one chunk
+  ADHOC_COV = ADHOC_DESC_BASE + 1,        // cov_block: -s2 V^T V, then +s2 T T^T (two slots)
+  ADHOC_NOISE = ADHOC_DESC_BASE + 3,      // gpe_noise_sample: the draws L U^T
+  ADHOC_PIVCHOL = ADHOC_DESC_BASE + 4,    // gpe_posterior_pivchol: the trailing update S -= W W^T
+  ADHOC_TEST = ADHOC_DESC_BASE + 8,       // gpe_test_gemm
+  ADHOC_BENCH = ADHOC_DESC_BASE + 16,     // gpe_bench_gemm
+};
 
 struct Launch {       // one grouped GEMM launch of the cached schedule
   int kind;           // 0: <0,0>, 1: <1,0>, 2: <1,1>, 3: <0,1>, 4: <0,0> fused Cholesky step
@@ -146,7 +161,7 @@ struct gpe_ctx {
   double* dT2 = nullptr;     // P^2
   double* dcpart = nullptr;  // contraction partials
   size_t cpart_cap = 0;
-  size_t invd_cap = 0, csum_cap = 0, gram_cap = 0;   // dinvdelta (d), dcsum (d + 3), dgram / dT2 (P^2)
+  size_t invd_cap = 0, csum_cap = 0, gram_cap = 0, t2_cap = 0;   // dinvdelta (d), dcsum (d + 3), dgram, dT2 (P^2)
   double* dcsum = nullptr;   // d+3
   GemmProb* dprobs = nullptr;
   unsigned* dtiles = nullptr;    // tile lists: training plan [0, cap/2), aux plan [cap/2, cap)
@@ -155,12 +170,12 @@ struct gpe_ctx {
   // posterior workspace
   double* dW1 = nullptr;
   double* dW2 = nullptr;
-  size_t w_cap = 0;
+  size_t w1_cap = 0, w2_cap = 0;
   double* dW3 = nullptr;     // full posterior covariance
   size_t w3_cap = 0;
   double* dXs = nullptr;
   double* dXsw = nullptr;
-  size_t xs_cap = 0;
+  size_t xs_cap = 0, xsw_cap = 0;
   double* dsmall = nullptr;  // generic small device scratch
   double* dtiny = nullptr;   // n <= 128 path: X's image, W, the helpers' partials
   int tiny_ek = 0, tiny_eg = 0;   // k_tiny's call ordinals (its sync words in dinfo[1..4])
@@ -327,45 +342,42 @@ int fail(gpe_ctx* c, int code, const std::string& msg) {
   return code;
 }
 
+// the device allocator of realloc_buf / grow_to (gpemu_host_alloc.hpp)
+struct HipAlloc {
+  int malloc(void** p, size_t bytes) { return (int)hipMalloc(p, bytes); }
+  void free(void* p) { (void)hipFree(p); }
+};
+
+int alloc_failed(gpe_ctx* c, int e, size_t bytes) {
+  return fail(c, GPE_ERR_ALLOC, std::string("hipMalloc failed: ") + hipGetErrorString((hipError_t)e) + " (" +
+                                    std::to_string(bytes) + " bytes)");
+}
+
+// replace *p by a fresh buffer of count elements (contents not kept; NULL on failure)
 template <typename T>
 int dalloc(gpe_ctx* c, T** p, size_t count) {
-  if (*p) {
-    (void)hipFree(*p);
-    *p = nullptr;
-  }
-  if (count == 0) return GPE_OK;
-  hipError_t e = hipMalloc((void**)p, count * sizeof(T));
-  if (e != hipSuccess) {
-    *p = nullptr;
-    return fail(c, GPE_ERR_ALLOC, std::string("hipMalloc failed: ") + hipGetErrorString(e) +
-                                      " (" + std::to_string(count * sizeof(T)) + " bytes)");
-  }
-  return GPE_OK;
+  HipAlloc al;
+  const int e = realloc_buf(al, p, count);
+  return e ? alloc_failed(c, e, count * sizeof(T)) : GPE_OK;
+}
+
+// grow a device buffer to at least need elements (contents not kept): the one way the
+// context's buffers grow (grow_to: a failed allocation leaves no stale capacity behind)
+template <class T>
+int grow_buf(gpe_ctx* c, T** p, size_t* cap, size_t need) {
+  HipAlloc al;
+  const int e = grow_to(al, p, cap, need);
+  return e ? alloc_failed(c, e, need * sizeof(T)) : GPE_OK;
 }
 
 // the per-dimension and per-basis-column device buffers, grown to the shape in use: the
 // reference takes any d and any basis (_emulatorkernels.py:39-50), and so does the library
 // (d > 32 and P > 33 run the LDS-staged wide kernels)
-// (each cap is zeroed before its reallocation: a failed dalloc leaves the buffer NULL, and
-// the next call must not find the old, larger cap and skip it)
 int ensure_shape_bufs(gpe_ctx* c, int d, int P) {
-  if ((size_t)d > c->invd_cap) {
-    c->invd_cap = 0;
-    CHK(dalloc(c, &c->dinvdelta, (size_t)d));
-    c->invd_cap = (size_t)d;
-  }
-  if ((size_t)d + 3 > c->csum_cap) {
-    c->csum_cap = 0;
-    CHK(dalloc(c, &c->dcsum, (size_t)d + 3));
-    c->csum_cap = (size_t)d + 3;
-  }
-  const size_t pp = (size_t)P * P;
-  if (pp > c->gram_cap) {
-    c->gram_cap = 0;
-    CHK(dalloc(c, &c->dgram, pp));
-    CHK(dalloc(c, &c->dT2, pp));
-    c->gram_cap = pp;
-  }
+  CHK(grow_buf(c, &c->dinvdelta, &c->invd_cap, (size_t)d));
+  CHK(grow_buf(c, &c->dcsum, &c->csum_cap, (size_t)d + 3));
+  CHK(grow_buf(c, &c->dgram, &c->gram_cap, (size_t)P * P));
+  CHK(grow_buf(c, &c->dT2, &c->t2_cap, (size_t)P * P));
   return GPE_OK;
 }
 
@@ -380,11 +392,7 @@ int ensure_pinned(gpe_ctx* c, size_t doubles) {
 }
 
 int ensure_small(gpe_ctx* c, size_t doubles) {
-  if (doubles <= c->small_cap) return GPE_OK;
-  c->small_cap = 0;
-  CHK(dalloc(c, &c->dsmall, doubles));
-  c->small_cap = doubles;
-  return GPE_OK;
+  return grow_buf(c, &c->dsmall, &c->small_cap, doubles);
 }
 
 // ------------------------------------------------------------------ launches
@@ -721,6 +729,34 @@ GemmProb mkprob(const double* A, long long lda, const double* B, long long ldb, 
   p.cpost = nullptr;
   p.kti_mul = 1; p.kti_off = 0;
   return p;
+}
+
+// GEMMs outside the cached plans: g[i] (k_gemm instance `kind` as Launch::kind, every tile of
+// p in the implicit order) takes descriptor slot + i.  The descriptors are uploaded in one
+// copy on the context's stream, then each launch is issued in order, or with `out` handed
+// back (out[i]) for a caller that launches later or more than once.  standalone (the test and
+// bench GEMMs): a blocking upload and k_gemm's CDEF instance where the problem takes it.
+struct AdhocGemm { int kind; GemmProb p; };
+int adhoc_gemm(gpe_ctx* c, AdhocSlot slot, const std::vector<AdhocGemm>& g, Launch* out = nullptr,
+               bool standalone = false) {
+  std::vector<GemmProb> d;
+  for (const AdhocGemm& e : g) {
+    d.push_back(e.p);
+    d.back().tile_begin = 0;
+    d.back().ntiles = prob_tiles(e.p);
+  }
+  if (standalone)
+    HIPCHK(c, hipMemcpy(c->dprobs + slot, d.data(), d.size() * sizeof(GemmProb), hipMemcpyHostToDevice));
+  else
+    HIPCHK(c, hipMemcpyAsync(c->dprobs + slot, d.data(), d.size() * sizeof(GemmProb), hipMemcpyHostToDevice,
+                             c->stream));
+  for (size_t i = 0; i < g.size(); ++i) {
+    Launch L{g[i].kind, (int)slot + (int)i, 1, d[i].ntiles, 0.0};
+    L.cdef = standalone && gemm_cdef(d[i]);
+    if (out) out[i] = L;
+    else CHK(launch_gemm_range(c, L));
+  }
+  return GPE_OK;
 }
 
 // Build the (n_pad-dependent, data-independent) GEMM schedule and upload it.
@@ -1230,11 +1266,10 @@ int build_plan(gpe_ctx* c, Fact& F) {
   // tile lists: each workspace owns half of the list array
   const size_t half = pl.tiles.size() + 1;
   const size_t need = 2 * half;
-  if (need > c->tiles_cap) {
+  const bool regrow = need > c->tiles_cap;
+  CHK(grow_buf(c, &c->dtiles, &c->tiles_cap, need));
+  if (regrow) {
     // growing invalidates the other plan's uploaded lists: force its rebuild
-    c->tiles_cap = 0;
-    CHK(dalloc(c, &c->dtiles, need));
-    c->tiles_cap = need;
     Fact& other = (&F == &c->tr) ? c->aux : c->tr;
     other.plan = Plan();
   }
@@ -1338,16 +1373,6 @@ int kbuild(gpe_ctx* c, int kernel, double nu, double s2, double rscale) {
 // Every launcher of a workspace's schedule first makes sure it is built: growing the
 // tile-list array for one workspace's plan resets the other's (build_plan), e.g. the
 // aux plan of gpe_noise_sample between gpe_factor and a later on-demand TRTRI / LAUUM.
-// grow a device buffer to at least need elements (contents not kept)
-template <class T>
-int grow_buf(gpe_ctx* c, T** p, size_t* cap, size_t need) {
-  if (need <= *cap) return GPE_OK;
-  *cap = 0;
-  CHK(dalloc(c, p, need));
-  *cap = need;
-  return GPE_OK;
-}
-
 int oz_prepare(gpe_ctx* c, Fact& F);
 int chol_schur(gpe_ctx* c, Fact& F, hipStream_t st, bool with_aug);
 
@@ -1469,12 +1494,7 @@ int skinny(gpe_ctx* c, bool transposed, const double* M, long long ldm, int ntr,
   const int chk = std::max(1, std::min(SK_CH, (kext + want - 1) / want));
   const int nch = (kext + chk - 1) / chk;
   const long long rows = (long long)nit * TILE;
-  const size_t need = (size_t)nch * rows * P;
-  if (need > c->skp_cap) {
-    c->skp_cap = 0;
-    CHK(dalloc(c, &c->dskp, need));
-    c->skp_cap = need;
-  }
+  CHK(grow_buf(c, &c->dskp, &c->skp_cap, (size_t)nch * rows * P));
   SkinnyArgs a;
   a.M = M; a.ldm = ldm; a.R = R; a.ldr = ldr; a.part = c->dskp; a.ldp = rows;
   a.pstride = rows * P; a.P = P; a.ntr = ntr; a.lower = lower ? 1 : 0; a.nit = nit;
@@ -1513,12 +1533,7 @@ int skinny_t_sq(gpe_ctx* c, const double* M, long long ldm, int nt, long long n_
   const int nch = (nt + chk - 1) / chk;
   const long long rows = (long long)nt * TILE;
   if (ldy != rows) return fail(c, GPE_ERR_STATE, "skinny: output ld mismatch");
-  const size_t need = (size_t)nch * rows * (pc + 1);
-  if (need > c->skp_cap) {
-    c->skp_cap = 0;
-    CHK(dalloc(c, &c->dskp, need));
-    c->skp_cap = need;
-  }
+  CHK(grow_buf(c, &c->dskp, &c->skp_cap, (size_t)nch * rows * (pc + 1)));
   SkinnyArgs a;
   a.M = M; a.ldm = ldm; a.R = R; a.ldr = ldr; a.part = c->dskp; a.ldp = rows;
   a.pstride = rows * (pc + 1); a.P = pc; a.ntr = nt; a.lower = 1; a.nit = nt;
@@ -2672,16 +2687,6 @@ int gpe_factor(gpe_ctx* c, int32_t kernel, const double* delta, double nu, doubl
 }
 
 // ---------------------------------------------------------------- sensitivity
-// grow a device buffer to at least `need` doubles
-static int grow(gpe_ctx* c, double** p, size_t* cap, size_t need) {
-  if (need <= *cap) return GPE_OK;
-  *cap = 0;
-  CHK(dalloc(c, p, need));
-  *cap = need;
-  return GPE_OK;
-}
-
-
 // moduli of the posterior's int8 product: 16 for precision 64 (53-bit operands at n_pad <=
 // 16384, as the objective's), for precision 32 the fewest whose operands keep >= 24 bits (the
 // fp32 significand: 8 at n_pad <= 16384) -- exact products of operands as precise as fp32's
@@ -2806,16 +2811,16 @@ int gpe_sense_pairs(gpe_ctx* c, int32_t J, const double* w, const double* u, int
   const int NB = c->NB;
   CHK(ensure_ainv(c));
   const long long ldp = (long long)J * (1 + p * p);
-  CHK(grow(c, &c->dSU, &c->su_cap, (size_t)J * np));
-  CHK(grow(c, &c->dSZ, &c->sz_cap, (size_t)np * p));
-  CHK(grow(c, &c->dSW, &c->sw_cap, (size_t)J * d));
+  CHK(grow_buf(c, &c->dSU, &c->su_cap, (size_t)J * np));
+  CHK(grow_buf(c, &c->dSZ, &c->sz_cap, (size_t)np * p));
+  CHK(grow_buf(c, &c->dSW, &c->sw_cap, (size_t)J * d));
   // column slices: enough workgroups to fill the chip (>= 2048) when J is small
   const int ct = wide ? SPW_CT : SP_CT;
   const int nct = (int)((n + ct - 1) / ct);
   const int CS = std::max(1, std::min(nct, (2048 + NB * J - 1) / (NB * J)));
   const int cslice = ((nct + CS - 1) / CS) * ct;
-  CHK(grow(c, &c->dSpart, &c->spart_cap, (size_t)NB * CS * 4 * ldp));
-  CHK(grow(c, &c->dSout, &c->sout_cap, (size_t)ldp));
+  CHK(grow_buf(c, &c->dSpart, &c->spart_cap, (size_t)NB * CS * 4 * ldp));
+  CHK(grow_buf(c, &c->dSout, &c->sout_cap, (size_t)ldp));
   CHK(ensure_pinned(c, std::max<size_t>({(size_t)J * np, (size_t)np * p, (size_t)J * d, (size_t)ldp}) + 64));
   // w, u (J x n_pad, zero padded), Z (n_pad x p column-major): staged one at a time
   std::memcpy(c->hpin, w, (size_t)J * d * sizeof(double));
@@ -2874,7 +2879,7 @@ int gpe_gauss_transform(gpe_ctx* c, int64_t m, int32_t ns, const int32_t* dims, 
   const long long n = c->n;
   // device layout: a (n) | Y (m x ns) | out (m)
   const size_t need = (size_t)n + (size_t)m * ns + (size_t)m;
-  CHK(grow(c, &c->dSout, &c->sout_cap, need));
+  CHK(grow_buf(c, &c->dSout, &c->sout_cap, need));
   CHK(ensure_pinned(c, need + 64));
   std::memcpy(c->hpin, a, (size_t)n * sizeof(double));
   std::memcpy(c->hpin + n, Y, (size_t)m * ns * sizeof(double));
@@ -2950,60 +2955,87 @@ int gpe_loo(gpe_ctx* c, double sigma, double* mean_out, double* var_out, double*
   return GPE_OK;
 }
 
-// Posterior mean and variance (gpe_posterior).  With keep_dev the full variance stays
-// on the device (ld = m rounded up to TILE, identity padding) and var_out is not
-// written: in c->dW3 for m <= 16384 (one chunk), else in dev_full, whose lower
-// triangle of blocks is formed chunk pair by chunk pair; rnew (m, device copy made
-// here) adds s2 * rnew_scale * rnew to its diagonal: Dnew's own r/s2 in Dnew.A
-// (_emulatorclasses.py:572-575, :625).
-static int posterior_impl(gpe_ctx* c, int64_t m, const double* Xs, const double* Hs, const double* beta,
-                          double sigma, int32_t full_var, int32_t precision, double* mean_out, double* var_out,
-                          const double* rnew, double rnew_scale, bool keep_dev, double* dev_full = nullptr) {
-  CHK(check_ready(c));
-  if (!c->factor_valid) return fail(c, GPE_ERR_STATE, "no resident factor (call gpe_factor)");
-  if (m <= 0 || !Xs || !Hs || !beta || !mean_out || (!var_out && !keep_dev))
-    return fail(c, GPE_ERR_ARG, "bad posterior args");
-  if (keep_dev && (!full_var || (m > 16384 && !dev_full)))
-    return fail(c, GPE_ERR_ARG, "device-resident variance: full, and beyond one chunk a device target");
-  if (precision != 64 && precision != 32) return fail(c, GPE_ERR_ARG, "precision must be 64 or 32");
-  if (precision == 32 && full_var) return fail(c, GPE_ERR_UNSUPPORTED, "precision 32 is for the diagonal variance");
-  CHK(ensure_linv(c));
-  const bool f32 = precision == 32;
-  const bool ozp = c->oz_on && c->n_pad >= std::min(c->oz_min_np, OZ_POST_MIN_NP) &&
-                   c->n_pad <= OZ_POST_MAX_NP;   // V on the int8 cores (posterior_oz)
-  const int d = c->d, q = c->q, P = q + 1;
-  const long long np = c->n_pad;
-  const long long CHUNK = full_var ? 16384 : 8192;
-  if (f32 && !ozp && !c->x32_valid) {
-    // fp32 copy of L^-1 (the full square: the GEMM reads only k <= its row tile)
-    const size_t need = (size_t)np * np;
-    if (need > c->x32_cap) {
-      if (c->dX32) (void)hipFree(c->dX32);
-      c->dX32 = nullptr;
-      HIPCHK(c, hipMalloc((void**)&c->dX32, need * sizeof(float)));
-      c->x32_cap = need;
+}  // extern "C"
+
+// ------------------------------------------------------------------ posterior
+// Posterior mean and variance at m points for the resident factor: gpe_posterior, and the
+// covariance that gpe_noise_sample and gpe_posterior_pivchol go on from (posterior_impl).
+namespace {
+
+// points per chunk: the full variance forms one chunk pair's block at a time, the diagonal
+// pipeline holds two chunks in flight
+constexpr long long POST_CHUNK_FULL = 16384, POST_CHUNK_DIAG = 8192;
+
+inline long long pad_tile(long long m) { return ((m + TILE - 1) / TILE) * TILE; }
+
+// where the variance goes (on the device: column-major, ld = m rounded up to TILE, identity
+// padding)
+enum class PostVar {
+  DIAG,       // its diagonal to var_out (m)
+  FULL,       // m x m to var_out
+  FULL_DW3,   // m x m left in c->dW3: one chunk (m <= POST_CHUNK_FULL)
+  FULL_DEV,   // m x m into dev_out, beyond one chunk: the lower triangle of chunk blocks
+};
+
+struct PostReq {
+  int64_t m = 0;
+  const double* Xs = nullptr;     // points (m x d)
+  const double* Hs = nullptr;     // their basis (m x q)
+  const double* beta = nullptr;
+  double sigma = 0.0;
+  int precision = 64;             // 32: the diagonal variance only
+  double* mean_out = nullptr;
+  PostVar var = PostVar::DIAG;
+  double* var_out = nullptr;      // host (DIAG, FULL)
+  double* dev_out = nullptr;      // device (FULL_DEV)
+  // rnew (m, host; the device copy is made here) adds s2 * rnew_scale * rnew to the full
+  // variance's diagonal: Dnew's own r/s2 in Dnew.A (_emulatorclasses.py:572-575, :625)
+  const double* rnew = nullptr;
+  double rnew_scale = 0.0;
+};
+
+// One chunk of points as cov_block reads it
+struct CovSide {
+  const double* X;   // scaled points (mp x d)
+  const double* V;   // L^-1 K* (np x mp, ld np)
+  double* T;         // T Kq^-T (mp x kq column-major, ld ldt)
+  long long ldt;
+  long long s0, mc, mp;   // first point, points, points padded to TILE
+};
+
+// One call: the request, its sizes, what setup() and workspace() derive, and the steps.
+struct Posterior : PostReq {
+  gpe_ctx* c;
+  const bool full, f32, ozp;   // full variance; fp32 product; V on the int8 cores (posterior_oz)
+  const int d, q, P, kq;       // kq: q rounded up to the GEMM's K step
+  const long long np, CHUNK;
+  const bool big;              // a full variance of more than one chunk
+  const long long mtot, mp0;   // m padded; the largest chunk (the first) padded
+  int fam = 0;                 // the resident factor's correlation family
+  double coff = 0.0, cdiag = 0.0, s2 = 0.0;
+  std::vector<double> Kinv;    // Kq^-1, Kq Kq^T = H^T A^-1 H
+  size_t rs = 0;               // one result slot: Y (mp x P), then the column norms
+  double *pin_in[2] = {}, *pin_out[2] = {};   // pinned staging: two slots of points, two of results
+
+  Posterior(gpe_ctx* ctx, const PostReq& r)
+      : PostReq(r), c(ctx), full(var != PostVar::DIAG), f32(precision == 32),
+        ozp(c->oz_on && c->n_pad >= std::min(c->oz_min_np, OZ_POST_MIN_NP) && c->n_pad <= OZ_POST_MAX_NP),
+        d(c->d), q(c->q), P(q + 1), kq(((q + 15) / 16) * 16), np(c->n_pad),
+        CHUNK(full ? POST_CHUNK_FULL : POST_CHUNK_DIAG), big(full && m > CHUNK), mtot(pad_tile(m)),
+        mp0(pad_tile(std::min<long long>(CHUNK, m))) {}
+
+  // Setup: the fp32 copy of L^-1 where the fp32 product needs it, [gamma, G] =
+  // A^-1 [f - H beta, H] (in dWa; L^-1 [..] in dZ), Kq and its inverse, the kernel's constants.
+  int setup() {
+    if (f32 && !ozp && !c->x32_valid) {
+      // fp32 copy of L^-1 (the full square: the GEMM reads only k <= its row tile)
+      CHK(grow_buf(c, &c->dX32, &c->x32_cap, (size_t)np * np));
+      hipLaunchKernelGGL(k_to_f32, dim3((unsigned)((np * np + 255) / 256)), dim3(256), 0, c->stream, c->tr.B, np,
+                         c->dX32, np, np, (int)np);
+      HIPCHK(c, hipGetLastError());
+      c->x32_valid = true;
     }
-    const long long tot = np * np;
-    hipLaunchKernelGGL(k_to_f32, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, c->stream, c->tr.B, np,
-                       c->dX32, np, np, (int)np);
-    HIPCHK(c, hipGetLastError());
-    c->x32_valid = true;
-  }
-  // full covariance of more than one chunk: every chunk's V, scaled points and T Kq^-T
-  // are kept on the device, then the m x m result is formed block by block (below)
-  const bool big = full_var && m > CHUNK;
-  const long long mtot = ((m + TILE - 1) / TILE) * TILE;
-  const int kq = ((q + 15) / 16) * 16;
-  std::vector<double> Th;
-  if (big) {
-    CHK(grow(c, &c->dVall, &c->vall_cap, (size_t)np * mtot));
-    CHK(grow(c, &c->dXall, &c->xall_cap, (size_t)mtot * d));
-    CHK(grow(c, &c->dTall, &c->tall_cap, (size_t)mtot * kq));
-    Th.assign((size_t)mtot * kq, 0.0);
-  }
-  // [gamma, G] = A^-1 [f - H beta, H]
-  CHK(ensure_pinned(c, (size_t)P * P + 64));
-  {
+    CHK(ensure_pinned(c, (size_t)P * P + 64));
     std::vector<double> T((size_t)P * P, 0.0);  // col-major
     T[0] = 1.0;
     for (int i = 0; i < q; ++i) {
@@ -3012,96 +3044,84 @@ static int posterior_impl(gpe_ctx* c, int64_t m, const double* Xs, const double*
     }
     std::memcpy(c->hpin, T.data(), T.size() * sizeof(double));
     HIPCHK(c, hipMemcpyAsync(c->dT2, c->hpin, T.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    CHK(apply_small(c, c->dF, np, P, c->dT2, P, c->dR2, np, (int)np, nullptr));
+    CHK(skinny(c, false, c->tr.B, np, c->NB, c->NB, true, c->dR2, np, P, c->dZ, np));   // L^-1 [f-Hb, H]
+    CHK(skinny(c, true, c->tr.B, np, c->NB, c->NB, true, c->dZ, np, P, c->dWa, np));   // A^-1 [f-Hb, H]
+    std::vector<double> G((size_t)P * P);
+    CHK(gram(c, c->dZ, np, P, (int)np, G.data()));
+    // Q = H^T A^-1 H = G[1:,1:]
+    std::vector<double> Kq((size_t)q * q);
+    for (int i = 0; i < q; ++i)
+      for (int j = 0; j < q; ++j) Kq[i * q + j] = G[(i + 1) * P + (j + 1)];
+    if (!small_chol(Kq, q)) return fail(c, GPE_NOT_PD, "H^T A^-1 H not positive definite");
+    Kinv = small_trinv(Kq, q);
+    kernel_consts(c->f_kernel, c->f_nu, true, &coff, &cdiag);
+    fam = kernel_fam(c->f_kernel);
+    s2 = sigma * sigma;
+    return GPE_OK;
   }
-  CHK(apply_small(c, c->dF, np, P, c->dT2, P, c->dR2, np, (int)np, nullptr));
-  CHK(skinny(c, false, c->tr.B, np, c->NB, c->NB, true, c->dR2, np, P, c->dZ, np));   // L^-1 [f-Hb, H]
-  CHK(skinny(c, true, c->tr.B, np, c->NB, c->NB, true, c->dZ, np, P, c->dWa, np));   // A^-1 [f-Hb, H]
-  std::vector<double> G((size_t)P * P);
-  CHK(gram(c, c->dZ, np, P, (int)np, G.data()));
-  // Q = H^T A^-1 H = G[1:,1:]
-  std::vector<double> Kq((size_t)q * q);
-  for (int i = 0; i < q; ++i)
-    for (int j = 0; j < q; ++j) Kq[i * q + j] = G[(i + 1) * P + (j + 1)];
-  if (!small_chol(Kq, q)) return fail(c, GPE_NOT_PD, "H^T A^-1 H not positive definite");
-  std::vector<double> Kinv = small_trinv(Kq, q);
-  double coff, cdiag;
-  kernel_consts(c->f_kernel, c->f_nu, true, &coff, &cdiag);
-  const int fam = kernel_fam(c->f_kernel);   // the resident factor's correlation family
-  const double s2 = sigma * sigma;
 
-  // workspace for the largest chunk (the first): K* (np x mp) and V (np x mp), the chunk's
-  // points, two pinned staging slots of points and two of results, two device result slots
-  const long long mp0 = ((std::min<long long>(CHUNK, m) + TILE - 1) / TILE) * TILE;
-  if ((size_t)np * mp0 > c->w_cap) {
-    c->w_cap = 0;
-    CHK(dalloc(c, &c->dW1, (size_t)np * mp0));
-    CHK(dalloc(c, &c->dW2, (size_t)np * mp0));
-    c->w_cap = (size_t)np * mp0;
+  // Workspace for the largest chunk (the first): K* (np x mp) and V (np x mp), the chunk's
+  // points, two pinned staging slots of points and two of results, two device result slots;
+  // 1 / delta on the device.  A full covariance of more than one chunk also keeps every
+  // chunk's V, scaled points and T Kq^-T on the device until its blocks are formed.
+  int workspace() {
+    if (big) {
+      CHK(grow_buf(c, &c->dVall, &c->vall_cap, (size_t)np * mtot));
+      CHK(grow_buf(c, &c->dXall, &c->xall_cap, (size_t)mtot * d));
+      CHK(grow_buf(c, &c->dTall, &c->tall_cap, (size_t)mtot * kq));
+    }
+    CHK(grow_buf(c, &c->dW1, &c->w1_cap, (size_t)np * mp0));
+    CHK(grow_buf(c, &c->dW2, &c->w2_cap, (size_t)np * mp0));
+    CHK(grow_buf(c, &c->dXs, &c->xs_cap, (size_t)mp0 * d));
+    CHK(grow_buf(c, &c->dXsw, &c->xsw_cap, (size_t)mp0 * d));
+    rs = (size_t)mp0 * P + mp0;
+    CHK(ensure_small(c, 2 * rs + 64));
+    // (the full covariance also stages T Kq^-T, mp x kq, at the front: the capacity is set
+    // here once, so the slots never move)
+    CHK(ensure_pinned(c, std::max<size_t>(2 * (size_t)mp0 * d + 2 * rs + d, (size_t)mp0 * kq) + 64));
+    pin_in[0] = c->hpin, pin_in[1] = pin_in[0] + (size_t)mp0 * d;
+    pin_out[0] = pin_in[1] + (size_t)mp0 * d, pin_out[1] = pin_out[0] + rs;
+    double* pin_dl = pin_out[1] + rs;   // 1 / delta
+    for (int k = 0; k < d; ++k) pin_dl[k] = 1.0 / c->f_delta[k];
+    HIPCHK(c, hipMemcpyAsync(c->dinvdelta, pin_dl, d * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    if (!c->ev_pipe[0])
+      for (hipEvent_t& e : c->ev_pipe) HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    return GPE_OK;
   }
-  if ((size_t)mp0 * d > c->xs_cap) {
-    c->xs_cap = 0;
-    CHK(dalloc(c, &c->dXs, (size_t)mp0 * d));
-    CHK(dalloc(c, &c->dXsw, (size_t)mp0 * d));
-    c->xs_cap = (size_t)mp0 * d;
-  }
-  const size_t rs = (size_t)mp0 * P + mp0;   // one result slot: Y (mp x P), then the column norms
-  CHK(ensure_small(c, 2 * rs + 64));
-  // (the full covariance also stages T Kq^-T, mp x kq, at the front: the capacity is set here
-  // once, so the slots never move)
-  CHK(ensure_pinned(c, std::max<size_t>(2 * (size_t)mp0 * d + 2 * rs + d, (size_t)mp0 * kq) + 64));
-  double* pin_in[2] = {c->hpin, c->hpin + (size_t)mp0 * d};
-  double* pin_out[2] = {c->hpin + 2 * (size_t)mp0 * d, c->hpin + 2 * (size_t)mp0 * d + rs};
-  double* pin_dl = c->hpin + 2 * (size_t)mp0 * d + 2 * rs;   // 1 / delta
-  for (int k = 0; k < d; ++k) pin_dl[k] = 1.0 / c->f_delta[k];
-  HIPCHK(c, hipMemcpyAsync(c->dinvdelta, pin_dl, d * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  if (!c->ev_pipe[0])
-    for (hipEvent_t& e : c->ev_pipe) HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  // one chunk's device work: its points from the pinned slot pin, K*, Y = K*^T [gamma, G]
-  // into dY, V = L^-1 K* into vdst (fp32 path: into dK32)
-  auto dev_chunk = [&](long long s0, double* pin, double* dY, double* vdst) -> int {
-    const long long mc = std::min(CHUNK, m - s0);
-    const long long mp = ((mc + TILE - 1) / TILE) * TILE;
+
+  // One chunk's device work: its points from the pinned slot pin, K*, Y = K*^T [gamma, G]
+  // into dY, V = L^-1 K* into vdst (fp32 path: into dK32).
+  int dev_chunk(long long s0, double* pin, double* dY, double* vdst) {
+    const long long mc = std::min(CHUNK, m - s0), mp = pad_tile(mc);
     const int mt = (int)(mp / TILE);
     std::memset(pin, 0, (size_t)mp * d * sizeof(double));
     std::memcpy(pin, Xs + s0 * d, (size_t)mc * d * sizeof(double));
     HIPCHK(c, hipMemcpyAsync(c->dXs, pin, (size_t)mp * d * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    {
-      const long long tot = mp * d;
-      hipLaunchKernelGGL(k_scale_points, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, c->stream,
-                         c->dXs, c->dinvdelta, d, (int)mc, (int)mp, c->dXsw);
-      HIPCHK(c, hipGetLastError());
-    }
+    hipLaunchKernelGGL(k_scale_points, dim3((unsigned)((mp * d + 255) / 256)), dim3(256), 0, c->stream,
+                       c->dXs, c->dinvdelta, d, (int)mc, (int)mp, c->dXsw);
+    HIPCHK(c, hipGetLastError());
     // K*(i, s) = coff * exp(-|x_i - xs_s|^2), padded rows/cols 0
-    {
-      PairArgs a;
-      a.xr = c->dXw; a.xc = c->dXsw; a.out = c->dW1; a.ld = np; a.d = d;
-      a.nr_valid = (int)c->n; a.nc_valid = (int)mc; a.mt = c->NB; a.nt = mt; a.mode = 0;
-      a.s2 = 1.0; a.coff = coff; a.cdiag = cdiag; a.rscale = 0.0; a.r = nullptr;
-      a.fam = fam;
-      CHK(launch_pairs(c, a, c->NB * mt));
-    }
+    PairArgs a;
+    a.xr = c->dXw; a.xc = c->dXsw; a.out = c->dW1; a.ld = np; a.d = d;
+    a.nr_valid = (int)c->n; a.nc_valid = (int)mc; a.mt = c->NB; a.nt = mt; a.mode = 0;
+    a.s2 = 1.0; a.coff = coff; a.cdiag = cdiag; a.rscale = 0.0; a.r = nullptr;
+    a.fam = fam;
+    CHK(launch_pairs(c, a, c->NB * mt));
     // Y = K*^T [gamma, G]  (mp x P)
     // skinny transposed over a full matrix: M = K* (np x mp), k tiles = NB, out tiles = mt;
     // 32 columns of [gamma, G] at a time
     for (int c0 = 0; c0 < P; c0 += SK_PMAX) {
       const int pc = std::min(SK_PMAX, P - c0);
       const int nch = (c->NB + SK_CH - 1) / SK_CH;
-      const size_t needp = (size_t)nch * mp * pc;
-      if (needp > c->skp_cap) {
-        c->skp_cap = 0;
-        CHK(dalloc(c, &c->dskp, needp));
-        c->skp_cap = needp;
-      }
-      SkinnyArgs a;
-      a.M = c->dW1; a.ldm = np; a.R = c->dWa + (long long)c0 * np; a.ldr = np; a.part = c->dskp; a.ldp = mp;
-      a.pstride = mp * pc; a.P = pc; a.ntr = c->NB; a.lower = 0; a.nit = mt; a.abort_flag = nullptr;
-      a.chk = SK_CH;
-      dim3 grid(mt * nch);
-      if (pc <= 16) {
-        hipLaunchKernelGGL((k_skinny_mfma<16, true>), grid, dim3(256), 0, c->stream, a);
-      } else {
-        hipLaunchKernelGGL((k_skinny_mfma<32, true>), grid, dim3(256), 0, c->stream, a);
-      }
+      CHK(grow_buf(c, &c->dskp, &c->skp_cap, (size_t)nch * mp * pc));
+      SkinnyArgs k;
+      k.M = c->dW1; k.ldm = np; k.R = c->dWa + (long long)c0 * np; k.ldr = np; k.part = c->dskp; k.ldp = mp;
+      k.pstride = mp * pc; k.P = pc; k.ntr = c->NB; k.lower = 0; k.nit = mt; k.abort_flag = nullptr;
+      k.chk = SK_CH;
+      const dim3 grid(mt * nch);
+      if (pc <= 16) hipLaunchKernelGGL((k_skinny_mfma<16, true>), grid, dim3(256), 0, c->stream, k);
+      else hipLaunchKernelGGL((k_skinny_mfma<32, true>), grid, dim3(256), 0, c->stream, k);
       HIPCHK(c, hipGetLastError());
       const long long tot = mp * pc;
       hipLaunchKernelGGL(k_reduce_chunks, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, c->stream,
@@ -3110,56 +3130,46 @@ static int posterior_impl(gpe_ctx* c, int64_t m, const double* Xs, const double*
       HIPCHK(c, hipGetLastError());
     }
     // V = L^-1 K*   (np x mp), X lower-triangular -> kend = (ti+1)*128
-    if (ozp) {
-      CHK(posterior_oz(c, f32, c->dW1, mp, vdst));
-    } else if (f32) {
-      const size_t need32 = 2 * (size_t)np * mp;
-      if (need32 > c->k32_cap) {
-        if (c->dK32) (void)hipFree(c->dK32);
-        c->dK32 = nullptr;
-        HIPCHK(c, hipMalloc((void**)&c->dK32, need32 * sizeof(float)));
-        c->k32_cap = need32;
-      }
-      float* K32 = c->dK32;
-      float* V32 = c->dK32 + (size_t)np * mp;
-      const long long tot = np * mp;
-      hipLaunchKernelGGL(k_to_f32, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, c->stream, c->dW1, np,
-                         K32, np, np, (int)mp);
-      HIPCHK(c, hipGetLastError());
-      hipLaunchKernelGGL(k_gemm_f32, dim3((unsigned)(c->NB * mt)), dim3(256), 2 * F32_STAGE * sizeof(float),
-                         c->stream, c->dX32, np, K32, np, V32, np, c->NB, (int)np, 1);
-      HIPCHK(c, hipGetLastError());
-    } else {
-      std::vector<GemmProb> pv = {mkprob(c->tr.B, np, c->dW1, np, vdst, np, c->NB, mt, (int)np,
-                                         G_KEND_TI, 1.0, 0.0)};
-      pv[0].tile_begin = 0;
-      pv[0].ntiles = c->NB * mt;
-      HIPCHK(c, hipMemcpyAsync(c->dprobs + ADHOC_DESC_BASE, pv.data(), sizeof(GemmProb), hipMemcpyHostToDevice, c->stream));
-      Launch L{3, ADHOC_DESC_BASE, 1, c->NB * mt, 0.0};
-      CHK(launch_gemm_range(c, L));
-    }
+    if (ozp) return posterior_oz(c, f32, c->dW1, mp, vdst);
+    if (!f32)
+      return adhoc_gemm(c, ADHOC_POST_V,
+                        {{3, mkprob(c->tr.B, np, c->dW1, np, vdst, np, c->NB, mt, (int)np, G_KEND_TI, 1.0, 0.0)}});
+    CHK(grow_buf(c, &c->dK32, &c->k32_cap, 2 * (size_t)np * mp));
+    float *K32 = c->dK32, *V32 = c->dK32 + (size_t)np * mp;
+    hipLaunchKernelGGL(k_to_f32, dim3((unsigned)((np * mp + 255) / 256)), dim3(256), 0, c->stream, c->dW1, np,
+                       K32, np, np, (int)mp);
+    HIPCHK(c, hipGetLastError());
+    hipLaunchKernelGGL(k_gemm_f32, dim3((unsigned)(c->NB * mt)), dim3(256), 2 * F32_STAGE * sizeof(float),
+                       c->stream, c->dX32, np, K32, np, V32, np, c->NB, (int)np, 1);
+    HIPCHK(c, hipGetLastError());
     return GPE_OK;
-  };
-  if (!full_var) {
-    // diagonal variance, pipelined: chunk i's device work (and the copy of its Y and column
-    // norms into pinned slot i % 2) is queued before the host turns chunk i - 1's results
-    // into means and variances, so the GPU does not idle on the host between chunks
+  }
+
+  // Per-point host algebra, from the chunk's Y = K*^T [gamma, G] (Yh, mp x P column-major):
+  // the mean Y_0 + hs . beta into mean_out, and row(o, (T Kq^-T)_o) for o < q, T = Hs - K*^T G.
+  template <class Row>
+  void point(const double* Yh, long long mp, long long s0, long long s, Row&& row) const {
+    const double* hs = Hs + (s0 + s) * q;
+    double mu = Yh[s];
+    for (int i = 0; i < q; ++i) mu += hs[i] * beta[i];
+    mean_out[s0 + s] = mu;
+    for (int o = 0; o < q; ++o) {
+      double acc = 0.0;
+      for (int i = 0; i < q; ++i) acc += (hs[i] - Yh[s + (long long)(i + 1) * mp]) * Kinv[o * q + i];
+      row(o, acc);
+    }
+  }
+
+  // Diagonal variance, pipelined: chunk i's device work (and the copy of its Y and column
+  // norms into pinned slot i % 2) is queued before the host turns chunk i - 1's results
+  // into means and variances, so the GPU does not idle on the host between chunks.
+  int diag() {
     auto host_chunk = [&](long long s0, const double* out) {
-      const long long mc = std::min(CHUNK, m - s0);
-      const long long mp = ((mc + TILE - 1) / TILE) * TILE;
-      const double* Yh = out;
+      const long long mc = std::min(CHUNK, m - s0), mp = pad_tile(mc);
       const double* nrm = out + (size_t)mp * P;
       for (long long s = 0; s < mc; ++s) {
-        const double* hs = Hs + (s0 + s) * q;
-        double mu = Yh[s];
-        for (int i = 0; i < q; ++i) mu += hs[i] * beta[i];
-        mean_out[s0 + s] = mu;
-        double tq = 0.0;   // |T Kq^-T|^2, T = Hs - K*^T G
-        for (int o = 0; o < q; ++o) {
-          double acc = 0.0;
-          for (int i = 0; i < q; ++i) acc += (hs[i] - Yh[s + (long long)(i + 1) * mp]) * Kinv[o * q + i];
-          tq += acc * acc;
-        }
+        double tq = 0.0;   // |T Kq^-T|^2
+        point(out, mp, s0, s, [&](int, double acc) { tq += acc * acc; });
         var_out[s0 + s] = s2 * (cdiag - nrm[s] + tq);
       }
     };
@@ -3167,8 +3177,7 @@ static int posterior_impl(gpe_ctx* c, int64_t m, const double* Xs, const double*
     long long prev = -1;
     auto pipeline = [&]() -> int {
       for (long long s0 = 0; s0 < m; s0 += CHUNK, slot ^= 1) {
-        const long long mc = std::min(CHUNK, m - s0);
-        const long long mp = ((mc + TILE - 1) / TILE) * TILE;
+        const long long mp = pad_tile(std::min(CHUNK, m - s0));
         double* dY = c->dsmall + slot * rs;
         double* dn = dY + (size_t)mp * P;
         CHK(dev_chunk(s0, pin_in[slot], dY, c->dW2));
@@ -3199,186 +3208,147 @@ static int posterior_impl(gpe_ctx* c, int64_t m, const double* Xs, const double*
     return rc;
   }
 
-  for (long long s0 = 0; s0 < m; s0 += CHUNK) {
-    const long long mc = std::min(CHUNK, m - s0);
-    const long long mp = ((mc + TILE - 1) / TILE) * TILE;
-    const int mt = (int)(mp / TILE);
-    double* dY = c->dsmall;
-    CHK(dev_chunk(s0, pin_in[0], dY, big ? c->dVall + s0 * np : c->dW2));
-    // host pieces: mean, T = Hs - K*^T G
-    std::vector<double> Yh((size_t)mp * P);
-    HIPCHK(c, hipMemcpyAsync(pin_out[0], dY, (size_t)mp * P * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    std::memcpy(Yh.data(), pin_out[0], Yh.size() * sizeof(double));
-    std::vector<double> Tt((size_t)mc * q);   // T Kq^-T, row-major mc x q
-    for (long long s = 0; s < mc; ++s) {
-      const double* hs = Hs + (s0 + s) * q;
-      double mu = Yh[s];
-      for (int i = 0; i < q; ++i) mu += hs[i] * beta[i];
-      mean_out[s0 + s] = mu;
-      for (int o = 0; o < q; ++o) {
-        double acc = 0.0;
-        for (int i = 0; i < q; ++i) acc += (hs[i] - Yh[s + (long long)(i + 1) * mp]) * Kinv[o * q + i];
-        Tt[s * q + o] = acc;
-      }
+  // One block of the covariance, dst (ld) = s2 (A** - V_R^T V_C + T_R T_C^T) for the points R
+  // (rows) and C (columns): the pair kernel (dg: a diagonal block, its lower tiles mirrored,
+  // identity padding and s2 * rnew_scale * rnew on the diagonal), then the two products.
+  // t_stage > 0: that many doubles of R.T wait in the pinned buffer and are uploaded behind
+  // the pair kernel (the single chunk, whose T lives behind the block).
+  int cov_block(const CovSide& R, const CovSide& C, double* dst, long long ld, bool dg, size_t t_stage = 0) {
+    const int mt = (int)(R.mp / TILE), nt = (int)(C.mp / TILE);
+    PairArgs a;
+    a.xr = R.X; a.xc = C.X; a.out = dst; a.ld = ld; a.d = d;
+    a.nr_valid = (int)R.mc; a.nc_valid = (int)C.mc; a.mt = mt; a.nt = nt; a.mode = dg ? (1 | 2 | 4) : 0;
+    a.s2 = s2; a.coff = coff; a.cdiag = cdiag; a.rscale = 0.0; a.r = nullptr;
+    a.fam = fam;
+    if (dg && rnew) {
+      CHK(grow_buf(c, &c->dRn, &c->rn_cap, (size_t)R.mp));
+      // (synchronous copy; padded rows do not read r)
+      HIPCHK(c, hipMemcpy(c->dRn, rnew + R.s0, (size_t)R.mc * sizeof(double), hipMemcpyHostToDevice));
+      a.r = c->dRn;
+      a.rscale = s2 * rnew_scale;
     }
-    if (big) {
-      // keep this chunk's scaled points and T Kq^-T for the blocks formed after the loop
-      HIPCHK(c, hipMemcpyAsync(c->dXall + s0 * d, c->dXsw, (size_t)mp * d * sizeof(double), hipMemcpyDeviceToDevice,
-                               c->stream));
-      for (long long s = 0; s < mc; ++s)
-        for (int o = 0; o < q; ++o) Th[(s0 + s) + (size_t)o * mtot] = Tt[s * q + o];
-      continue;
-    }
-    {
-      // C = s2 * (A** - V^T V + Tt Tt^T), all tiles (full symmetric)
-      const size_t needc = (size_t)mp * mp;
-      if (needc + (size_t)mp * kq > c->w3_cap) {
-        c->w3_cap = 0;
-        CHK(dalloc(c, &c->dW3, needc + (size_t)mp * kq));
-        c->w3_cap = needc + (size_t)mp * kq;
-      }
-      double* dC = c->dW3;
-      double* dTt = c->dW3 + needc;
-      {
-        PairArgs a;
-        a.xr = c->dXsw; a.xc = c->dXsw; a.out = dC; a.ld = mp; a.d = d;
-        a.nr_valid = (int)mc; a.nc_valid = (int)mc; a.mt = mt; a.nt = mt; a.mode = 1 | 2 | 4;
-        a.s2 = s2; a.coff = coff; a.cdiag = cdiag; a.rscale = 0.0; a.r = nullptr;
-        a.fam = fam;
-        if (rnew) {
-          CHK(grow(c, &c->dRn, &c->rn_cap, (size_t)mp));
-          // synchronous copy: hpin is about to be reused for T below
-          HIPCHK(c, hipMemcpy(c->dRn, rnew + s0, (size_t)mc * sizeof(double), hipMemcpyHostToDevice));
-          a.r = c->dRn;
-          a.rscale = s2 * rnew_scale;
-        }
-        CHK(launch_pairs(c, a, mt * (mt + 1) / 2));
-      }
-      std::vector<double> tth((size_t)mp * kq, 0.0);   // column-major mp x kq
-      for (long long s = 0; s < mc; ++s)
-        for (int o = 0; o < q; ++o) tth[s + (size_t)o * mp] = Tt[s * q + o];
-      CHK(ensure_pinned(c, tth.size() + 64));
-      std::memcpy(c->hpin, tth.data(), tth.size() * sizeof(double));
-      HIPCHK(c, hipMemcpyAsync(dTt, c->hpin, tth.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
-      std::vector<GemmProb> p2 = {
-          mkprob(c->dW2, np, c->dW2, np, dC, mp, mt, mt, (int)np, 0, -s2, 1.0),
-          mkprob(dTt, mp, dTt, mp, dC, mp, mt, mt, kq, 0, s2, 1.0)};
-      p2[0].tile_begin = 0; p2[0].ntiles = mt * mt;
-      p2[1].tile_begin = 0; p2[1].ntiles = mt * mt;
-      HIPCHK(c, hipMemcpyAsync(c->dprobs + ADHOC_DESC_BASE + 1, p2.data(), 2 * sizeof(GemmProb), hipMemcpyHostToDevice, c->stream));
-      Launch L1{2, ADHOC_DESC_BASE + 1, 1, mt * mt, 0.0};
-      CHK(launch_gemm_range(c, L1));
-      Launch L2{0, ADHOC_DESC_BASE + 2, 1, mt * mt, 0.0};
-      CHK(launch_gemm_range(c, L2));
-      if (keep_dev) {   // drain: the caller reuses the pinned staging buffer
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        return GPE_OK;
-      }
+    CHK(launch_pairs(c, a, dg ? mt * (mt + 1) / 2 : mt * nt));
+    if (t_stage)
+      HIPCHK(c, hipMemcpyAsync(R.T, c->hpin, t_stage * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    return adhoc_gemm(c, ADHOC_COV, {{2, mkprob(R.V, np, C.V, np, dst, ld, mt, nt, (int)np, 0, -s2, 1.0)},
+                                     {0, mkprob(R.T, R.ldt, C.T, C.ldt, dst, ld, mt, nt, kq, 0, s2, 1.0)}});
+  }
+
+  // Full variance.  One chunk: its block in dW3, copied out unless it stays there.  More:
+  // every chunk's V, scaled points and T Kq^-T are kept, then the blocks of the lower
+  // (FULL_DEV) or upper (FULL, mirrored on the host) triangle of chunk pairs are formed.
+  int full_var() {
+    std::vector<double> Th;   // every point's T Kq^-T (mtot x kq column-major)
+    if (big) Th.assign((size_t)mtot * kq, 0.0);
+    for (long long s0 = 0; s0 < m; s0 += CHUNK) {
+      const long long mc = std::min(CHUNK, m - s0), mp = pad_tile(mc);
+      double* dY = c->dsmall;
+      CHK(dev_chunk(s0, pin_in[0], dY, big ? c->dVall + s0 * np : c->dW2));
+      std::vector<double> Yh((size_t)mp * P);
+      HIPCHK(c, hipMemcpyAsync(pin_out[0], dY, (size_t)mp * P * sizeof(double), hipMemcpyDeviceToHost, c->stream));
       HIPCHK(c, hipStreamSynchronize(c->stream));
+      std::memcpy(Yh.data(), pin_out[0], Yh.size() * sizeof(double));
+      if (big) {
+        // keep this chunk's scaled points and T Kq^-T for the blocks formed after the loop
+        HIPCHK(c, hipMemcpyAsync(c->dXall + s0 * d, c->dXsw, (size_t)mp * d * sizeof(double),
+                                 hipMemcpyDeviceToDevice, c->stream));
+        for (long long s = 0; s < mc; ++s)
+          point(Yh.data(), mp, s0, s, [&](int o, double acc) { Th[(s0 + s) + (size_t)o * mtot] = acc; });
+        continue;
+      }
+      // C (mp x mp, all tiles: full symmetric), then T Kq^-T (mp x kq column-major) behind it
+      const size_t needc = (size_t)mp * mp, nt = (size_t)mp * kq;
+      CHK(grow_buf(c, &c->dW3, &c->w3_cap, needc + nt));
+      double* dC = c->dW3;
+      CHK(ensure_pinned(c, nt + 64));
+      std::memset(c->hpin, 0, nt * sizeof(double));
+      for (long long s = 0; s < mc; ++s)
+        point(Yh.data(), mp, s0, s, [&](int o, double acc) { c->hpin[s + (size_t)o * mp] = acc; });
+      const CovSide side{c->dXsw, c->dW2, dC + needc, mp, s0, mc, mp};
+      CHK(cov_block(side, side, dC, mp, true, nt));
+      // (FULL_DW3: the caller reuses the pinned staging buffer)
+      HIPCHK(c, hipStreamSynchronize(c->stream));
+      if (var == PostVar::FULL_DW3) return GPE_OK;
       // copy out m x m (col-major == row-major for the symmetric result)
       std::vector<double> hc((size_t)mp * mc);
       HIPCHK(c, hipMemcpy(hc.data(), dC, hc.size() * sizeof(double), hipMemcpyDeviceToHost));
       for (long long j = 0; j < mc; ++j)
         std::memcpy(var_out + j * m, hc.data() + (size_t)j * mp, (size_t)mc * sizeof(double));
     }
+    if (big) CHK(blocks(Th));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return GPE_OK;
   }
-  if (big) {
-    // blocks (a, b), b >= a, of C = s2 (A** - V^T V + T T^T) over chunk pairs, each formed
-    // in dW3 and written to the host at rows a, columns b (and mirrored)
+
+  // the chunk-pair blocks of a full variance of more than one chunk (Th: every point's T Kq^-T)
+  int blocks(const std::vector<double>& Th) {
     HIPCHK(c, hipMemcpyAsync(c->dTall, Th.data(), Th.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    const size_t needc = (size_t)CHUNK * CHUNK;
-    if (!keep_dev && needc > c->w3_cap) {
-      c->w3_cap = 0;
-      CHK(dalloc(c, &c->dW3, needc));
-      c->w3_cap = needc;
-    }
+    const bool dev = var == PostVar::FULL_DEV;
+    if (!dev) CHK(grow_buf(c, &c->dW3, &c->w3_cap, (size_t)CHUNK * CHUNK));
     double* dC = c->dW3;
     std::vector<double> hc;
-    for (long long a0 = 0; a0 < m; a0 += CHUNK) {
-      const long long mca = std::min(CHUNK, m - a0), mpa = ((mca + TILE - 1) / TILE) * TILE;
-      const int mta = (int)(mpa / TILE);
+    auto side = [&](long long s0) {
+      const long long mc = std::min(CHUNK, m - s0);
+      return CovSide{c->dXall + s0 * d, c->dVall + s0 * np, c->dTall + s0, mtot, s0, mc, pad_tile(mc)};
+    };
+    for (long long a0 = 0; a0 < m; a0 += CHUNK)
       for (long long b0 = a0; b0 < m; b0 += CHUNK) {
-        const long long mcb = std::min(CHUNK, m - b0), mpb = ((mcb + TILE - 1) / TILE) * TILE;
-        const int mtb = (int)(mpb / TILE);
+        const CovSide A = side(a0), B = side(b0);
         const bool dg = a0 == b0;
-        if (keep_dev) {
-          // block (b, a) of the lower triangle straight into dev_full (ld = mtot): rows of
+        if (dev) {
+          // block (b, a) of the lower triangle straight into dev_out (ld = mtot): rows of
           // chunk b, columns of chunk a.  Padded rows / columns come out 0 off the
           // diagonal (zero K*, V and T there) and identity on it (the pair kernel).
-          double* dst = dev_full + b0 + a0 * mtot;
-          PairArgs a;
-          a.xr = c->dXall + b0 * d; a.xc = c->dXall + a0 * d; a.out = dst; a.ld = mtot; a.d = d;
-          a.nr_valid = (int)mcb; a.nc_valid = (int)mca; a.mt = mtb; a.nt = mta; a.mode = dg ? (1 | 2 | 4) : 0;
-          a.s2 = s2; a.coff = coff; a.cdiag = cdiag; a.rscale = 0.0; a.r = nullptr;
-          a.fam = fam;
-          if (dg && rnew) {
-            CHK(grow(c, &c->dRn, &c->rn_cap, (size_t)mpa));
-            // (synchronous copy; padded rows do not read r)
-            HIPCHK(c, hipMemcpy(c->dRn, rnew + a0, (size_t)mca * sizeof(double), hipMemcpyHostToDevice));
-            a.r = c->dRn;
-            a.rscale = s2 * rnew_scale;
-          }
-          CHK(launch_pairs(c, a, dg ? mta * (mta + 1) / 2 : mta * mtb));
-          std::vector<GemmProb> p2 = {
-              mkprob(c->dVall + b0 * np, np, c->dVall + a0 * np, np, dst, mtot, mtb, mta, (int)np, 0, -s2, 1.0),
-              mkprob(c->dTall + b0, mtot, c->dTall + a0, mtot, dst, mtot, mtb, mta, kq, 0, s2, 1.0)};
-          p2[0].tile_begin = 0; p2[0].ntiles = mta * mtb;
-          p2[1].tile_begin = 0; p2[1].ntiles = mta * mtb;
-          HIPCHK(c, hipMemcpyAsync(c->dprobs + ADHOC_DESC_BASE + 1, p2.data(), 2 * sizeof(GemmProb),
-                                   hipMemcpyHostToDevice, c->stream));
-          Launch L1{2, ADHOC_DESC_BASE + 1, 1, mta * mtb, 0.0};
-          CHK(launch_gemm_range(c, L1));
-          Launch L2{0, ADHOC_DESC_BASE + 2, 1, mta * mtb, 0.0};
-          CHK(launch_gemm_range(c, L2));
+          CHK(cov_block(B, A, dev_out + b0 + a0 * mtot, mtot, dg));
           // the descriptors are re-uploaded for the next block: drain before overwriting
           HIPCHK(c, hipStreamSynchronize(c->stream));
           continue;
         }
-        PairArgs a;   // A** block: the diagonal block as the single-chunk path, else rectangular
-        a.xr = c->dXall + a0 * d; a.xc = c->dXall + b0 * d; a.out = dC; a.ld = mpa; a.d = d;
-        a.nr_valid = (int)mca; a.nc_valid = (int)mcb; a.mt = mta; a.nt = mtb; a.mode = dg ? (1 | 2 | 4) : 0;
-        a.s2 = s2; a.coff = coff; a.cdiag = cdiag; a.rscale = 0.0; a.r = nullptr;
-        a.fam = fam;
-        if (dg && rnew) {
-          CHK(grow(c, &c->dRn, &c->rn_cap, (size_t)mpa));
-          HIPCHK(c, hipMemcpy(c->dRn, rnew + a0, (size_t)mca * sizeof(double), hipMemcpyHostToDevice));
-          a.r = c->dRn;
-          a.rscale = s2 * rnew_scale;
-        }
-        CHK(launch_pairs(c, a, dg ? mta * (mta + 1) / 2 : mta * mtb));
-        std::vector<GemmProb> p2 = {
-            mkprob(c->dVall + a0 * np, np, c->dVall + b0 * np, np, dC, mpa, mta, mtb, (int)np, 0, -s2, 1.0),
-            mkprob(c->dTall + a0, mtot, c->dTall + b0, mtot, dC, mpa, mta, mtb, kq, 0, s2, 1.0)};
-        p2[0].tile_begin = 0; p2[0].ntiles = mta * mtb;
-        p2[1].tile_begin = 0; p2[1].ntiles = mta * mtb;
-        HIPCHK(c, hipMemcpyAsync(c->dprobs + ADHOC_DESC_BASE + 1, p2.data(), 2 * sizeof(GemmProb),
-                                 hipMemcpyHostToDevice, c->stream));
-        Launch L1{2, ADHOC_DESC_BASE + 1, 1, mta * mtb, 0.0};
-        CHK(launch_gemm_range(c, L1));
-        Launch L2{0, ADHOC_DESC_BASE + 2, 1, mta * mtb, 0.0};
-        CHK(launch_gemm_range(c, L2));
-        hc.resize((size_t)mpa * mpb);
+        // block (a, b) in dW3 (ld = mpa), written to the host at rows a, columns b (and mirrored)
+        CHK(cov_block(A, B, dC, A.mp, dg));
+        hc.resize((size_t)A.mp * B.mp);
         HIPCHK(c, hipMemcpyAsync(hc.data(), dC, hc.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         // dC(i, j) = C(a0 + i, b0 + j), column-major; var_out row-major m x m
-        for (long long j = 0; j < mcb; ++j)
-          for (long long i = 0; i < mca; ++i) {
-            const double v = hc[(size_t)i + (size_t)j * mpa];
+        for (long long j = 0; j < B.mc; ++j)
+          for (long long i = 0; i < A.mc; ++i) {
+            const double v = hc[(size_t)i + (size_t)j * A.mp];
             var_out[(a0 + i) * m + (b0 + j)] = v;
             if (!dg) var_out[(b0 + j) * m + (a0 + i)] = v;
           }
       }
-    }
+    return GPE_OK;
   }
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return GPE_OK;
+};
+
+int posterior_impl(gpe_ctx* c, const PostReq& r) {
+  CHK(check_ready(c));
+  if (!c->factor_valid) return fail(c, GPE_ERR_STATE, "no resident factor (call gpe_factor)");
+  const bool to_host = r.var == PostVar::DIAG || r.var == PostVar::FULL;
+  if (r.m <= 0 || !r.Xs || !r.Hs || !r.beta || !r.mean_out || (to_host && !r.var_out))
+    return fail(c, GPE_ERR_ARG, "bad posterior args");
+  if ((r.var == PostVar::FULL_DW3 && r.m > POST_CHUNK_FULL) ||
+      (r.var == PostVar::FULL_DEV && (r.m <= POST_CHUNK_FULL || !r.dev_out)))
+    return fail(c, GPE_ERR_ARG, "device-resident variance: one chunk in place, beyond one chunk a device target");
+  if (r.precision != 64 && r.precision != 32) return fail(c, GPE_ERR_ARG, "precision must be 64 or 32");
+  if (r.precision == 32 && r.var != PostVar::DIAG)
+    return fail(c, GPE_ERR_UNSUPPORTED, "precision 32 is for the diagonal variance");
+  CHK(ensure_linv(c));
+  Posterior S(c, r);
+  CHK(S.setup());
+  CHK(S.workspace());
+  return S.full ? S.full_var() : S.diag();
 }
+
+}  // namespace
+
+extern "C" {
 
 int gpe_posterior(gpe_ctx* c, int64_t m, const double* Xs, const double* Hs, const double* beta,
                   double sigma, int32_t full_var, int32_t precision, double* mean_out, double* var_out) {
-  return posterior_impl(c, m, Xs, Hs, beta, sigma, full_var, precision, mean_out, var_out, nullptr, 0.0, false);
+  PostReq r{m, Xs, Hs, beta, sigma, precision, mean_out, full_var ? PostVar::FULL : PostVar::DIAG, var_out};
+  return posterior_impl(c, r);
 }
 
 int gpe_noise_sample(gpe_ctx* c, int64_t m, const double* Xs, const double* Hs, const double* beta,
@@ -3397,12 +3367,12 @@ int gpe_noise_sample(gpe_ctx* c, int64_t m, const double* Xs, const double* Hs, 
   Fact& F = c->aux;
   CHK(ensure_fact(c, F, mp));
   CHK(build_plan(c, F));
-  if (m <= 16384) {
-    CHK(posterior_impl(c, m, Xs, Hs, beta, sigma, 1, 64, mean_out, nullptr, r_new, r_scale, true));
+  const bool one = m <= POST_CHUNK_FULL;
+  PostReq r{m, Xs, Hs, beta, sigma, 64, mean_out, one ? PostVar::FULL_DW3 : PostVar::FULL_DEV, nullptr,
+            one ? nullptr : F.A, r_new, r_scale};
+  CHK(posterior_impl(c, r));
+  if (one)
     HIPCHK(c, hipMemcpyAsync(F.A, c->dW3, (size_t)mp * mp * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-  } else {
-    CHK(posterior_impl(c, m, Xs, Hs, beta, sigma, 1, 64, mean_out, nullptr, r_new, r_scale, true, F.A));
-  }
   HIPCHK(c, hipMemsetAsync(c->dinfo, 0, sizeof(int), c->stream));
   CHK(potrf(c, F));
   int info = 0;
@@ -3415,7 +3385,7 @@ int gpe_noise_sample(gpe_ctx* c, int64_t m, const double* Xs, const double* Hs, 
   hipLaunchKernelGGL(k_zero_upper_diag_tiles, dim3((unsigned)mt), dim3(256), 0, c->stream, F.A, mp);
   HIPCHK(c, hipGetLastError());
   // U^T (mp x sp, column j = draw j, zero padding) and e = t - mean
-  CHK(grow(c, &c->dNU, &c->nu_cap, 2 * (size_t)mp * sp + 2 * (size_t)mp));
+  CHK(grow_buf(c, &c->dNU, &c->nu_cap, 2 * (size_t)mp * sp + 2 * (size_t)mp));
   double* dU = c->dNU;
   double* dY = c->dNU + (size_t)mp * sp;
   double* dE = dY + (size_t)mp * sp;
@@ -3429,13 +3399,7 @@ int gpe_noise_sample(gpe_ctx* c, int64_t m, const double* Xs, const double* Hs, 
   for (long long i = 0; i < m; ++i) c->hpin[i] = t[i] - mean_out[i];
   HIPCHK(c, hipMemcpyAsync(dE, c->hpin, (size_t)mp * sizeof(double), hipMemcpyHostToDevice, c->stream));
   // Y = L U^T: the s draws L.dot(u) of noise_fit.py:135-136 as one MFMA GEMM
-  std::vector<GemmProb> pv = {mkprob(F.A, mp, dU, mp, dY, mp, mt, st, (int)mp, G_KEND_TI, 1.0, 0.0)};
-  pv[0].tile_begin = 0;
-  pv[0].ntiles = mt * st;
-  HIPCHK(c, hipMemcpyAsync(c->dprobs + ADHOC_DESC_BASE + 3, pv.data(), sizeof(GemmProb), hipMemcpyHostToDevice,
-                           c->stream));
-  Launch L{3, ADHOC_DESC_BASE + 3, 1, mt * st, 0.0};
-  CHK(launch_gemm_range(c, L));
+  CHK(adhoc_gemm(c, ADHOC_NOISE, {{3, mkprob(F.A, mp, dU, mp, dY, mp, mt, st, (int)mp, G_KEND_TI, 1.0, 0.0)}}));
   // z_i = sum_j 0.5 (e_i - Y_ij)^2  (noise_fit.py:137)
   hipLaunchKernelGGL(k_noise_sq, dim3((unsigned)(mp / 256 + 1)), dim3(256), 0, c->stream, dY, mp, s, dE,
                      (int)m, dZs);
@@ -3472,14 +3436,15 @@ int gpe_posterior_pivchol(gpe_ctx* c, int64_t m, const double* Xs, const double*
     for (int i = 0; i < 8; ++i) c->phase_ms[i] = 0.0;
     HIPCHK(c, hipEventRecord(c->ev[0], c->stream));
   }
-  CHK(posterior_impl(c, m, Xs, Hs, beta, sigma, 1, 64, mean_out, nullptr, r_new, r_scale, true));
+  PostReq r{m, Xs, Hs, beta, sigma, 64, mean_out, PostVar::FULL_DW3, nullptr, nullptr, r_new, r_scale};
+  CHK(posterior_impl(c, r));
   // workspace: [state | pivvar (k) | piv (k ints)] (read back in one copy), d (m_pad), the
   // partial maxima (2 G), then the ints: flags (m_pad) and partial indices (2 G)
   const size_t kh = (size_t)(k + 1) / 2;
   const size_t head = 2 + (size_t)k + kh;
-  CHK(grow(c, &c->dPc, &c->pc_cap, head + (size_t)mp + 2 * (size_t)G + (size_t)mp / 2 + (size_t)G));
+  CHK(grow_buf(c, &c->dPc, &c->pc_cap, head + (size_t)mp + 2 * (size_t)G + (size_t)mp / 2 + (size_t)G));
   const size_t wsz = (size_t)mp * PC_PANEL;
-  CHK(grow(c, &c->dPcL, &c->pcl_cap, wsz + (L_out ? (size_t)m * (size_t)k : 0)));
+  CHK(grow_buf(c, &c->dPcL, &c->pcl_cap, wsz + (L_out ? (size_t)m * (size_t)k : 0)));
   double* W = c->dPcL;
   double* Ld = c->dPcL + wsz;
   PcArgs a;
@@ -3494,13 +3459,11 @@ int gpe_posterior_pivchol(gpe_ctx* c, int64_t m, const double* Xs, const double*
   a.tol = tol;
   static_assert(sizeof(PcState) == 2 * sizeof(double), "PcState");
   // the trailing update's descriptor: S -= W W^T, every tile, K = PC_PANEL (the same for every panel)
-  std::vector<GemmProb> pv = {mkprob(W, mp, W, mp, c->dW3, mp, mt, mt, PC_PANEL, 0, -1.0, 1.0)};
-  pv[0].tile_begin = 0;
-  pv[0].ntiles = mt * mt;
-  const Launch Lt{0, ADHOC_DESC_BASE + 4, 1, mt * mt, 2.0 * (double)mp * (double)mp * PC_PANEL};
-  if (k > PC_PANEL)
-    HIPCHK(c, hipMemcpyAsync(c->dprobs + ADHOC_DESC_BASE + 4, pv.data(), sizeof(GemmProb), hipMemcpyHostToDevice,
-                             c->stream));
+  Launch Lt{};
+  if (k > PC_PANEL) {
+    CHK(adhoc_gemm(c, ADHOC_PIVCHOL, {{0, mkprob(W, mp, W, mp, c->dW3, mp, mt, mt, PC_PANEL, 0, -1.0, 1.0)}}, &Lt));
+    Lt.flops = 2.0 * (double)mp * (double)mp * PC_PANEL;
+  }
   hipLaunchKernelGGL(k_pc_init, dim3(G), dim3(PC_ROWS), 0, c->stream, a, (int)k);
   HIPCHK(c, hipGetLastError());
   float ms = 0.f;
@@ -3878,15 +3841,12 @@ int gpe_test_gemm(gpe_ctx* c, int32_t trans_a, int32_t trans_b, int64_t M, int64
     copy_checked(c, rc, da, ha.data(), ha.size() * sizeof(double), hipMemcpyHostToDevice);
     copy_checked(c, rc, db, hb.data(), hb.size() * sizeof(double), hipMemcpyHostToDevice);
     copy_checked(c, rc, dc, hc.data(), hc.size() * sizeof(double), hipMemcpyHostToDevice);
-    GemmProb p = mkprob(da, lda, db, ldb, dc, M, (int)(M / TILE), (int)(N / TILE), (int)K, 0, alpha, beta);
-    p.tile_begin = 0;
-    p.ntiles = p.mt * p.nt;
-    copy_checked(c, rc, c->dprobs + ADHOC_DESC_BASE + 8, &p, sizeof(GemmProb), hipMemcpyHostToDevice);
-    HIPCHK(c, hipMemsetAsync(c->dinfo, 0, sizeof(int), c->stream));
+    const GemmProb p = mkprob(da, lda, db, ldb, dc, M, (int)(M / TILE), (int)(N / TILE), (int)K, 0, alpha, beta);
     const int kind = trans_a ? (trans_b ? 2 : 1) : (trans_b ? 3 : 0);
-    Launch L{kind, ADHOC_DESC_BASE + 8, 1, p.ntiles, 0.0};
-    L.cdef = gemm_cdef(p);
-    rc = launch_gemm_range(c, L);
+    Launch L{};
+    if (rc == GPE_OK) rc = adhoc_gemm(c, ADHOC_TEST, {{kind, p}}, &L, true);
+    HIPCHK(c, hipMemsetAsync(c->dinfo, 0, sizeof(int), c->stream));
+    if (rc == GPE_OK) rc = launch_gemm_range(c, L);
     if (rc == GPE_OK) {
       hipError_t e = hipStreamSynchronize(c->stream);
       if (e != hipSuccess) rc = fail(c, GPE_ERR_HIP, hipGetErrorString(e));
@@ -3927,17 +3887,14 @@ int gpe_bench_gemm(gpe_ctx* c, int32_t trans_a, int32_t trans_b, int32_t mt, int
     // 128 values); =2 operands from a window of (tiles + K) x 128 doubles (ld = 128: L2-
     // resident, every k still reads other values, so the MFMA inputs toggle as when cold)
     if (const char* hot = std::getenv("GPEMU_BENCH_HOT")) lda = ldb = (std::atoi(hot) == 2) ? TILE : 0;
-    GemmProb p = mkprob(da, lda, db, ldb, dc, M, mt, nt, K, lower ? G_CLOWER : 0, -1.0, beta);
-    p.tile_begin = 0;
-    p.ntiles = prob_tiles(p);
-    (void)hipMemcpy(c->dprobs + ADHOC_DESC_BASE + 16, &p, sizeof(GemmProb), hipMemcpyHostToDevice);
-    HIPCHK(c, hipMemsetAsync(c->dinfo, 0, sizeof(int), c->stream));
+    const GemmProb p = mkprob(da, lda, db, ldb, dc, M, mt, nt, K, lower ? G_CLOWER : 0, -1.0, beta);
     const int kind = trans_a ? (trans_b ? 2 : 1) : (trans_b ? 3 : 0);
-    Launch L{kind, ADHOC_DESC_BASE + 16, 1, p.ntiles, 0.0};
-    L.cdef = gemm_cdef(p);
+    Launch L{};
+    rc = adhoc_gemm(c, ADHOC_BENCH, {{kind, p}}, &L, true);
+    HIPCHK(c, hipMemsetAsync(c->dinfo, 0, sizeof(int), c->stream));
     const bool prof = c->prof;
     c->prof = false;
-    rc = launch_gemm_range(c, L);   // warm-up
+    if (rc == GPE_OK) rc = launch_gemm_range(c, L);   // warm-up
     hipEvent_t e0, e1;
     (void)hipEventCreate(&e0);
     (void)hipEventCreate(&e1);
