@@ -1,5 +1,6 @@
 """Public API with the reference's signatures (emulatorfunctions.py:13-286):
-setup, train, plot, posterior, posterior_sample; and loo, which the reference lacks."""
+setup, train, plot, posterior, posterior_sample; and loo and posterior_gradient, which the
+reference lacks."""
 from __future__ import annotations
 
 import numpy as _np
@@ -89,6 +90,15 @@ def posterior(E, x, predict=True):
     xs = _model.Data(x, None, E.basis, E.par, E.beliefs, E.K)
     p = _model.Posterior(xs, E.training, E.par, E.beliefs, E.K, predict=predict)
     return p.mean, p.var
+
+
+def posterior_gradient(E, x, want_var=True):
+    """(dmean, dvar), m x d each: the gradients of ``posterior``'s mean and of the diagonal of
+    its covariance with respect to x, as ``posterior`` takes it (no counterpart in the
+    reference).  Analytic and for every kernel family; dvar is None without want_var."""
+    x = _as_points(E, x)
+    xs = _model.Data(x, None, E.basis, E.par, E.beliefs, E.K)
+    return _model.posterior_gradient(xs, E.training, E.par, E.K, want_var=want_var)
 
 
 def loo(E):

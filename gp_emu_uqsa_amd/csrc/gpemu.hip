@@ -29,6 +29,7 @@
 #include "gpemu_snb.hpp"
 #include "gpemu_ozaki.hpp"
 #include "gpemu_pivchol.hpp"
+#include "gpemu_postgrad.hpp"
 #include "gpemu_host_alloc.hpp"
 
 using namespace gpe;
@@ -44,13 +45,15 @@ constexpr int ADHOC_DESC_BASE = MAX_PROBS - 64;
 // Descriptor slots of the GEMMs outside the cached plans (adhoc_gemm), each named for its
 // owner.  Live within one call: gpe_noise_sample and gpe_posterior_pivchol run the posterior
 // first (ADHOC_POST_V, then the ADHOC_COV pair, re-uploaded per chunk and per block) and then
-// their own slot; ADHOC_PIVCHOL is uploaded once and launched after every panel of that call.
+// their own slot; ADHOC_PIVCHOL is uploaded once and launched after every panel of that call;
+// gpe_posterior_grad re-uploads the ADHOC_POST_U pair per chunk, behind that chunk's ADHOC_POST_V.
 // The test and bench GEMMs stand alone.
 enum AdhocSlot {
   ADHOC_POST_V = ADHOC_DESC_BASE + 0,     // posterior: V = L^-1 K* of one chunk
   ADHOC_COV = ADHOC_DESC_BASE + 1,        // cov_block: -s2 V^T V, then +s2 T T^T (two slots)
   ADHOC_NOISE = ADHOC_DESC_BASE + 3,      // gpe_noise_sample: the draws L U^T
   ADHOC_PIVCHOL = ADHOC_DESC_BASE + 4,    // gpe_posterior_pivchol: the trailing update S -= W W^T
+  ADHOC_POST_U = ADHOC_DESC_BASE + 5,     // gpe_posterior_grad: U = L^-T V, then U += G tau^T (two slots)
   ADHOC_TEST = ADHOC_DESC_BASE + 8,       // gpe_test_gemm
   ADHOC_BENCH = ADHOC_DESC_BASE + 16,     // gpe_bench_gemm
 };
@@ -270,6 +273,10 @@ struct gpe_ctx {
   double* dPc = nullptr;
   double* dPcL = nullptr;
   size_t pc_cap = 0, pcl_cap = 0;
+  // gradient of the posterior (gpe_posterior_grad): the chunk's basis and its derivative, tau,
+  // Q^-1, beta, hdim, the results, k_post_grad's partial sums and G padded to the GEMM's K step
+  double* dPg = nullptr;
+  size_t pg_cap = 0;
 
   // resident factor (gpe_factor)
   bool factor_valid = false;
@@ -2138,7 +2145,7 @@ void gpe_destroy(gpe_ctx* c) {
                     c->aux.logdet, c->dinvdelta, c->dZ,
                     c->dR2, c->dWa, c->dskp, c->dgpart, c->dgram, c->dT2, c->dcpart, c->dcsum,
                     c->dW1, c->dW2, c->dW3, c->dXs, c->dXsw, c->dsmall, c->dtiny, c->dsnb, c->dRn, c->dNU,
-                    c->dVall, c->dXall, c->dTall, c->dPc, c->dPcL};
+                    c->dVall, c->dXall, c->dTall, c->dPc, c->dPcL, c->dPg};
   for (double* b : bufs)
     if (b) hipFree(b);
   if (c->dinfo) hipFree(c->dinfo);
@@ -2992,7 +2999,33 @@ struct PostReq {
   // variance's diagonal: Dnew's own r/s2 in Dnew.A (_emulatorclasses.py:572-575, :625)
   const double* rnew = nullptr;
   double rnew_scale = 0.0;
+  // gpe_posterior_grad (DIAG, precision 64): dmean_out set asks for the gradients.  dHs
+  // (m x q): each basis column's derivative in its own input hdim[j] (-1: a constant column)
+  const double* dHs = nullptr;
+  const int32_t* hdim = nullptr;
+  double* dmean_out = nullptr;    // m x d
+  double* dvar_out = nullptr;     // m x d, or NULL: the second product is skipped
 };
+
+// k_post_grad<DMAX, FAM, WIDE, WB> for d inputs: the register widths of d <= 32, beyond that
+// the wide instance with one workgroup column per 32 dimensions (grid.z)
+template <int FAM, bool WB>
+void launch_post_grad_fam(int d, dim3 g, hipStream_t st, const PostGradArgs& a) {
+  const dim3 b(PG_PTS);
+  if (d > 32) hipLaunchKernelGGL((k_post_grad<PG_WIDE, FAM, true, WB>), g, b, 0, st, a);
+  else if (d <= 4) hipLaunchKernelGGL((k_post_grad<4, FAM, false, WB>), g, b, 0, st, a);
+  else if (d <= 8) hipLaunchKernelGGL((k_post_grad<8, FAM, false, WB>), g, b, 0, st, a);
+  else if (d <= 12) hipLaunchKernelGGL((k_post_grad<12, FAM, false, WB>), g, b, 0, st, a);
+  else if (d <= 16) hipLaunchKernelGGL((k_post_grad<16, FAM, false, WB>), g, b, 0, st, a);
+  else hipLaunchKernelGGL((k_post_grad<32, FAM, false, WB>), g, b, 0, st, a);
+}
+
+template <bool WB>
+void launch_post_grad(int fam, int d, dim3 g, hipStream_t st, const PostGradArgs& a) {
+  if (fam == FAM_MATERN32) launch_post_grad_fam<FAM_MATERN32, WB>(d, g, st, a);
+  else if (fam == FAM_MATERN52) launch_post_grad_fam<FAM_MATERN52, WB>(d, g, st, a);
+  else launch_post_grad_fam<FAM_GAUSS, WB>(d, g, st, a);
+}
 
 // One chunk of points as cov_block reads it
 struct CovSide {
@@ -3016,13 +3049,20 @@ struct Posterior : PostReq {
   std::vector<double> Kinv;    // Kq^-1, Kq Kq^T = H^T A^-1 H
   size_t rs = 0;               // one result slot: Y (mp x P), then the column norms
   double *pin_in[2] = {}, *pin_out[2] = {};   // pinned staging: two slots of points, two of results
+  // the gradients (grad): pinned slots of [Hs, dHs] and of [dmean, dvar], the parts of c->dPg
+  const bool grad;
+  double *gpin_in[2] = {}, *gpin_out[2] = {};
+  struct {
+    double *Hs, *dHs, *tau, *Qinv, *beta, *dmean, *dvar, *part, *Gq;
+    int* hdim;
+  } g = {};
 
   Posterior(gpe_ctx* ctx, const PostReq& r)
       : PostReq(r), c(ctx), full(var != PostVar::DIAG), f32(precision == 32),
         ozp(c->oz_on && c->n_pad >= std::min(c->oz_min_np, OZ_POST_MIN_NP) && c->n_pad <= OZ_POST_MAX_NP),
         d(c->d), q(c->q), P(q + 1), kq(((q + 15) / 16) * 16), np(c->n_pad),
         CHUNK(full ? POST_CHUNK_FULL : POST_CHUNK_DIAG), big(full && m > CHUNK), mtot(pad_tile(m)),
-        mp0(pad_tile(std::min<long long>(CHUNK, m))) {}
+        mp0(pad_tile(std::min<long long>(CHUNK, m))), grad(r.dmean_out != nullptr) {}
 
   // Setup: the fp32 copy of L^-1 where the fp32 product needs it, [gamma, G] =
   // A^-1 [f - H beta, H] (in dWa; L^-1 [..] in dZ), Kq and its inverse, the kernel's constants.
@@ -3079,12 +3119,21 @@ struct Posterior : PostReq {
     CHK(ensure_small(c, 2 * rs + 64));
     // (the full covariance also stages T Kq^-T, mp x kq, at the front: the capacity is set
     // here once, so the slots never move)
-    CHK(ensure_pinned(c, std::max<size_t>(2 * (size_t)mp0 * d + 2 * rs + d, (size_t)mp0 * kq) + 64));
+    // (the gradients add two slots of [Hs, dHs] and two of [dmean, dvar] behind 1 / delta)
+    const size_t gsl = grad ? 2 * (size_t)mp0 * q + 2 * (size_t)mp0 * d : 0;
+    CHK(ensure_pinned(c, std::max<size_t>(2 * (size_t)mp0 * d + 2 * rs + d + 2 * gsl, (size_t)mp0 * kq) + 64));
     pin_in[0] = c->hpin, pin_in[1] = pin_in[0] + (size_t)mp0 * d;
     pin_out[0] = pin_in[1] + (size_t)mp0 * d, pin_out[1] = pin_out[0] + rs;
     double* pin_dl = pin_out[1] + rs;   // 1 / delta
     for (int k = 0; k < d; ++k) pin_dl[k] = 1.0 / c->f_delta[k];
     HIPCHK(c, hipMemcpyAsync(c->dinvdelta, pin_dl, d * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    if (grad) {
+      for (int i = 0; i < 2; ++i) {
+        gpin_in[i] = pin_dl + d + i * gsl;
+        gpin_out[i] = gpin_in[i] + 2 * (size_t)mp0 * q;
+      }
+      CHK(grad_workspace());
+    }
     if (!c->ev_pipe[0])
       for (hipEvent_t& e : c->ev_pipe) HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
     return GPE_OK;
@@ -3145,6 +3194,108 @@ struct Posterior : PostReq {
     return GPE_OK;
   }
 
+  // k_post_grad's split of the training rows for a chunk of mp points: about 1024 workgroups
+  // (two per SIMD pair of the chip), at most 64 partial sums per point and dimension
+  int grad_nsplit(long long mp) const {
+    const long long cols = (mp / PG_PTS) * (d > 32 ? (d + PG_WIDE - 1) / PG_WIDE : 1);
+    return (int)std::max<long long>(1, std::min<long long>({np / PG_RI, 64, 1024 / cols}));
+  }
+
+  // The gradients' device workspace (the parts of c->dPg, U in dW3) and what does not change
+  // from chunk to chunk: Q^-1 = Kq^-T Kq^-1, beta, hdim, and G = dWa's columns 1..q copied
+  // into kq zero-padded columns, the first operand of the rank-q update.
+  int grad_workspace() {
+    const long long mpl = pad_tile(m - ((m - 1) / CHUNK) * CHUNK);   // the last chunk
+    const size_t nhd = (size_t)q / 2 + 1;
+    // (a and b sums of every split; a short last chunk may split its rows further than the first)
+    const size_t npart =
+        2 * (size_t)d * std::max<size_t>((size_t)grad_nsplit(mp0) * mp0, (size_t)grad_nsplit(mpl) * mpl);
+    const size_t sz[] = {(size_t)mp0 * q, (size_t)mp0 * q, (size_t)mp0 * kq, (size_t)q * q, (size_t)q, nhd,
+                         (size_t)mp0 * d, (size_t)mp0 * d, npart, (size_t)np * kq};
+    size_t tot = 0;
+    for (size_t s : sz) tot += s;
+    CHK(grow_buf(c, &c->dPg, &c->pg_cap, tot));
+    double* p = c->dPg;
+    g.Hs = p, p += sz[0];
+    g.dHs = p, p += sz[1];
+    g.tau = p, p += sz[2];
+    g.Qinv = p, p += sz[3];
+    g.beta = p, p += sz[4];
+    g.hdim = reinterpret_cast<int*>(p), p += sz[5];
+    g.dmean = p, p += sz[6];
+    g.dvar = p, p += sz[7];
+    g.part = p, p += sz[8];
+    g.Gq = p;
+    std::vector<double> hc((size_t)q * q + q + nhd, 0.0);
+    for (int a = 0; a < q; ++a)
+      for (int b = 0; b < q; ++b) {
+        double acc = 0.0;
+        for (int o = 0; o < q; ++o) acc += Kinv[o * q + a] * Kinv[o * q + b];
+        hc[(size_t)a * q + b] = acc;
+      }
+    for (int i = 0; i < q; ++i) hc[(size_t)q * q + i] = beta[i];
+    std::memcpy(hc.data() + (size_t)q * q + q, hdim, (size_t)q * sizeof(int32_t));
+    // (Q^-1, beta and hdim lie together; a blocking copy, once per call)
+    HIPCHK(c, hipMemcpy(g.Qinv, hc.data(), hc.size() * sizeof(double), hipMemcpyHostToDevice));
+    if (!dvar_out) return GPE_OK;
+    CHK(grow_buf(c, &c->dW3, &c->w3_cap, (size_t)np * mp0));
+    HIPCHK(c, hipMemsetAsync(g.Gq, 0, (size_t)np * kq * sizeof(double), c->stream));
+    HIPCHK(c, hipMemcpyAsync(g.Gq, c->dWa + np, (size_t)np * q * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    return GPE_OK;
+  }
+
+  // One chunk's gradients, queued behind its dev_chunk (Y in dY, V in dW2): tau on the
+  // device from Y (no host round trip, so the two-chunk pipeline stays as it is), U =
+  // L^-T V + G tau^T in dW3, the fused sums, the epilogue, and the copy of [dmean, dvar] into
+  // the pinned slot.  L^-1 is read K-contiguous from its row tile on, as the LAUUM reads it.
+  int grad_chunk(long long s0, int slot, const double* dY) {
+    const long long mc = std::min(CHUNK, m - s0), mp = pad_tile(mc);
+    const int mt = (int)(mp / TILE);
+    const size_t hq = (size_t)mc * q, md = (size_t)mp * d;
+    double* hin = gpin_in[slot];
+    std::memcpy(hin, Hs + s0 * q, hq * sizeof(double));
+    std::memcpy(hin + (size_t)mp0 * q, dHs + s0 * q, hq * sizeof(double));
+    HIPCHK(c, hipMemcpyAsync(g.Hs, hin, hq * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(g.dHs, hin + (size_t)mp0 * q, hq * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    const bool wb = dvar_out != nullptr;
+    if (wb) {
+      hipLaunchKernelGGL(k_post_tau, dim3((unsigned)((mp * kq + 255) / 256)), dim3(256), 0, c->stream, dY, (int)mp,
+                         (int)mc, q, kq, g.Hs, g.Qinv, g.tau);
+      HIPCHK(c, hipGetLastError());
+      CHK(adhoc_gemm(c, ADHOC_POST_U,
+                     {{2, mkprob(c->tr.B, np, c->dW2, np, c->dW3, np, c->NB, mt, (int)np, G_KBEG_TI, 1.0, 0.0)},
+                      {0, mkprob(g.Gq, np, g.tau, mp, c->dW3, np, c->NB, mt, kq, 0, 1.0, 1.0)}}));
+    }
+    PostGradArgs a;
+    a.xw = c->dXw; a.xsw = c->dXsw; a.gam = c->dWa; a.U = wb ? c->dW3 : nullptr; a.ldu = np;
+    a.part = g.part; a.n = (int)c->n; a.np = (int)np; a.mp = (int)mp; a.d = d; a.nsplit = grad_nsplit(mp);
+    const dim3 grid((unsigned)(mp / PG_PTS), (unsigned)a.nsplit, (unsigned)(d > 32 ? (d + PG_WIDE - 1) / PG_WIDE : 1));
+    if (c->prof) HIPCHK(c, hipEventRecord(c->ev[4], c->stream));
+    if (wb) launch_post_grad<true>(fam, d, grid, c->stream, a);
+    else launch_post_grad<false>(fam, d, grid, c->stream, a);
+    HIPCHK(c, hipGetLastError());
+    if (c->prof) {   // (profiling only: one synchronisation per chunk)
+      float ms = 0.f;
+      HIPCHK(c, hipEventRecord(c->ev[5], c->stream));
+      HIPCHK(c, hipEventSynchronize(c->ev[5]));
+      (void)hipEventElapsedTime(&ms, c->ev[4], c->ev[5]);
+      c->phase_ms[0] += ms;
+      c->phase_ms[1] += 1.0;
+    }
+    PostGradFin f;
+    f.part = g.part; f.invdelta = c->dinvdelta; f.dHs = g.dHs; f.hdim = g.hdim; f.beta = g.beta; f.tau = g.tau;
+    f.dmean = g.dmean; f.dvar = wb ? g.dvar : nullptr; f.coff = coff; f.s2 = s2;
+    f.nsplit = a.nsplit; f.mp = (int)mp; f.mc = (int)mc; f.d = d; f.q = q;
+    hipLaunchKernelGGL(k_post_grad_fin, dim3((unsigned)((md + 255) / 256)), dim3(256), 0, c->stream, f);
+    HIPCHK(c, hipGetLastError());
+    // (dmean and dvar are adjacent: mp0 x d each)
+    HIPCHK(c, hipMemcpyAsync(gpin_out[slot], g.dmean, md * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (wb)
+      HIPCHK(c, hipMemcpyAsync(gpin_out[slot] + (size_t)mp0 * d, g.dvar, md * sizeof(double), hipMemcpyDeviceToHost,
+                               c->stream));
+    return GPE_OK;
+  }
+
   // Per-point host algebra, from the chunk's Y = K*^T [gamma, G] (Yh, mp x P column-major):
   // the mean Y_0 + hs . beta into mean_out, and row(o, (T Kq^-T)_o) for o < q, T = Hs - K*^T G.
   template <class Row>
@@ -3173,6 +3324,12 @@ struct Posterior : PostReq {
         var_out[s0 + s] = s2 * (cdiag - nrm[s] + tq);
       }
     };
+    // the chunk's gradients out of its pinned slot (row-major, the points contiguous)
+    auto host_grad = [&](long long s0, const double* out) {
+      const size_t cnt = (size_t)std::min(CHUNK, m - s0) * d;
+      std::memcpy(dmean_out + s0 * d, out, cnt * sizeof(double));
+      if (dvar_out) std::memcpy(dvar_out + s0 * d, out + (size_t)mp0 * d, cnt * sizeof(double));
+    };
     int slot = 0;
     long long prev = -1;
     auto pipeline = [&]() -> int {
@@ -3190,15 +3347,18 @@ struct Posterior : PostReq {
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, hipMemcpyAsync(pin_out[slot], dY, ((size_t)mp * P + mp) * sizeof(double), hipMemcpyDeviceToHost,
                                  c->stream));
+        if (grad) CHK(grad_chunk(s0, slot, dY));
         HIPCHK(c, hipEventRecord(c->ev_pipe[slot], c->stream));
         if (prev >= 0) {
           HIPCHK(c, hipEventSynchronize(c->ev_pipe[slot ^ 1]));
           host_chunk(prev, pin_out[slot ^ 1]);
+          if (grad) host_grad(prev, gpin_out[slot ^ 1]);
         }
         prev = s0;
       }
       HIPCHK(c, hipEventSynchronize(c->ev_pipe[slot ^ 1]));
       host_chunk(prev, pin_out[slot ^ 1]);
+      if (grad) host_grad(prev, gpin_out[slot ^ 1]);
       return GPE_OK;
     };
     const int rc = pipeline();
@@ -3334,6 +3494,13 @@ int posterior_impl(gpe_ctx* c, const PostReq& r) {
   if (r.precision != 64 && r.precision != 32) return fail(c, GPE_ERR_ARG, "precision must be 64 or 32");
   if (r.precision == 32 && r.var != PostVar::DIAG)
     return fail(c, GPE_ERR_UNSUPPORTED, "precision 32 is for the diagonal variance");
+  if (r.dmean_out) {
+    if (r.var != PostVar::DIAG || r.precision != 64 || !r.dHs || !r.hdim)
+      return fail(c, GPE_ERR_ARG, "bad posterior_grad args");
+    for (int j = 0; j < c->q; ++j)
+      if (r.hdim[j] < -1 || r.hdim[j] >= c->d)
+        return fail(c, GPE_ERR_ARG, "hdim[" + std::to_string(j) + "] is outside [-1, d)");
+  }
   CHK(ensure_linv(c));
   Posterior S(c, r);
   CHK(S.setup());
@@ -3348,6 +3515,22 @@ extern "C" {
 int gpe_posterior(gpe_ctx* c, int64_t m, const double* Xs, const double* Hs, const double* beta,
                   double sigma, int32_t full_var, int32_t precision, double* mean_out, double* var_out) {
   PostReq r{m, Xs, Hs, beta, sigma, precision, mean_out, full_var ? PostVar::FULL : PostVar::DIAG, var_out};
+  return posterior_impl(c, r);
+}
+
+int gpe_posterior_grad(gpe_ctx* c, int64_t m, const double* Xs, const double* Hs, const double* dHs,
+                       const int32_t* hdim, const double* beta, double sigma, double* mean_out, double* var_out,
+                       double* dmean_out, double* dvar_out) {
+  CHK(check_ready(c));
+  if (!c->factor_valid) return fail(c, GPE_ERR_STATE, "no resident factor (call gpe_factor)");
+  if (!dHs || !hdim || !dmean_out) return fail(c, GPE_ERR_ARG, "bad posterior_grad args");
+  if (c->prof)   // phase 0: k_post_grad's device time over the chunks, phase 1: the chunks
+    for (int i = 0; i < 8; ++i) c->phase_ms[i] = 0.0;
+  PostReq r{m, Xs, Hs, beta, sigma, 64, mean_out, PostVar::DIAG, var_out};
+  r.dHs = dHs;
+  r.hdim = hdim;
+  r.dmean_out = dmean_out;
+  r.dvar_out = dvar_out;
   return posterior_impl(c, r);
 }
 

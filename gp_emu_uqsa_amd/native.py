@@ -47,6 +47,8 @@ SIGNATURES = {
     "gpe_loo": (_ct.c_int, [_VP, _ct.c_double, _D, _D, _D]),
     "gpe_posterior": (_ct.c_int, [_VP, _ct.c_int64, _D, _D, _D, _ct.c_double, _ct.c_int32, _ct.c_int32,
                                   _D, _D]),
+    "gpe_posterior_grad": (_ct.c_int, [_VP, _ct.c_int64, _D, _D, _D, _ct.POINTER(_ct.c_int32), _D, _ct.c_double,
+                                       _D, _D, _D, _D]),
     "gpe_noise_sample": (_ct.c_int, [_VP, _ct.c_int64, _D, _D, _D, _ct.c_double, _D, _ct.c_double,
                                      _D, _ct.c_int32, _D, _D, _D]),
     "gpe_posterior_pivchol": (_ct.c_int, [_VP, _ct.c_int64, _D, _D, _D, _ct.c_double, _D, _ct.c_double,
@@ -287,6 +289,30 @@ class Context:
                                            1 if full_var else 0, int(precision), _ptr(mean), _ptr(var)),
                     "gpe_posterior")
         return mean, var
+
+    def posterior_grad(self, Xs, Hs, dHs, hdim, beta, sigma, want_var=True):
+        """(mean, var, dmean, dvar): the posterior mean and diagonal variance at Xs, bit for bit
+        those of posterior(full_var=False), and their gradients in the point (m x d each, in
+        the coordinates of Xs).  dHs (m x q) is each basis column's derivative in its own
+        input hdim[j] (-1: a constant column).  want_var=False skips the variance gradient's
+        n^2 m product; dvar is then None."""
+        Xs = _f64(Xs)
+        if Xs.ndim == 1:
+            Xs = Xs.reshape(-1, 1)
+        m = Xs.shape[0]
+        Hs = _f64(Hs, (m, self.q))
+        dHs = _f64(dHs, (m, self.q))
+        hdim = _np.ascontiguousarray(hdim, dtype=_np.int32).reshape(self.q)
+        beta = _f64(beta).ravel()
+        mean = _np.zeros(m)
+        var = _np.zeros(m)
+        dmean = _np.zeros((m, self.d))
+        dvar = _np.zeros((m, self.d)) if want_var else None
+        self._check(self.lib.gpe_posterior_grad(self._h, m, _ptr(Xs), _ptr(Hs), _ptr(dHs),
+                                                hdim.ctypes.data_as(_ct.POINTER(_ct.c_int32)), _ptr(beta),
+                                                float(sigma), _ptr(mean), _ptr(var), _ptr(dmean), _ptr(dvar)),
+                    "gpe_posterior_grad")
+        return mean, var, dmean, dvar
 
     def noise_sample(self, Xs, Hs, beta, sigma, t, U, r_new=None, r_scale=0.0):
         """noise_fit's estimation step for the resident factor: the posterior at Xs

@@ -36,13 +36,32 @@ from __future__ import annotations
 
 import numpy as np
 
-from .model import upload_training
+from .model import Data, posterior_gradient, upload_training
 
-__all__ = ["setup", "sense_table", "Sensitivity", "NonGaussianKernel"]
+__all__ = ["setup", "sense_table", "Sensitivity", "NonGaussianKernel", "derivative_measures"]
 
 
 class NonGaussianKernel(ValueError):
     """The emulator's correlation family has no closed-form sensitivity integrals here."""
+
+
+def derivative_measures(emul, x):
+    """Derivative-based global sensitivity measures of the emulator's posterior mean over the
+    points x (m x d, in the coordinates ``posterior`` takes, drawn from the inputs'
+    distribution): (nu, nu / sum(nu)) with nu_k = mean over the points of (d mean / d x_k)^2.
+
+    No closed form is involved, so this works for every correlation family, and it is the
+    route for Matern emulators, on which ``setup`` raises ``NonGaussianKernel``.  One
+    gpe_posterior_grad call without the variance gradient (``posterior_gradient`` with
+    want_var=False)."""
+    x = np.asarray(x, dtype=float)
+    if x.ndim == 1:
+        x = x.reshape(-1, 1)
+    xs = Data(x, None, emul.basis, emul.par, emul.beliefs, emul.K)
+    dmean, _ = posterior_gradient(xs, emul.training, emul.par, emul.K, want_var=False)
+    nu = np.mean(dmean ** 2, axis=0)
+    tot = float(np.sum(nu))
+    return nu, (nu / tot if tot > 0.0 else np.zeros_like(nu))
 
 
 def setup(emul, m, v, case="case2"):

@@ -35,8 +35,9 @@ extern "C" {
                                 7: gpe_lhc_maximin; 8: gpe_dist_rank_bytes,
                                 gpe_device_synchronize, gpe_build_id;
                                 9: gpe_dist_local_rows takes the basis width q;
-                                10: gpe_ozaki_stats (gpe_loo and gpe_posterior_pivchol were
-                                added within 10: additions, nothing existing changed) */
+                                10: gpe_ozaki_stats (gpe_loo, gpe_posterior_pivchol and
+                                gpe_posterior_grad were added within 10: additions, nothing
+                                existing changed) */
 
 enum gpe_status {
     GPE_OK = 0,
@@ -164,6 +165,33 @@ int gpe_loo(gpe_ctx* ctx, double sigma, double* mean_out, double* var_out, doubl
 int gpe_posterior(gpe_ctx* ctx, int64_t m, const double* Xs, const double* Hs,
                   const double* beta, double sigma, int32_t full_var, int32_t precision,
                   double* mean_out, double* var_out);
+
+/* Posterior mean and diagonal variance at m points with their gradients in the point (an
+ * addition within ABI 10; the reference has no counterpart).  Coordinates are those of
+ * gpe_posterior's Xs.  mean_out (m) and var_out (m) are bit for bit what
+ * gpe_posterior(full_var = 0, precision = 64) returns for the same arguments; dmean_out
+ * (m x d row-major) is d mean / d x_k and dvar_out (m x d, or NULL) d var / d x_k.
+ * With s_i = sum_k ((x_k - x_ik) / delta_k)^2, K*_i = coff rho(s_i) (coff = 1 - nu std, 1
+ * alt) and g the family's derivative factor (Gaussian exp(-s), MATERN32 (3/2) exp(-sqrt(3) r),
+ * MATERN52 (5/6)(1 + sqrt(5) r) exp(-sqrt(5) r)):
+ *   d K*_i / d x_k = -2 coff g(s_i) (x_k - x_ik) / delta_k^2
+ *   d mean / d x_k = d_k h . beta + sum_i gamma_i d_k K*_i,    gamma = A^-1 (f - H beta)
+ *   d var / d x_k  = sigma^2 (-2 sum_i u_i d_k K*_i + 2 tau . d_k h),
+ *   tau = (H^T A^-1 H)^-1 (h - G^T K*),  u = A^-1 K* + G tau,  G = A^-1 H.
+ * Nothing divides by r: a point on a training point is fine (MATERN32 is C^1).  Every basis
+ * column depends on one input: dHs (m x q) is each column's derivative in its own input
+ * hdim[j] (q values in [-1, d), -1 a constant column; columns may share an input), so
+ * (d_k h)_j = dHs[., j] if hdim[j] = k, else 0.
+ * Any m, in chunks of 8192 points through the diagonal posterior's two-slot pipeline; per
+ * chunk one more triangular n^2 m product (U = L^-T V, fp64 MFMA; skipped with dvar_out NULL)
+ * and one fused kernel (gpemu_postgrad.hpp).  Every family and nugget kind, with or without
+ * r.  Fixed summation order, no floating-point atomics: repeated calls on one factor return
+ * the same bits, and the resident factor stays usable.
+ * GPE_ERR_STATE without a resident factor; GPE_ERR_ARG for m <= 0, a NULL among Xs, Hs, dHs,
+ * hdim, beta, mean_out, var_out, dmean_out, or hdim[j] outside [-1, d). */
+int gpe_posterior_grad(gpe_ctx* ctx, int64_t m, const double* Xs, const double* Hs,
+                       const double* dHs, const int32_t* hdim, const double* beta, double sigma,
+                       double* mean_out, double* var_out, double* dmean_out, double* dvar_out);
 
 /* ---- Sensitivity / UQ building blocks, resident factor --------
  * Replace the O(n^2) parts of sensitivity/_sensitivityclasses.py (case2): the
@@ -302,6 +330,8 @@ int gpe_posterior_pivchol(gpe_ctx* ctx, int64_t m, const double* Xs, const doubl
  * [4] skinny solves / small algebra, [5] gradient contraction, [6] total.
  * After gpe_posterior_pivchol: [0] forming the covariance, [1] the pivot steps, [2] the
  * trailing updates and panel copies, [6] their sum (one synchronisation per panel is added).
+ * After gpe_posterior_grad: [0] k_post_grad's device time summed over the chunks, [1] the
+ * number of chunks (one synchronisation per chunk is added).
  * Only filled when profiling is on. */
 int gpe_set_profiling(gpe_ctx* ctx, int32_t on);
 int gpe_phase_times(gpe_ctx* ctx, double* ms_out, int32_t n);
