@@ -1834,10 +1834,10 @@ int oz_prepare(gpe_ctx* c, Fact& F) {
   return GPE_OK;
 }
 
-int oz_gemm_crt(gpe_ctx* c, const OzGemm& g, const OzCrt& r, int nti, double ops, double flops64,
+// one k_oz_gemm + k_oz_crt pair with the constants k: tile rows [r.ti0, r.ti0 + nti)
+int oz_gemm_crt(gpe_ctx* c, const OzConst& k, const OzGemm& g, const OzCrt& r, int nti, double ops, double flops64,
                 hipStream_t st = nullptr) {
   if (!st) st = c->stream;
-  const OzConst& k = c->oz_c;
   if (c->prof) {
     while (c->oev_used + 2 > c->oev.size()) {
       hipEvent_t e;
@@ -1854,9 +1854,16 @@ int oz_gemm_crt(gpe_ctx* c, const OzGemm& g, const OzCrt& r, int nti, double ops
     c->oz_ops += ops;
     c->oz_flops64 += flops64;
   }
-  hipLaunchKernelGGL(k_oz_crt, dim3((g.tri ? nti * (nti + 1) / 2 : nti * g.ntj) * 16), dim3(256), 0, st, r, k);
+  const int t1 = r.ti0 + nti;   // (lower tiles of the rows from ti0: those up to t1 less those above ti0)
+  hipLaunchKernelGGL(k_oz_crt, dim3((g.tri ? t1 * (t1 + 1) / 2 - r.ti0 * (r.ti0 + 1) / 2 : nti * g.ntj) * 16), dim3(256),
+                     0, st, r, k);
   HIPCHK(c, hipGetLastError());
   return GPE_OK;
+}
+// ... with the context's constants (oz_prepare)
+int oz_gemm_crt(gpe_ctx* c, const OzGemm& g, const OzCrt& r, int nti, double ops, double flops64,
+                hipStream_t st = nullptr) {
+  return oz_gemm_crt(c, c->oz_c, g, r, nti, ops, flops64, st);
 }
 
 // Between the phases of the split sweep (potrf), in its stream order on st: L11 and L21 are
@@ -4042,6 +4049,173 @@ int gpe_test_gemm(gpe_ctx* c, int32_t trans_a, int32_t trans_b, int64_t M, int64
   if (da) (void)hipFree(da);
   if (db) (void)hipFree(db);
   if (dc) (void)hipFree(dc);
+  return rc;
+}
+
+// ---- gpe_test_oz_product: one int8 product on buffers of its own
+struct OzTestBufs {   // (freed on every way out)
+  double *sa = nullptr, *sb = nullptr, *C = nullptr;
+  int *exa = nullptr, *exb = nullptr;
+  int8_t *pa = nullptr, *pb = nullptr, *res = nullptr;
+  unsigned* list = nullptr;
+  ~OzTestBufs() {
+    for (void* p : {(void*)sa, (void*)sb, (void*)C, (void*)exa, (void*)exb, (void*)pa, (void*)pb, (void*)res, (void*)list})
+      if (p) (void)hipFree(p);
+  }
+};
+
+// the doubles of src that op(r, k), r < R, k < Kv, spans from offset on (0: the window is bad)
+static long long oz_test_extent(const gpe_oz_operand& o, int R, int Kv) {
+  if (!o.src || o.len <= 0 || o.offset < 0 || o.ld < 1 || R < 1 || Kv < 1) return 0;
+  const long long ext = o.trans ? (long long)(Kv - 1) * o.ld + R : (long long)(R - 1) * o.ld + Kv;
+  return ext <= o.len - o.offset ? ext : 0;
+}
+
+// a rectangular operand: source to the device, row exponents, planes (P rows of Kp bytes per
+// modulus), with the launch lines of oz_l21_launch / oz_tri_pair_launches / posterior_oz
+static int oz_test_operand(gpe_ctx* c, const gpe_oz_operand& o, const OzConst& k, int P, int Kp, double** dsrc, int** dex,
+                           int8_t** dpl) {
+  hipStream_t st = c->stream;
+  CHK(dalloc(c, dsrc, (size_t)o.len));
+  CHK(dalloc(c, dex, (size_t)P));
+  CHK(dalloc(c, dpl, (size_t)k.nmod * P * Kp));
+  HIPCHK(c, hipMemcpy(*dsrc, o.src, (size_t)o.len * sizeof(double), hipMemcpyHostToDevice));
+  const double* s = *dsrc + o.offset;
+  const long long pb = (long long)P * Kp;
+  if (o.trans) {
+    HIPCHK(c, hipMemsetAsync(*dex, 0, (size_t)P * sizeof(int), st));
+    hipLaunchKernelGGL(k_oz_rowexp<true>, dim3(P / 64, (o.Kv + 255) / 256), dim3(256), 0, st, s, (long long)o.ld, o.R, P,
+                       o.Kv, o.mask, k.beta, *dex);
+    hipLaunchKernelGGL(k_oz_il_to_ex, dim3((P + 255) / 256), dim3(256), 0, st, *dex, P, k.beta);
+    hipLaunchKernelGGL(k_oz_split_rect<true>, dim3(P / 64, Kp / 64), dim3(256), 0, st, s, (long long)o.ld, o.R, o.Kv,
+                       o.mask, *dex, *dpl, pb, (long long)Kp, Kp, k);
+  } else {
+    hipLaunchKernelGGL(k_oz_rowexp<false>, dim3(P / 4), dim3(256), 0, st, s, (long long)o.ld, o.R, P, o.Kv, o.mask,
+                       k.beta, *dex);
+    hipLaunchKernelGGL(k_oz_split_rect<false>, dim3(P, (Kp + 2047) / 2048), dim3(256), 0, st, s, (long long)o.ld, o.R,
+                       o.Kv, o.mask, *dex, *dpl, pb, (long long)Kp, Kp, k);
+  }
+  HIPCHK(c, hipGetLastError());
+  return GPE_OK;
+}
+
+static int oz_test_product(gpe_ctx* c, const gpe_oz_operand& a, const gpe_oz_operand* b, gpe_oz_params p, double* C,
+                           int32_t* exa_out, int32_t* exb_out, int8_t* res_out) {
+  const auto bad = [&](const char* what) { return fail(c, GPE_ERR_ARG, std::string("gpe_test_oz_product: ") + what); };
+  if (p.nmod < 6 || p.nmod > OZ_MAXMOD) return bad("nmod outside [6, 16]");
+  if (res_out && (p.res_mod < 0 || p.res_mod >= p.nmod)) return bad("res_mod is not a modulus number");
+  if (a.R < 1 || a.R > (1 << 20)) return bad("bad operand rows");
+  const int Pa = (a.R + OZ_T - 1) / OZ_T * OZ_T;
+  int Pb = Pa;
+  if (p.packed) {
+    // k_oz_split's 16-byte loads: every column of X starts 16-byte aligned
+    if (a.R % TILE || (a.offset & 1) || (a.ld & 1) || a.ld < a.R || !oz_test_extent(a, 1, 1) ||
+        (long long)(a.R - 1) * a.ld + a.R > a.len - a.offset)
+      return bad("packed: X is R x R, R a multiple of 128, ld >= R and offset even, inside src");
+    p.K = Pa; p.kbeg = 1; p.kend = 0; p.kdiv = 1; p.ti0 = 0; p.tri = 1; p.lower128 = 1;
+    p.rows = p.cols = a.R;
+    b = nullptr;
+  } else {
+    if (p.K < OZ_SK || p.K % OZ_SK || p.K > OZ_MAX_K) return bad("K is not a multiple of 64 in [64, 2^17 - 128]");
+    if (a.mask < 0 || a.mask > 2 || a.Kv > p.K || !oz_test_extent(a, a.R, a.Kv)) return bad("operand A outside its source");
+    if (b) {
+      if (b->R < 1 || b->R > (1 << 20) || b->mask < 0 || b->mask > 2 || b->Kv > p.K || !oz_test_extent(*b, b->R, b->Kv))
+        return bad("operand B outside its source");
+      Pb = (b->R + OZ_T - 1) / OZ_T * OZ_T;
+    }
+    if (p.kbeg < 0 || p.kbeg > 3 || p.kend < 0 || p.kend > 1 || p.kdiv < 1) return bad("bad kbeg / kend / kdiv");
+    if (p.ti0 < 0 || p.ti0 >= Pa / OZ_T) return bad("ti0 past the last tile row");
+    if (p.tri && Pb < Pa) return bad("tri: B has fewer tile rows than A");
+  }
+  if (p.rows <= OZ_T * p.ti0 || p.rows > Pa || p.cols < 1 || p.cols > Pb) return bad("rows / cols outside the product");
+  if (!C || p.ldc < 1 || p.c_len < 1 || (long long)(p.rows - 1 - OZ_T * p.ti0) + (long long)(p.cols - 1) * p.ldc >= p.c_len)
+    return bad("C too small for rows x cols at ldc");
+  const int K = p.K, ti0 = p.ti0, nti = Pa / OZ_T - ti0, ntj = Pb / OZ_T, t1 = ti0 + nti;
+  const OzConst k = oz_consts(p.nmod, K);
+  OzTestBufs d;
+  hipStream_t st = c->stream;
+  OzGemm g;
+  if (p.packed) {
+    const long long pbytes = oz_plane_bytes(Pa);
+    CHK(dalloc(c, &d.sa, (size_t)a.len));
+    CHK(dalloc(c, &d.exa, (size_t)Pa));
+    CHK(dalloc(c, &d.pa, (size_t)k.nmod * pbytes));
+    HIPCHK(c, hipMemcpy(d.sa, a.src, (size_t)a.len * sizeof(double), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_oz_colexp, dim3((Pa + 3) / 4), dim3(256), 0, st, d.sa + a.offset, (long long)a.ld, a.R, Pa,
+                       k.beta, d.exa);
+    hipLaunchKernelGGL(k_oz_split, dim3(Pa, (Pa + 256 * OZ_SPLIT_ROWS - 1) / (256 * OZ_SPLIT_ROWS)), dim3(256), 0, st,
+                       d.sa + a.offset, (long long)a.ld, a.R, Pa, d.exa, d.pa, pbytes, k);
+    HIPCHK(c, hipGetLastError());
+    g.a = g.b = OzOpnd{d.pa, pbytes, 0, Pa};
+  } else {
+    CHK(oz_test_operand(c, a, k, Pa, K, &d.sa, &d.exa, &d.pa));
+    g.a = g.b = OzOpnd{d.pa, (long long)Pa * K, K, 0};
+    if (b) {
+      CHK(oz_test_operand(c, *b, k, Pb, K, &d.sb, &d.exb, &d.pb));
+      g.b = OzOpnd{d.pb, (long long)Pb * K, K, 0};
+    }
+  }
+  const std::vector<unsigned> list = oz_list(nti, p.tri ? t1 : ntj, p.tri != 0, [&](int ti, int tj) {
+    const int kb = p.kbeg == 1 ? OZ_T * ti : (p.kbeg == 2 ? OZ_T * tj : (p.kbeg == 3 ? 128 * ((2 * ti) / p.kdiv) : 0));
+    return (double)std::max(0, (p.kend ? std::min(K, OZ_T * (ti + 1)) : K) - kb);
+  }, ti0);
+  const long long ntiles = p.tri ? (long long)t1 * (t1 + 1) / 2 - (long long)ti0 * (ti0 + 1) / 2 : (long long)nti * ntj;
+  const long long rb = ntiles * OZ_T * OZ_T;
+  CHK(dalloc(c, &d.list, list.size()));
+  CHK(dalloc(c, &d.res, (size_t)k.nmod * rb));
+  CHK(dalloc(c, &d.C, (size_t)p.c_len));
+  HIPCHK(c, hipMemcpy(d.list, list.data(), list.size() * sizeof(unsigned), hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(d.C, C, (size_t)p.c_len * sizeof(double), hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemsetAsync(d.res, 0, (size_t)k.nmod * rb, st));
+  g.list = d.list;
+  g.list_len = (int)list.size();
+  g.K = K;
+  g.kbeg = p.kbeg;
+  g.kend = p.kend;
+  g.tri = p.tri ? 1 : 0;
+  g.ntj = p.tri ? 0 : ntj;
+  g.res = d.res;
+  g.res_bytes = rb;
+  g.kdiv = p.kdiv;
+  g.ti0 = ti0;
+  OzCrt r{d.res, rb, g.tri, g.ntj, d.exa, b ? d.exb : d.exa, d.C, (long long)p.ldc, p.rows, p.cols, p.lower128 ? 1 : 0,
+          p.alpha, ti0};
+  r.acc = p.acc ? 1 : 0;
+  CHK(oz_gemm_crt(c, k, g, r, nti, 0.0, 0.0));
+  HIPCHK(c, hipStreamSynchronize(st));
+  HIPCHK(c, hipMemcpy(C, d.C, (size_t)p.c_len * sizeof(double), hipMemcpyDeviceToHost));
+  if (exa_out) HIPCHK(c, hipMemcpy(exa_out, d.exa, (size_t)Pa * sizeof(int), hipMemcpyDeviceToHost));
+  if (exb_out) HIPCHK(c, hipMemcpy(exb_out, b ? d.exb : d.exa, (size_t)Pb * sizeof(int), hipMemcpyDeviceToHost));
+  if (res_out) {
+    // k_oz_gemm's order (see there and k_oz_crt) -> (row, column)
+    std::vector<int8_t> h((size_t)rb);
+    HIPCHK(c, hipMemcpy(h.data(), d.res + (long long)p.res_mod * rb, (size_t)rb, hipMemcpyDeviceToHost));
+    std::memset(res_out, 0, (size_t)nti * OZ_T * Pb);
+    const auto tile_of = [&](long long ti, long long tj) { return p.tri ? ti * (ti + 1) / 2 + tj : ti * ntj + tj; };
+    for (const unsigned ent : list) {
+      if (ent == 0xffffffffu) continue;
+      const int ti = (int)(ent >> 16), tj = (int)(ent & 0xffffu);
+      const int8_t* t = h.data() + (tile_of(ti, tj) - tile_of(ti0, 0)) * (OZ_T * OZ_T);
+      for (int u = 0; u < OZ_T * OZ_T / 16; ++u) {
+        const int wave = u >> 10, blk = (u >> 6) & 15, lane = u & 63;
+        const long long gm = OZ_T * (ti - ti0) + (wave >> 1) * 128 + 32 * (blk >> 2) + (lane & 31);
+        const long long gn0 = OZ_T * tj + (wave & 1) * 128 + 32 * (blk & 3) + 4 * (lane >> 5);
+        for (int q = 0; q < 16; ++q) res_out[gm * Pb + gn0 + (q & 3) + 8 * (q >> 2)] = t[(long long)u * 16 + q];
+      }
+    }
+  }
+  return GPE_OK;
+}
+
+int gpe_test_oz_product(gpe_ctx* c, const gpe_oz_operand* a, const gpe_oz_operand* b, const gpe_oz_params* p, double* C,
+                        int32_t* exa_out, int32_t* exb_out, int8_t* res_out) {
+  if (!c) return GPE_ERR_ARG;
+  if (!a || !p) return fail(c, GPE_ERR_ARG, "gpe_test_oz_product: NULL operand or parameters");
+  HIPCHK(c, hipSetDevice(c->device));
+  const bool prof = c->prof;   // (not a product of the objective: kept out of gpe_ozaki_stats)
+  c->prof = false;
+  const int rc = oz_test_product(c, *a, b, *p, C, exa_out, exb_out, res_out);
+  c->prof = prof;
   return rc;
 }
 

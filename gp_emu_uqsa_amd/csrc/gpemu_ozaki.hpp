@@ -90,7 +90,9 @@ static __global__ void __launch_bounds__(256) k_oz_colexp(const double* __restri
 
 // X -> the N int8 planes: thread = 8 consecutive rows of one column (a wave reads 4 KB of
 // the column and writes 512 contiguous bytes per plane); entries above the diagonal (and past
-// np) are zero
+// np) are zero.  Precondition: X is 16-byte aligned and ldx even (every column starts on a
+// 16-byte boundary: the double2 loads below; the callers' ldx is n_pad, a multiple of 128).
+// Entries above the diagonal are never read.
 constexpr int OZ_SPLIT_ROWS = 8;
 static __global__ void __launch_bounds__(256) k_oz_split(const double* __restrict__ X, long long ldx, int np,
                                                          int np2, const int* __restrict__ ex, int8_t* __restrict__ planes,
@@ -167,6 +169,10 @@ __device__ __forceinline__ const int8_t* oz_tile_rows(const OzOpnd& o, int t, in
 // 256 (ti + 1) (kend 0 / 1): the triangular operands' nonzero k (kbeg 3: the rows of a
 // lower-triangular X dealt cyclically by 128-row tiles over kdiv ranks, seen from one rank).
 // Tile rows from ti0 (the residues of tile (ti, tj) at its index less that of (ti0, 0)).
+// Preconditions: every k range a multiple of 64 long (K and the range starts are multiples of
+// 128 or 256 at every call site; a remainder would be dropped without a word: the test hook
+// gpe_test_oz_product refuses such a K), K <= OZ_MAX_K, and the operands zero on the k a
+// range skips.  One product at a time against exact integers: tests/test_gpu_oz_product.py.
 struct OzGemm {
   OzOpnd a, b;
   const unsigned* list;

@@ -30,8 +30,24 @@ MUCM = 1
 _D = _ct.POINTER(_ct.c_double)
 _VP = _ct.c_void_p
 
+class OzOperand(_ct.Structure):
+    """gpe_oz_operand (gpe_test_oz_product)"""
+    _fields_ = [("src", _D), ("len", _ct.c_int64), ("offset", _ct.c_int64), ("ld", _ct.c_int64),
+                ("trans", _ct.c_int32), ("R", _ct.c_int32), ("Kv", _ct.c_int32), ("mask", _ct.c_int32)]
+
+
+class OzParams(_ct.Structure):
+    """gpe_oz_params (gpe_test_oz_product)"""
+    _fields_ = [(n, _ct.c_int32) for n in ("packed", "K", "kbeg", "kend", "kdiv", "ti0", "tri", "lower128", "acc",
+                                           "nmod", "rows", "cols", "res_mod")] + \
+               [("ldc", _ct.c_int64), ("c_len", _ct.c_int64), ("alpha", _ct.c_double)]
+
+
 # name -> (restype, argtypes); the full exported surface of include/gpemu.h
 SIGNATURES = {
+    "gpe_test_oz_product": (_ct.c_int, [_VP, _ct.POINTER(OzOperand), _ct.POINTER(OzOperand),
+                                        _ct.POINTER(OzParams), _D, _ct.POINTER(_ct.c_int32),
+                                        _ct.POINTER(_ct.c_int32), _ct.POINTER(_ct.c_int8)]),
     "gpe_abi_version": (_ct.c_int, []),
     "gpe_build_id": (_ct.c_char_p, []),
     "gpe_device_count": (_ct.c_int, []),
@@ -495,6 +511,43 @@ class Context:
                                            _ptr(B), _ptr(C), float(alpha), float(beta)),
                     "gpe_test_gemm")
         return C
+
+    def test_oz_product(self, a, b=None, *, C, ldc, packed=False, K=0, kbeg=0, kend=0, kdiv=1, ti0=0,
+                        tri=False, lower128=False, alpha=1.0, acc=False, nmod=16, rows=0, cols=0,
+                        res_mod=None):
+        """One exact int8 product through the production kernels (gpe_test_oz_product, a test
+        hook).  a, b: dicts with src (1-d fp64 array, sent as it is), ld and optionally offset,
+        trans, R, Kv, mask; b None: B is A.  C: 1-d fp64 array, the column-major output with
+        leading dimension ldc (copied, read when acc).  Returns dict(C, exa, exb, res): the
+        new C, the row exponents of both operands (padded to 256) and, with res_mod, the
+        centred residues of that modulus as int8 (padded rows from tile row ti0 x padded
+        columns)."""
+        keep = []
+
+        def opnd(o):
+            src = _np.ascontiguousarray(o["src"], dtype=_np.float64).ravel()
+            keep.append(src)
+            return OzOperand(_ptr(src), src.size, int(o.get("offset", 0)), int(o["ld"]), int(o.get("trans", 0)),
+                             int(o.get("R", 0)), int(o.get("Kv", 0)), int(o.get("mask", 0)))
+
+        oa = opnd(a)
+        ob = opnd(b) if b is not None else None
+        pad = lambda r: (r + 255) // 256 * 256
+        Pa = pad(oa.R)
+        Pb = pad(ob.R) if ob is not None else Pa
+        Cc = _np.array(C, dtype=_np.float64).ravel()
+        p = OzParams(int(bool(packed)), int(K), int(kbeg), int(kend), int(kdiv), int(ti0), int(bool(tri)),
+                     int(bool(lower128)), int(bool(acc)), int(nmod), int(rows), int(cols),
+                     -1 if res_mod is None else int(res_mod), int(ldc), Cc.size, float(alpha))
+        exa = _np.zeros(max(Pa, 1), dtype=_np.int32)
+        exb = _np.zeros(max(Pb, 1), dtype=_np.int32)
+        res = None if res_mod is None else _np.zeros((max(Pa - 256 * int(ti0), 1), max(Pb, 1)), dtype=_np.int8)
+        i32 = _ct.POINTER(_ct.c_int32)
+        self._check(self.lib.gpe_test_oz_product(
+            self._h, _ct.byref(oa), _ct.byref(ob) if ob is not None else None, _ct.byref(p), _ptr(Cc),
+            exa.ctypes.data_as(i32), exb.ctypes.data_as(i32),
+            None if res is None else res.ctypes.data_as(_ct.POINTER(_ct.c_int8))), "gpe_test_oz_product")
+        return {"C": Cc, "exa": exa, "exb": exb, "res": res}
 
     def bench_gemm(self, mt, nt, K, trans_a=0, trans_b=0, lower=False, beta=1.0, reps=5):
         ms = _ct.c_double()

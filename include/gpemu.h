@@ -35,9 +35,9 @@ extern "C" {
                                 7: gpe_lhc_maximin; 8: gpe_dist_rank_bytes,
                                 gpe_device_synchronize, gpe_build_id;
                                 9: gpe_dist_local_rows takes the basis width q;
-                                10: gpe_ozaki_stats (gpe_loo, gpe_posterior_pivchol and
-                                gpe_posterior_grad were added within 10: additions, nothing
-                                existing changed) */
+                                10: gpe_ozaki_stats (gpe_loo, gpe_posterior_pivchol,
+                                gpe_posterior_grad and the test hook gpe_test_oz_product were
+                                added within 10: additions, nothing existing changed) */
 
 enum gpe_status {
     GPE_OK = 0,
@@ -274,6 +274,51 @@ int gpe_cholesky(gpe_ctx* ctx, int64_t m, const double* A, double* L_out,
 int gpe_test_gemm(gpe_ctx* ctx, int32_t trans_a, int32_t trans_b, int64_t M, int64_t N,
                   int64_t K, const double* A, const double* B, double* C,
                   double alpha, double beta);
+
+/* Test hook for one exact int8 product (gpemu_ozaki.hpp), an addition within ABI 10; the
+ * reference has no counterpart.  C = alpha op(A) op(B)^T (+ C with acc) through the
+ * production sequence -- exponents, split into int8 planes, k_oz_gemm, k_oz_crt -- on device
+ * buffers of its own, freed on exit; the context's resident factor and cached plans are not
+ * touched.  The tile list comes from oz_list, the constants from oz_consts(nmod, K), the
+ * launches from the routine every single-GPU product goes through.
+ *
+ * An operand is a window of a host fp64 array `src` of `len` doubles, copied to the device
+ * as it is: op(r, k) = src[offset + k + r ld] (trans 0) or src[offset + r + k ld] (trans 1)
+ * for r < R, k < Kv, zero outside, and zero where k < r (mask 1) or k > r (mask 2).  Rows are
+ * padded to a multiple of 256 (Pa, Pb) and k to K.
+ *
+ * Rectangular form (packed 0): a and b (b NULL: B is A, one set of planes and one exponent
+ * array) and the product's parameters, passed on as they are to OzGemm / OzCrt: K (a
+ * multiple of 64 in [64, 2^17 - 128], >= both Kv), kbeg 0 to 3, kend 0 / 1, kdiv >= 1,
+ * ti0 (first tile row: the product covers tile rows [ti0, Pa / 256)), tri (then Pb >= Pa and
+ * only tiles tj <= ti), lower128, alpha, acc, nmod in [6, 16].  C is column-major, c_len
+ * doubles, read first and written back whole: entry (i, j) of the product, i < rows <= Pa,
+ * j < cols <= Pb, goes to C[i - 256 ti0 + j ldc]; nothing else changes.
+ * Packed form (packed 1; the A^-1 = X^T X of the objective's gradient): a describes X, R x R
+ * column-major lower-triangular (R a multiple of 128, trans / Kv / mask ignored, entries above
+ * the diagonal never read), through k_oz_colexp and k_oz_split; K, kbeg, kend, tri, lower128,
+ * ti0, rows and cols are fixed to the production call's (kbeg 1, tri, lower128, rows = cols = R)
+ * and only alpha, acc, nmod, ldc and res_mod are read from p.
+ *
+ * Optional outputs (NULL: skipped): exa_out (Pa ints) / exb_out (Pb ints; with B = A a copy
+ * of exa) the row exponents; res_out the centred residues of modulus number res_mod as
+ * int8, (Pa - 256 ti0) x Pb row-major in the product's own (row, column) order (tiles the
+ * product does not cover: 0).
+ * GPE_ERR_ARG for anything outside the above (K not a multiple of 64 included: the kernel
+ * would drop the remainder silently). */
+typedef struct gpe_oz_operand {
+    const double* src;
+    int64_t len, offset, ld;
+    int32_t trans, R, Kv, mask;
+} gpe_oz_operand;
+typedef struct gpe_oz_params {
+    int32_t packed, K, kbeg, kend, kdiv, ti0, tri, lower128, acc, nmod, rows, cols, res_mod;
+    int64_t ldc, c_len;
+    double alpha;
+} gpe_oz_params;
+int gpe_test_oz_product(gpe_ctx* ctx, const gpe_oz_operand* a, const gpe_oz_operand* b,
+                        const gpe_oz_params* p, double* C, int32_t* exa_out, int32_t* exb_out,
+                        int8_t* res_out);
 
 /* Benchmark hook: time `reps` launches of the grouped GEMM on device-resident
  * random operands: C (mt*128 x nt*128, lower tiles only if lower) += -A B^T-style

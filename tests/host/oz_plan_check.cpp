@@ -73,6 +73,14 @@ static void check_consts() {
   static_assert(OZ_MAX_K <= (1 << 17) - 128, "K bound");
   std::printf("beta12_4096=%d\n", oz_consts(12, 4096).beta);
   std::printf("beta12_16384=%d beta14_16384=%d\n", oz_consts(12, 16384).beta, oz_consts(14, 16384).beta);
+  // the constants tests/oz_product_ref.py restates (tests/test_oz_product_ref_host.py)
+  std::printf("mods=");
+  for (int l = 0; l < OZ_MAXMOD; ++l) std::printf("%d%s", oz_consts(OZ_MAXMOD, 64).m[l], l + 1 < OZ_MAXMOD ? "," : "\n");
+  for (int nmod = 6; nmod <= OZ_MAXMOD; ++nmod) {
+    std::printf("Md %d %a\n", nmod, oz_consts(nmod, 64).Md);
+    for (int K : {64, 128, 192, 256, 320, 448, 512, 576, 1024, 1536, 4096, 16384, 65536, 130560, OZ_MAX_K})
+      std::printf("beta %d %d %d\n", nmod, K, oz_consts(nmod, K).beta);
+  }
 }
 
 // every wanted tile once, the rest 0xffffffff, length a multiple of 8

@@ -21,8 +21,17 @@ def _hipcc():
     return cand if os.path.exists(cand) else shutil.which("hipcc")
 
 
+_RUN = {}   # the program is built and run once a session (test_oz_product_ref_host.py reads it too)
+
+
 @pytest.fixture(scope="module")
 def plan_check(tmp_path_factory):
+    if "run" not in _RUN:
+        _RUN["run"] = _build_and_run(tmp_path_factory)
+    return _RUN["run"]
+
+
+def _build_and_run(tmp_path_factory):
     hipcc = _hipcc()
     if not hipcc:
         pytest.skip("no hipcc: the host check of the int8 plans cannot be built")
