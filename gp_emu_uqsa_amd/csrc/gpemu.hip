@@ -420,6 +420,41 @@ static void launch_pairs_fam(int dm, dim3 g, dim3 b, hipStream_t st, const PairA
   }
 }
 
+// k_tiny<DM, FAM> / k_snb<DM, FAM> for the padded width DM >= d of the one-launch kernels
+template <int FAM>
+static void launch_tiny_fam(int d, size_t lds, hipStream_t st, const TinyArgs& a) {
+  const dim3 g(1 + TINY_NH), b(256);
+  if (d <= 4) hipLaunchKernelGGL((k_tiny<4, FAM>), g, b, lds, st, a);
+  else if (d <= 8) hipLaunchKernelGGL((k_tiny<8, FAM>), g, b, lds, st, a);
+  else if (d <= 12) hipLaunchKernelGGL((k_tiny<12, FAM>), g, b, lds, st, a);
+  else if (d <= 16) hipLaunchKernelGGL((k_tiny<16, FAM>), g, b, lds, st, a);
+  else hipLaunchKernelGGL((k_tiny<32, FAM>), g, b, lds, st, a);
+}
+template <int FAM>
+static void launch_snb_fam(int d, size_t lds, hipStream_t st, const SnbArgs& a) {
+  const dim3 g(1 + SNB_NH), b(256);
+  if (d <= 4) hipLaunchKernelGGL((k_snb<4, FAM>), g, b, lds, st, a);
+  else if (d <= 8) hipLaunchKernelGGL((k_snb<8, FAM>), g, b, lds, st, a);
+  else if (d <= 12) hipLaunchKernelGGL((k_snb<12, FAM>), g, b, lds, st, a);
+  else if (d <= 16) hipLaunchKernelGGL((k_snb<16, FAM>), g, b, lds, st, a);
+  else hipLaunchKernelGGL((k_snb<32, FAM>), g, b, lds, st, a);
+}
+// the dynamic LDS sizes of every width of one family's k_tiny and k_snb
+template <int FAM>
+static bool onel_lds_attr(int tiny_bytes, int snb_bytes) {
+  const auto at = hipFuncAttributeMaxDynamicSharedMemorySize;
+  return hipFuncSetAttribute((const void*)k_tiny<4, FAM>, at, tiny_bytes) == hipSuccess &&
+         hipFuncSetAttribute((const void*)k_tiny<8, FAM>, at, tiny_bytes) == hipSuccess &&
+         hipFuncSetAttribute((const void*)k_tiny<12, FAM>, at, tiny_bytes) == hipSuccess &&
+         hipFuncSetAttribute((const void*)k_tiny<16, FAM>, at, tiny_bytes) == hipSuccess &&
+         hipFuncSetAttribute((const void*)k_tiny<32, FAM>, at, tiny_bytes) == hipSuccess &&
+         hipFuncSetAttribute((const void*)k_snb<4, FAM>, at, snb_bytes) == hipSuccess &&
+         hipFuncSetAttribute((const void*)k_snb<8, FAM>, at, snb_bytes) == hipSuccess &&
+         hipFuncSetAttribute((const void*)k_snb<12, FAM>, at, snb_bytes) == hipSuccess &&
+         hipFuncSetAttribute((const void*)k_snb<16, FAM>, at, snb_bytes) == hipSuccess &&
+         hipFuncSetAttribute((const void*)k_snb<32, FAM>, at, snb_bytes) == hipSuccess;
+}
+
 // The correlation family a.fam selects the instantiation (FAM_GAUSS: the kernels as they
 // were before the Matern families).
 int launch_pairs(gpe_ctx* c, const PairArgs& a, int nblocks) {
@@ -2123,16 +2158,8 @@ gpe_ctx* gpe_create(int32_t device) {
          hipFuncSetAttribute((const void*)k_xasm, hipFuncAttributeMaxDynamicSharedMemorySize,
                              (int)(DB_LDS_DOUBLES * sizeof(double))) == hipSuccess;
     const int tl = (G_LDS_LAUNCH_DOUBLES + 2 * TILE * TINY_ZP) * (int)sizeof(double);
-    ok = ok && hipFuncSetAttribute((const void*)k_tiny<4>, hipFuncAttributeMaxDynamicSharedMemorySize, tl) == hipSuccess &&
-         hipFuncSetAttribute((const void*)k_tiny<8>, hipFuncAttributeMaxDynamicSharedMemorySize, tl) == hipSuccess &&
-         hipFuncSetAttribute((const void*)k_tiny<12>, hipFuncAttributeMaxDynamicSharedMemorySize, tl) == hipSuccess &&
-         hipFuncSetAttribute((const void*)k_tiny<16>, hipFuncAttributeMaxDynamicSharedMemorySize, tl) == hipSuccess &&
-         hipFuncSetAttribute((const void*)k_tiny<32>, hipFuncAttributeMaxDynamicSharedMemorySize, tl) == hipSuccess &&
-         hipFuncSetAttribute((const void*)k_snb<4>, hipFuncAttributeMaxDynamicSharedMemorySize, SNB_LDS_DOUBLES * 8) == hipSuccess &&
-         hipFuncSetAttribute((const void*)k_snb<8>, hipFuncAttributeMaxDynamicSharedMemorySize, SNB_LDS_DOUBLES * 8) == hipSuccess &&
-         hipFuncSetAttribute((const void*)k_snb<12>, hipFuncAttributeMaxDynamicSharedMemorySize, SNB_LDS_DOUBLES * 8) == hipSuccess &&
-         hipFuncSetAttribute((const void*)k_snb<16>, hipFuncAttributeMaxDynamicSharedMemorySize, SNB_LDS_DOUBLES * 8) == hipSuccess &&
-         hipFuncSetAttribute((const void*)k_snb<32>, hipFuncAttributeMaxDynamicSharedMemorySize, SNB_LDS_DOUBLES * 8) == hipSuccess;
+    ok = ok && onel_lds_attr<FAM_GAUSS>(tl, SNB_LDS_DOUBLES * 8) && onel_lds_attr<FAM_MATERN32>(tl, SNB_LDS_DOUBLES * 8) &&
+         onel_lds_attr<FAM_MATERN52>(tl, SNB_LDS_DOUBLES * 8);
     if (!ok) c->err = "hipFuncSetAttribute(max dynamic LDS) failed";
   }
   if (!ok) {
@@ -2313,7 +2340,7 @@ int tiny_objective(gpe_ctx* c, bool gp4ml, int kernel, const double* hp, int n_h
   ev_rec(c, 0);
   a.X = c->dX; a.F = c->dF;
   a.r = (c->has_r && rscale != 0.0) ? c->dr : nullptr;
-  a.rdiag = (gp4ml && kernel == GPE_KERNEL_STD && c->has_r) ? c->dr : nullptr;
+  a.rdiag = (gp4ml && !kernel_alt(kernel) && c->has_r) ? c->dr : nullptr;
   a.xw = c->dXw; a.L = c->tr.A; a.Xo = c->tr.B; a.Z = c->dZ; a.small = c->hpin; a.abort_flag = c->dinfo + 1 + TINY_SYNC_INTS;
   a.K = c->tr.A; a.Xp = c->dtiny; a.Wg = c->dtiny + 36 * DB_BS; a.sync = c->dinfo + 1;
   a.n = (int)c->n; a.d = d; a.P = P; a.want_grad = want_grad ? 1 : 0; a.mucm = gp4ml ? 0 : 1;
@@ -2323,14 +2350,15 @@ int tiny_objective(gpe_ctx* c, bool gp4ml, int kernel, const double* hp, int n_h
   a.dbg_skip = c->dbg_skip_wait;
   a.tag = ++c->onel_tag;
   kernel_consts(kernel, nu, true, &a.coff, &a.cdiag);
+  // (the Matern families' pivot floor, as factor_and_invert's k_pivot_floor)
+  a.floor_rel = 4.0 * (double)c->n_pad * std::numeric_limits<double>::epsilon();
   const size_t lds = (G_LDS_LAUNCH_DOUBLES + 2 * TILE * TINY_ZP) * sizeof(double);
   c->hpin[P * P + 1] = -2.0;   // (workgroup 0 overwrites it on every path; -2: it did not)
   c->tiny_dirty = true;   // (until this call has ended cleanly: its sync words are then consistent)
-  if (d <= 4) hipLaunchKernelGGL(k_tiny<4>, dim3(1 + TINY_NH), dim3(256), lds, c->stream, a);
-  else if (d <= 8) hipLaunchKernelGGL(k_tiny<8>, dim3(1 + TINY_NH), dim3(256), lds, c->stream, a);
-  else if (d <= 12) hipLaunchKernelGGL(k_tiny<12>, dim3(1 + TINY_NH), dim3(256), lds, c->stream, a);
-  else if (d <= 16) hipLaunchKernelGGL(k_tiny<16>, dim3(1 + TINY_NH), dim3(256), lds, c->stream, a);
-  else hipLaunchKernelGGL(k_tiny<32>, dim3(1 + TINY_NH), dim3(256), lds, c->stream, a);
+  const int fam = kernel_fam(kernel);
+  if (fam == FAM_MATERN32) launch_tiny_fam<FAM_MATERN32>(d, lds, c->stream, a);
+  else if (fam == FAM_MATERN52) launch_tiny_fam<FAM_MATERN52>(d, lds, c->stream, a);
+  else launch_tiny_fam<FAM_GAUSS>(d, lds, c->stream, a);
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipStreamSynchronize(c->stream));   // (the kernel wrote its outputs to hpin)
   const int info = (int)c->hpin[P * P + 1];
@@ -2383,7 +2411,7 @@ int tiny_objective(gpe_ctx* c, bool gp4ml, int kernel, const double* hp, int n_h
       for (int h = 0; h < TINY_NH; ++h) v += part[h * 64 + k];
       red[k] = v;
     }
-    small_grad(red, d, kernel == GPE_KERNEL_ALT_NUG, nu, fitnug, gp4ml, gscale, s2, a.coff, a.cdiag, n_hp,
+    small_grad(red, d, kernel_alt(kernel), nu, fitnug, gp4ml, gscale, s2, a.coff, a.cdiag, n_hp,
                grad_out, a.rdiag != nullptr);
   }
   if (c->prof) {   // (one phase: the whole evaluation)
@@ -2432,7 +2460,7 @@ int snb_objective(gpe_ctx* c, bool gp4ml, int kernel, const double* hp, int n_hp
   ev_rec(c, 0);
   a.X = c->dX; a.F = c->dF;
   a.r = (c->has_r && rscale != 0.0) ? c->dr : nullptr;
-  a.rdiag = (gp4ml && kernel == GPE_KERNEL_STD && c->has_r) ? c->dr : nullptr;
+  a.rdiag = (gp4ml && !kernel_alt(kernel) && c->has_r) ? c->dr : nullptr;
   a.xw = c->dXw; a.A = c->tr.A; a.Lb = c->tr.B; a.Xt = c->dsnb;
   a.Zt = a.Xt + np * np; a.Zo = a.Zt + 32 * np; a.Wg = a.Zo + 32 * np; a.T2g = a.Wg + 32 * np;
   a.Xscr = a.T2g + TINY_DM * TINY_ZP;
@@ -2444,15 +2472,15 @@ int snb_objective(gpe_ctx* c, bool gp4ml, int kernel, const double* hp, int n_hp
   a.dbg_skip = c->dbg_skip_wait;
   a.tag = ++c->onel_tag;
   kernel_consts(kernel, nu, true, &a.coff, &a.cdiag);
+  // (the Matern families' pivot floor, as factor_and_invert's k_pivot_floor)
+  a.floor_rel = 4.0 * (double)c->n_pad * std::numeric_limits<double>::epsilon();
   const size_t lds = SNB_LDS_DOUBLES * sizeof(double);
   c->hpin[P * P + NB] = -2.0;   // (workgroup 0 overwrites it on every path; -2: it did not)
   c->snb_dirty = true;   // (until this call has ended cleanly)
-  const dim3 grid(1 + SNB_NH);
-  if (d <= 4) hipLaunchKernelGGL(k_snb<4>, grid, dim3(256), lds, c->stream, a);
-  else if (d <= 8) hipLaunchKernelGGL(k_snb<8>, grid, dim3(256), lds, c->stream, a);
-  else if (d <= 12) hipLaunchKernelGGL(k_snb<12>, grid, dim3(256), lds, c->stream, a);
-  else if (d <= 16) hipLaunchKernelGGL(k_snb<16>, grid, dim3(256), lds, c->stream, a);
-  else hipLaunchKernelGGL(k_snb<32>, grid, dim3(256), lds, c->stream, a);
+  const int fam = kernel_fam(kernel);
+  if (fam == FAM_MATERN32) launch_snb_fam<FAM_MATERN32>(d, lds, c->stream, a);
+  else if (fam == FAM_MATERN52) launch_snb_fam<FAM_MATERN52>(d, lds, c->stream, a);
+  else launch_snb_fam<FAM_GAUSS>(d, lds, c->stream, a);
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipStreamSynchronize(c->stream));   // (the kernel wrote its outputs to hpin)
   const double* h = c->hpin;
@@ -2502,7 +2530,7 @@ int snb_objective(gpe_ctx* c, bool gp4ml, int kernel, const double* hp, int n_hp
       for (int g = 0; g < SNB_NH; ++g) v += part[g * 64 + k];
       red[k] = v;
     }
-    small_grad(red, d, kernel == GPE_KERNEL_ALT_NUG, nu, fitnug, gp4ml, gscale, s2, a.coff, a.cdiag, n_hp,
+    small_grad(red, d, kernel_alt(kernel), nu, fitnug, gp4ml, gscale, s2, a.coff, a.cdiag, n_hp,
                grad_out, a.rdiag != nullptr);
   }
   if (c->prof) {
@@ -2548,9 +2576,7 @@ int gpe_objective(gpe_ctx* c, int32_t variant, int32_t kernel, const double* hp,
     c->oev_used = 0;
     c->oz_ms = c->oz_launches = c->oz_ops = c->oz_flops64 = 0.0;
   }
-  // (the one-launch paths are Gaussian only: a Matern objective takes the general path at
-  // every n, as GPEMU_TINY=0 does)
-  const bool one_launch = c->tiny && kernel_fam(kernel) == FAM_GAUSS;
+  const bool one_launch = c->tiny;
   if (one_launch && c->NB == 1 && d <= TINY_DM && q + 1 <= TINY_DM)
     return tiny_objective(c, gp4ml, kernel, hp, n_hp, fitnug, nu, s2, rscale, want_grad != 0, llh_out, grad_out,
                           sigma2_out);

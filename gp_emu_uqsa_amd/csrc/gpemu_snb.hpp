@@ -18,6 +18,11 @@
 // Hand-offs as k_tiny's (sc1 stores and loads, a barrier and one lane's counter add or
 // flag store): a helper counter hc (each helper workgroup adds 1 per finished phase) and a
 // main flag mf; both count up over a context's calls (bases in the arguments).
+// Correlation family: the template argument FAM, as k_tiny's.  The K-build writes pre * rho(s)
+// and the contraction recomputes rho and g from the staged points (matern_rho_g, as
+// k_contract<., ., FAM>); with a Matern family workgroup 0 holds each diagonal tile's pivots
+// against the pivot floor (tiny_pivot_floor) before it publishes X(k,k).  Phases, counters and
+// sizes do not depend on it, and FAM_GAUSS is the code as it was.
 // X and X^T (Xt) are both kept so every operand load has its 16 lanes on consecutive rows.
 // Limits: 128 < n <= 512, d <= 32, q + 1 <= 32.
 #pragma once
@@ -70,6 +75,7 @@ struct SnbArgs {
   int hcb, mfb;         // the counters' values before this call (hc in phases)
   double s2, coff, cdiag, rscale;
   double invd[32];
+  double floor_rel;     // the Matern pivot floor's 4 n_pad eps (tiny_pivot_floor); Gaussian: not read
 };
 
 // acc += sum over k in [k0, k1) of A(m16, k) B(k, m16) (this lane's operands from fa / fb),
@@ -96,7 +102,7 @@ __device__ __forceinline__ tiny_d4 snb_mma(tiny_d4 acc, int k0, int k1, FA fa, F
   return acc;
 }
 
-template <int DM>
+template <int DM, int FAM>
 __device__ void snb_helper(const SnbArgs& a, double* lds) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int m16 = lane & 15, k4 = lane >> 4;
@@ -158,7 +164,14 @@ __device__ void snb_helper(const SnbArgs& a, double* lds) {
           const double df = xi[k] - xj[r][k];
           s = fma(df, df, s);
         }
-        double v = pre * exp(-s);
+        double v;
+        if constexpr (FAM == FAM_GAUSS) {
+          v = pre * exp(-s);
+        } else {
+          double rho, g;
+          matern_rho_g<FAM>(s, rho, g);
+          v = pre * rho;
+        }
         const bool pad = i >= n || j >= n;
         const bool diag = i == j;
         double vd = a.s2 * a.cdiag;
@@ -372,10 +385,19 @@ __device__ void snb_helper(const SnbArgs& a, double* lds) {
         }
         sm.t += dg ? m : 0.0;
         sm.r += (dg && ok && a.rdiag) ? m * a.rdiag[i] : 0.0;
-        const double me = dg ? 0.0 : m * exp(-s);
-        sm.e += me;
+        if constexpr (FAM == FAM_GAUSS) {
+          const double me = dg ? 0.0 : m * exp(-s);
+          sm.e += me;
 #pragma unroll
-        for (int k = 0; k < DM; ++k) sm.acc[k] = fma(me, df2[k], sm.acc[k]);
+          for (int k = 0; k < DM; ++k) sm.acc[k] = fma(me, df2[k], sm.acc[k]);
+        } else {   // (rho and g recomputed, as k_contract<., ., FAM>)
+          double rho, g;
+          matern_rho_g<FAM>(s, rho, g);
+          sm.e += dg ? 0.0 : m * rho;
+          const double mg = dg ? 0.0 : m * g;
+#pragma unroll
+          for (int k = 0; k < DM; ++k) sm.acc[k] = fma(mg, df2[k], sm.acc[k]);
+        }
       }
     }
   }
@@ -388,11 +410,11 @@ __device__ void snb_helper(const SnbArgs& a, double* lds) {
   if (tid == 0) a.small[P * P + NB + 1 + d + 4 + h * 64 + 63] = a.tag;
 }
 
-template <int DM>
+template <int DM, int FAM = FAM_GAUSS>
 static __global__ void __launch_bounds__(256) k_snb(SnbArgs a) {
   extern __shared__ __attribute__((aligned(16))) double lds[];
   if (blockIdx.x > 0) {
-    snb_helper<DM>(a, lds);
+    snb_helper<DM, FAM>(a, lds);
     return;
   }
   constexpr int ZP = TINY_ZP;
@@ -431,7 +453,10 @@ static __global__ void __launch_bounds__(256) k_snb(SnbArgs a) {
     }
     __syncthreads();
     SNB_T(4 * k + 1);
-    const int bad = db_factor_invert(lb, a.Lb + c0 + c0 * np, np, a.Xscr, TILE, a.small + P * P + k, [] {}, true);
+    int bad = db_factor_invert(lb, a.Lb + c0 + c0 * np, np, a.Xscr, TILE, a.small + P * P + k, [] {}, true);
+    // (a Matern family: the pivot floor on this tile's columns; the tiles before it passed)
+    if constexpr (FAM != FAM_GAUSS)
+      bad = tiny_pivot_floor(lb, bad, n - (int)c0, a.floor_rel, a.s2 * a.cdiag, a.r ? a.r + c0 : nullptr, a.rscale);
     if (bad) {
       if (tid == 0) {
         a.small[P * P + NB] = (double)(c0 + bad);

@@ -21,6 +21,13 @@
 // k_pairs' to the bit: same scaled coordinates, same fma order, same selects); products and
 // sums run in other orders than the general path's GEMMs and k_contract, so results agree to
 // rounding.
+// Correlation family: a template argument FAM (FAM_* of gpemu_kernels.hpp) beside DM.  It is
+// read in two places of a helper only: the K-build's off-diagonal entry pre * rho(s) and the
+// contraction (<M, E> with rho, <M, E (.) D_k> with g; both kept in registers from the
+// K-build, one sqrt and one exp per entry in matern_rho_g).  A Matern family also holds every
+// pivot against the floor of k_pivot_floor (tiny_pivot_floor, workgroup 0, after the
+// factorisation and before anything is published).  Waits, flags, counters, grid and LDS
+// sizes do not depend on it, and FAM_GAUSS is the code as it was.
 // Global -> LDS staging issues every load of a thread before its first LDS store (a load /
 // store pair per loop iteration put one memory latency per iteration in sequence).
 // Limits: n <= 128, d <= 32, q + 1 <= 32 (the host takes the general path otherwise).
@@ -71,6 +78,7 @@ struct TinyArgs {
   double tag;           // this call's tag (never repeats in a context) for the helpers' sums
   double s2, coff, cdiag, rscale;
   double invd[32];
+  double floor_rel;     // the Matern pivot floor's 4 n_pad eps (tiny_pivot_floor); Gaussian: not read
 };
 
 constexpr int TINY_NH = 9;
@@ -231,13 +239,41 @@ __device__ __forceinline__ tiny_d4 tiny_mfma(double a, double b, tiny_d4 c) {
   return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
 }
 
+// The Matern pivot floor (k_pivot_floor) inside a one-launch kernel, by
+// workgroup 0 after db_factor_invert of a diagonal tile returned bad (0, or the 1-based
+// column at which it stopped).  Pivot j = L(j,j)^2 is held against floor_rel * A(j,j),
+// A(j,j) = dconst + rcoef r_j: at or below it, or NaN, column j + 1 is refused.  L(j,j)
+// is taken as 1 / X(j,j) from the leaves' xdiag (the image's own diagonal holds X by
+// now), for the nv valid columns of the leaves that finished -- the columns whose L the
+// general path's sweep has stored when k_pivot_floor reads them.  Returns the lowest
+// refused column (1-based; it lies before bad) or else bad, the same in every thread.
+__device__ __forceinline__ int tiny_pivot_floor(double* lb, int bad, int nv, double floor_rel, double dconst,
+                                                const double* r, double rcoef) {
+  const int tid = threadIdx.x;
+  const double* xdiag = lb + DB_LDS_DOUBLES;
+  int* first = reinterpret_cast<int*>(lb + DB_LDS_DOUBLES + 128);   // (db_factor_invert's reduction slots, free again)
+  const int done = bad ? ((bad - 1) & ~15) : TILE;
+  bool low = false;
+  if (tid < min(done, nv)) {
+    const double l = 1.0 / xdiag[tid];
+    const double ajj = dconst + (r ? rcoef * r[tid] : 0.0);
+    low = !(l * l > floor_rel * ajj);
+  }
+  const unsigned long long m = __ballot(low);
+  if ((tid & 63) == 0 && tid < TILE) first[tid >> 6] = m ? tid + __ffsll((long long)m) : 0;
+  __syncthreads();
+  const int f = first[0] ? first[0] : first[1];
+  return f ? f : bad;
+}
+
 // A helper workgroup (blockIdx 1 .. TINY_NH): wave w of helper h owns lower block b = 4h + w
 // = (bi, bj) of the 16 x 16 grid.  First its 256 entries of the K-build (k_pairs' training
 // mode, in the MFMA accumulator layout: lane -> rows 16 bi + lane / 16 + 4 r, column
-// 16 bj + lane % 16), written to K and their exp(-s) kept; then, once workgroup 0 has
-// published W, M(bi, bj) = X^T X - W W^T (MFMA, X and W from L2) contracted into the d + 3
-// sums; each helper's partial sums go to the host.
-template <int DM>
+// 16 bj + lane % 16), written to K and their rho(s) kept (exp(-s); a Matern family FAM: rho
+// and g of matern_rho_g, as k_pairs<., FAM> and k_contract<., ., FAM>); then, once workgroup 0
+// has published W, M(bi, bj) = X^T X - W W^T (MFMA, X and W from L2) contracted into the d + 3
+// sums (<M, E> with rho, <M, E (.) D_k> with g); each helper's partial sums go to the host.
+template <int DM, int FAM>
 __device__ void tiny_helper(const TinyArgs& a, double* lds) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h = blockIdx.x - 1;
   const int m16 = lane & 15, k4 = lane >> 4;
@@ -256,7 +292,8 @@ __device__ void tiny_helper(const TinyArgs& a, double* lds) {
   for (int r = 0; r < 4; ++r)
 #pragma unroll
     for (int k = 0; k < DM; ++k) xi[r][k] = coord(16 * bi + k4 + 4 * r, k);
-  double ex[4];
+  double ex[4];                             // rho(s) of the wave's entries
+  double gx[FAM == FAM_GAUSS ? 1 : 4];      // g(s) (Gaussian: g = rho, not kept twice)
   {
     const double pre = a.s2 * a.coff;
 #pragma unroll
@@ -268,7 +305,8 @@ __device__ void tiny_helper(const TinyArgs& a, double* lds) {
         const double df = xi[r][k] - xj[k];
         s = fma(df, df, s);
       }
-      ex[r] = exp(-s);
+      if constexpr (FAM == FAM_GAUSS) ex[r] = exp(-s);
+      else matern_rho_g<FAM>(s, ex[r], gx[r]);
       double v = pre * ex[r];
       const bool pad = i >= n || j >= n;
       const bool diag = i == j;
@@ -338,8 +376,14 @@ __device__ void tiny_helper(const TinyArgs& a, double* lds) {
     sm.r += (dg && ok && a.rdiag) ? m * a.rdiag[i] : 0.0;
     const double me = dg ? 0.0 : m * ex[r];
     sm.e += me;
+    if constexpr (FAM == FAM_GAUSS) {
 #pragma unroll
-    for (int k = 0; k < DM; ++k) sm.acc[k] = fma(me, df2[k], sm.acc[k]);
+      for (int k = 0; k < DM; ++k) sm.acc[k] = fma(me, df2[k], sm.acc[k]);
+    } else {
+      const double mg = dg ? 0.0 : m * gx[r];
+#pragma unroll
+      for (int k = 0; k < DM; ++k) sm.acc[k] = fma(mg, df2[k], sm.acc[k]);
+    }
   }
   double* red = lds + 8;   // (past st)
   sm.reduce(d, red, red + 4 * (DM + 3));
@@ -352,11 +396,11 @@ __device__ void tiny_helper(const TinyArgs& a, double* lds) {
 #endif
 }
 
-template <int DM>
+template <int DM, int FAM = FAM_GAUSS>
 static __global__ void __launch_bounds__(256) k_tiny(TinyArgs a) {
   extern __shared__ __attribute__((aligned(16))) double lds[];
   if (blockIdx.x > 0) {
-    tiny_helper<DM>(a, lds);
+    tiny_helper<DM, FAM>(a, lds);
     return;
   }
   constexpr int ZP = TINY_ZP;
@@ -395,7 +439,8 @@ static __global__ void __launch_bounds__(256) k_tiny(TinyArgs a) {
                                    [&](int e, double v) { if (e < 36 * DB_BS) lb[e] = v; });
   __syncthreads();
   TINY_T(2);
-  const int bad = db_factor_invert(lb, a.L, TILE, a.Xo, TILE, a.small + P * P, [] {}, true);
+  int bad = db_factor_invert(lb, a.L, TILE, a.Xo, TILE, a.small + P * P, [] {}, true);
+  if constexpr (FAM != FAM_GAUSS) bad = tiny_pivot_floor(lb, bad, n, a.floor_rel, a.s2 * a.cdiag, a.r, a.rscale);
   if (bad) {
     if (tid == 0) {
       a.small[P * P + 1] = (double)bad;

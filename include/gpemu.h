@@ -60,8 +60,9 @@ enum gpe_status {
  * the nugget and sigma derivatives are those of the Gaussian kernels with exp(-s) read as
  * rho.  Accepted by gpe_objective, gpe_factor (and through the resident factor by gpe_beta,
  * gpe_loo, gpe_solve, gpe_posterior, gpe_noise_sample, gpe_posterior_pivchol),
- * gpe_kernel_var, gpe_kernel_covar and gpe_kernel_grad_k.  A Matern objective always takes
- * the general (multi-launch) path.  gpe_dist_objective answers GPE_ERR_UNSUPPORTED to a
+ * gpe_kernel_var, gpe_kernel_covar and gpe_kernel_grad_k.  A Matern objective takes
+ * the one-launch paths at n <= 512 as a Gaussian one does (same limits, same pivot floor as
+ * on the general path).  gpe_dist_objective answers GPE_ERR_UNSUPPORTED to a
  * Matern code; gpe_sense_pairs / gpe_gauss_transform are Gaussian closed forms.  Any other
  * bit, or both family bits, is GPE_ERR_ARG.
  * GPE_NOT_PD for a Matern code: besides a non-positive or NaN pivot, a pivot at or below
