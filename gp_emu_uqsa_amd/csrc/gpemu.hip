@@ -4245,6 +4245,147 @@ int gpe_test_oz_product(gpe_ctx* c, const gpe_oz_operand* a, const gpe_oz_operan
   return rc;
 }
 
+// ---- gpe_test_gemm_group: one k_gemm launch on a group of problems, on buffers of its own
+struct GemmGroupBufs {   // (freed, and the context's descriptor / list arrays put back, on every way out)
+  gpe_ctx* c;
+  GemmProb* ctx_probs;
+  unsigned* ctx_tiles;
+  bool prof;
+  std::vector<double*> dev, keep;   // the buffers, and the inputs of those that hold a C
+  GemmProb* probs = nullptr;
+  unsigned* tiles = nullptr;
+  double* part = nullptr;
+  int* tcnt = nullptr;
+  explicit GemmGroupBufs(gpe_ctx* ctx) : c(ctx), ctx_probs(ctx->dprobs), ctx_tiles(ctx->dtiles), prof(ctx->prof) {}
+  ~GemmGroupBufs() {
+    c->dprobs = ctx_probs;
+    c->dtiles = ctx_tiles;
+    c->prof = prof;
+    for (double* p : dev) if (p) (void)hipFree(p);
+    for (double* p : keep) if (p) (void)hipFree(p);
+    for (void* p : {(void*)probs, (void*)tiles, (void*)part, (void*)tcnt}) if (p) (void)hipFree(p);
+  }
+};
+
+static int gemm_group_test(gpe_ctx* c, int nbuf, double* const* bufs, const int64_t* lens, int nprob,
+                           const gpe_gemm_group_prob* gp, const gpe_gemm_group_launch& gl, int32_t* ksplit_out,
+                           int32_t* info_out, uint32_t* tiles_out, int64_t tiles_cap) {
+  const auto bad = [&](const std::string& what) { return fail(c, GPE_ERR_ARG, "gpe_test_gemm_group: " + what); };
+  if (nbuf < 1 || nbuf > 64 || nprob < 1 || nprob > 1024) return bad("1 to 64 buffers, 1 to 1024 problems");
+  for (int i = 0; i < nbuf; ++i)
+    if (!bufs[i] || lens[i] < 1) return bad("NULL or empty buffer " + std::to_string(i));
+  if (gl.kind < 0 || gl.kind > 3 || (gl.split & ~1) || (gl.listed & ~1) || gl.reps < 1 || gl.reps > 16)
+    return bad("kind 0..3, split 0 / 1, listed 0 / 1, reps 1..16");
+  if (gl.listed && nprob >= 256) return bad("a tile list names at most 255 problems");
+  if (tiles_cap < 0 || (tiles_cap > 0 && !tiles_out)) return bad("tiles_out is NULL");
+  const bool AK = gl.kind == 1 || gl.kind == 2, BK = gl.kind == 2 || gl.kind == 3;
+  long long total = 0;
+  std::vector<char> holds_c(nbuf, 0);
+  for (int p = 0; p < nprob; ++p) {
+    const gpe_gemm_group_prob& g = gp[p];
+    const std::string who = "problem " + std::to_string(p) + ": ";
+    if (g.flags & ~(G_CLOWER | G_KBEG_TI | G_KEND_TI)) return bad(who + "only G_CLOWER, G_KBEG_TI, G_KEND_TI (no fused flag)");
+    if (g.K < GK || g.K % GK || g.K > (1 << 24)) return bad(who + "K is not a positive multiple of 16");
+    if (!(g.alpha != 0.0) || !std::isfinite(g.alpha) || std::isnan(g.beta)) return bad(who + "alpha is 0 or not finite (beta / alpha)");
+    if (g.mt < 1 || g.mt > 4096 || g.nt < 1 || g.nt > 4096) return bad(who + "mt, nt outside [1, 4096]");
+    if (g.kti_mul < 0 || g.kti_off < 0 || g.kti_mul > 4096 || g.kti_off > 4096) return bad(who + "kti_mul, kti_off outside [0, 4096]");
+    if (g.a_buf < 0 || g.a_buf >= nbuf || g.b_buf < 0 || g.b_buf >= nbuf || g.c_buf < 0 || g.c_buf >= nbuf)
+      return bad(who + "buffer index");
+    if (g.a_off < 0 || g.b_off < 0 || g.c_off < 0 || ((g.a_off | g.b_off | g.c_off) & 1)) return bad(who + "odd or negative offset");
+    if (g.lda < 2 || g.ldb < 2 || g.ldc < 2 || ((g.lda | g.ldb | g.ldc) & 1)) return bad(who + "odd leading dimension");
+    if (g.ldc > (1ll << 21)) return bad(who + "ldc > 2^21");
+    if (std::max({g.lda, g.ldb}) > (1ll << 40)) return bad(who + "leading dimension");
+    total += (g.flags & G_CLOWER) ? (long long)g.mt * (g.mt + 1) / 2 : (long long)g.mt * g.nt;
+    if (total > 65536) return bad("more than 65536 tiles");
+    holds_c[g.c_buf] = 1;
+    // every tile's windows: the operand panels over its own K range, its C tile
+    const long long la = lens[g.a_buf], lb = lens[g.b_buf], lc = lens[g.c_buf];
+    for (int ti = 0; ti < g.mt; ++ti) {
+      const long long kb = (g.flags & G_KBEG_TI) ? (long long)ti * TILE : 0;
+      const long long ke = (g.flags & G_KEND_TI) ? std::min<long long>(g.K, ((long long)ti * g.kti_mul + g.kti_off + 1) * TILE) : g.K;
+      const long long r1 = (long long)ti * TILE + TILE - 1;
+      if (ke > kb && g.a_off + (AK ? r1 * g.lda + ke - 1 : (ke - 1) * g.lda + r1) >= la)
+        return bad(who + "A leaves its buffer at tile row " + std::to_string(ti));
+      const int tjn = (g.flags & G_CLOWER) ? ti + 1 : g.nt;   // (G_CLOWER: tj <= ti, whatever nt)
+      const long long c1 = (long long)(tjn - 1) * TILE + TILE - 1;
+      if (ke > kb && g.b_off + (BK ? c1 * g.ldb + ke - 1 : (ke - 1) * g.ldb + c1) >= lb)
+        return bad(who + "B leaves its buffer at tile row " + std::to_string(ti));
+      if (g.c_off + r1 + c1 * g.ldc >= lc) return bad(who + "C leaves its buffer at tile row " + std::to_string(ti));
+    }
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  GemmGroupBufs d(c);
+  c->prof = false;   // (not a launch of the objective: kept out of gpe_gemm_stats)
+  d.dev.assign(nbuf, nullptr);
+  d.keep.assign(nbuf, nullptr);
+  for (int i = 0; i < nbuf; ++i) {
+    CHK(dalloc(c, &d.dev[i], (size_t)lens[i]));
+    HIPCHK(c, hipMemcpy(d.dev[i], bufs[i], (size_t)lens[i] * sizeof(double), hipMemcpyHostToDevice));
+    if (holds_c[i] && gl.reps > 1) {
+      CHK(dalloc(c, &d.keep[i], (size_t)lens[i]));
+      HIPCHK(c, hipMemcpy(d.keep[i], d.dev[i], (size_t)lens[i] * sizeof(double), hipMemcpyDeviceToDevice));
+    }
+  }
+  std::vector<GemmProb> probs;
+  for (int p = 0; p < nprob; ++p) {
+    const gpe_gemm_group_prob& g = gp[p];
+    GemmProb q = mkprob(d.dev[g.a_buf] + g.a_off, g.lda, d.dev[g.b_buf] + g.b_off, g.ldb, d.dev[g.c_buf] + g.c_off, g.ldc,
+                        g.mt, g.nt, g.K, g.flags, g.alpha, g.beta);
+    q.kti_mul = g.kti_mul;
+    q.kti_off = g.kti_off;
+    probs.push_back(q);
+  }
+  if (gl.split) {
+    // the partials start as NaN: a slot the sum reads but no share wrote shows in C
+    CHK(dalloc(c, &d.part, (size_t)SPLIT_SLOTS * TILE * TILE));
+    CHK(dalloc(c, &d.tcnt, (size_t)SPLIT_SLOTS));
+    HIPCHK(c, hipMemset(d.part, 0xff, (size_t)SPLIT_SLOTS * TILE * TILE * sizeof(double)));
+    HIPCHK(c, hipMemset(d.tcnt, 0, (size_t)SPLIT_SLOTS * sizeof(int)));
+    split_k(probs, d.part, d.tcnt);
+  }
+  Plan pl;
+  add_launch(pl, gl.kind, probs, 0.0);
+  Launch L = pl.launches[0];
+  if (!gl.listed) L.list = -1;
+  if (L.list >= 0 && (long long)pl.tiles.size() > tiles_cap) return bad("the tile list does not fit tiles_cap");
+  CHK(dalloc(c, &d.probs, pl.probs.size()));
+  HIPCHK(c, hipMemcpy(d.probs, pl.probs.data(), pl.probs.size() * sizeof(GemmProb), hipMemcpyHostToDevice));
+  if (L.list >= 0) {
+    CHK(dalloc(c, &d.tiles, pl.tiles.size()));
+    HIPCHK(c, hipMemcpy(d.tiles, pl.tiles.data(), pl.tiles.size() * sizeof(unsigned), hipMemcpyHostToDevice));
+  }
+  // launch_gemm_range reads the context's descriptor and list arrays: the hook's stand in
+  // for them until it returns (GemmGroupBufs puts the context's back)
+  c->dprobs = d.probs;
+  c->dtiles = d.tiles;
+  HIPCHK(c, hipMemsetAsync(c->dinfo, 0, sizeof(int), c->stream));
+  for (int r = 0; r < gl.reps; ++r) {
+    if (r > 0)
+      for (int i = 0; i < nbuf; ++i)
+        if (d.keep[i])
+          HIPCHK(c, hipMemcpyAsync(d.dev[i], d.keep[i], (size_t)lens[i] * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    CHK(launch_gemm_range(c, L));
+  }
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  for (int i = 0; i < nbuf; ++i)
+    HIPCHK(c, hipMemcpy(bufs[i], d.dev[i], (size_t)lens[i] * sizeof(double), hipMemcpyDeviceToHost));
+  for (int p = 0; p < nprob; ++p) ksplit_out[p] = pl.probs[p].ksplit;
+  info_out[0] = L.list >= 0;
+  info_out[1] = L.cdef;
+  info_out[2] = L.tiles;
+  if (L.list >= 0) std::copy(pl.tiles.begin(), pl.tiles.end(), tiles_out);
+  return GPE_OK;
+}
+
+int gpe_test_gemm_group(gpe_ctx* c, int32_t nbuf, double* const* bufs, const int64_t* lens, int32_t nprob,
+                        const gpe_gemm_group_prob* probs, const gpe_gemm_group_launch* launch, int32_t* ksplit_out,
+                        int32_t* info_out, uint32_t* tiles_out, int64_t tiles_cap) {
+  if (!c) return GPE_ERR_ARG;
+  if (!bufs || !lens || !probs || !launch || !ksplit_out || !info_out)
+    return fail(c, GPE_ERR_ARG, "gpe_test_gemm_group: NULL argument");
+  return gemm_group_test(c, nbuf, bufs, lens, nprob, probs, *launch, ksplit_out, info_out, tiles_out, tiles_cap);
+}
+
 int gpe_bench_gemm(gpe_ctx* c, int32_t trans_a, int32_t trans_b, int32_t mt, int32_t nt, int32_t K,
                    int32_t lower, double beta, int32_t reps, double* ms_out) {
   if (!c || !ms_out || mt <= 0 || nt <= 0 || K <= 0 || K % GK || reps <= 0) return GPE_ERR_ARG;

@@ -1034,6 +1034,24 @@ __device__ __forceinline__ void panel_subst(const PanelAddr& pa, const double* L
 // position was claimed by a workgroup that is already running, so the earliest unfinished
 // tile can always make progress whatever order the hardware dispatches the workgroups in
 // and whatever else occupies the CUs (other streams, other contexts' launches).
+// What every problem of a launch must satisfy (nothing here checks it; the test hook
+// gpe_test_gemm_group refuses what it can see):
+// - K a multiple of GK = 16: the K loop runs (kend - kbeg) / GK whole stages and would drop a
+//   remainder silently; the range flags keep kbeg and kend on multiples of 128.
+// - alpha != 0: C enters the accumulators as (beta / alpha) C and alpha scales the store.
+// - lda, ldb, ldc even, and A, B, C 16-byte aligned: stage loads, the C preload, the chunk
+//   loads and the epilogue move aligned pairs of doubles.
+// - every tile's operand panels over its own K range [kbeg, kend) and its 128 x 128 C tile lie
+//   inside their allocations: no load or store is predicated.  Outside that range nothing is
+//   read (no stage is prefetched past the last), and with beta == 0 the plain instances do
+//   not read C at all; the CDEF instance loads the C chunks of every tile with >= 10 stages
+//   and discards them where beta == 0 (c_chunk_add).
+// - ldc <= 2^21 for the deferred C (32-bit buffer offsets); a problem over it preloads C.
+// - a tile list holds p < 256, ti, tj < 4096 (tile_unpack) and no split-K problem; without a
+//   list tile_begin is non-decreasing over the problems and covers [0, gridDim.x).
+// - split K (ksplit > 1): beta == 0, part holds ntiles partial tiles and tcnt one zeroed
+//   counter per tile; the last share to arrive leaves the counter at zero again.
+// - an empty K range (kend <= kbeg) is legal: C = beta C.
 template <bool AK, bool BK, bool FUSED = false, bool CDEF = false>
 static __global__ void __launch_bounds__(256, 2) k_gemm(const GemmProb* __restrict__ probs, int nprob,
                                                   const unsigned* __restrict__ tiles,

@@ -43,8 +43,27 @@ class OzParams(_ct.Structure):
                [("ldc", _ct.c_int64), ("c_len", _ct.c_int64), ("alpha", _ct.c_double)]
 
 
+class GemmGroupProb(_ct.Structure):
+    """gpe_gemm_group_prob (gpe_test_gemm_group)"""
+    _fields_ = [(n, _ct.c_int32) for n in ("a_buf", "b_buf", "c_buf", "mt", "nt", "K", "flags", "kti_mul",
+                                           "kti_off")] + \
+               [(n, _ct.c_int64) for n in ("a_off", "lda", "b_off", "ldb", "c_off", "ldc")] + \
+               [("alpha", _ct.c_double), ("beta", _ct.c_double)]
+
+
+class GemmGroupLaunch(_ct.Structure):
+    """gpe_gemm_group_launch (gpe_test_gemm_group)"""
+    _fields_ = [(n, _ct.c_int32) for n in ("kind", "split", "listed", "reps")]
+
+
+G_CLOWER, G_KBEG_TI, G_KEND_TI = 1, 2, 4   # gpe_gemm_group_prob.flags
+
 # name -> (restype, argtypes); the full exported surface of include/gpemu.h
 SIGNATURES = {
+    "gpe_test_gemm_group": (_ct.c_int, [_VP, _ct.c_int32, _ct.POINTER(_D), _ct.POINTER(_ct.c_int64), _ct.c_int32,
+                                        _ct.POINTER(GemmGroupProb), _ct.POINTER(GemmGroupLaunch),
+                                        _ct.POINTER(_ct.c_int32), _ct.POINTER(_ct.c_int32),
+                                        _ct.POINTER(_ct.c_uint32), _ct.c_int64]),
     "gpe_test_oz_product": (_ct.c_int, [_VP, _ct.POINTER(OzOperand), _ct.POINTER(OzOperand),
                                         _ct.POINTER(OzParams), _D, _ct.POINTER(_ct.c_int32),
                                         _ct.POINTER(_ct.c_int32), _ct.POINTER(_ct.c_int8)]),
@@ -548,6 +567,38 @@ class Context:
             exa.ctypes.data_as(i32), exb.ctypes.data_as(i32),
             None if res is None else res.ctypes.data_as(_ct.POINTER(_ct.c_int8))), "gpe_test_oz_product")
         return {"C": Cc, "exa": exa, "exb": exb, "res": res}
+
+    def test_gemm_group(self, bufs, probs, *, kind, split=False, listed=False, reps=1):
+        """One launch of the grouped fp64 GEMM on a group of problems through the production
+        routines (gpe_test_gemm_group, a test hook).  bufs: 1-d fp64 arrays, sent as they are
+        (copied here).  probs: dicts with a, b, c = (buffer index, element offset, leading
+        dimension), mt, nt, K and optionally flags, kti_mul, kti_off, alpha, beta.  Returns
+        dict(bufs, ksplit, listed, cdef, workgroups, tiles): the buffers afterwards, the split
+        each problem got, whether the launch had a tile list and ran the CDEF instance, its
+        workgroup count and the tile list (codes p << 24 | ti << 12 | tj; None without one)."""
+        out = [_np.array(b, dtype=_np.float64).ravel() for b in bufs]
+        ptrs = (_D * len(out))(*[_ptr(b) for b in out])
+        lens = (_ct.c_int64 * len(out))(*[b.size for b in out])
+        ps = (GemmGroupProb * max(len(probs), 1))()
+        cap = 0
+        for q, p in zip(ps, probs):
+            (q.a_buf, q.a_off, q.lda), (q.b_buf, q.b_off, q.ldb), (q.c_buf, q.c_off, q.ldc) = \
+                [tuple(int(v) for v in p[k]) for k in ("a", "b", "c")]
+            q.mt, q.nt, q.K, q.flags = int(p["mt"]), int(p["nt"]), int(p["K"]), int(p.get("flags", 0))
+            q.kti_mul, q.kti_off = int(p.get("kti_mul", 1)), int(p.get("kti_off", 0))
+            q.alpha, q.beta = float(p.get("alpha", 1.0)), float(p.get("beta", 0.0))
+            if 0 < q.mt <= 4096 and 0 < q.nt <= 4096:
+                cap += q.mt * (q.mt + 1) // 2 if q.flags & G_CLOWER else q.mt * q.nt
+        gl = GemmGroupLaunch(int(kind), int(split), int(listed), int(reps))
+        ksplit = _np.zeros(max(len(probs), 1), dtype=_np.int32)
+        info = _np.zeros(3, dtype=_np.int32)
+        tiles = _np.zeros(max(cap, 1), dtype=_np.uint32)
+        i32 = _ct.POINTER(_ct.c_int32)
+        self._check(self.lib.gpe_test_gemm_group(
+            self._h, len(out), ptrs, lens, len(probs), ps, _ct.byref(gl), ksplit.ctypes.data_as(i32),
+            info.ctypes.data_as(i32), tiles.ctypes.data_as(_ct.POINTER(_ct.c_uint32)), cap), "gpe_test_gemm_group")
+        return {"bufs": out, "ksplit": ksplit[:len(probs)], "listed": bool(info[0]), "cdef": bool(info[1]),
+                "workgroups": int(info[2]), "tiles": tiles[:cap].copy() if info[0] else None}
 
     def bench_gemm(self, mt, nt, K, trans_a=0, trans_b=0, lower=False, beta=1.0, reps=5):
         ms = _ct.c_double()

@@ -36,8 +36,9 @@ extern "C" {
                                 gpe_device_synchronize, gpe_build_id;
                                 9: gpe_dist_local_rows takes the basis width q;
                                 10: gpe_ozaki_stats (gpe_loo, gpe_posterior_pivchol,
-                                gpe_posterior_grad and the test hook gpe_test_oz_product were
-                                added within 10: additions, nothing existing changed) */
+                                gpe_posterior_grad and the test hooks gpe_test_oz_product and
+                                gpe_test_gemm_group were added within 10: additions, nothing
+                                existing changed) */
 
 enum gpe_status {
     GPE_OK = 0,
@@ -320,6 +321,61 @@ typedef struct gpe_oz_params {
 int gpe_test_oz_product(gpe_ctx* ctx, const gpe_oz_operand* a, const gpe_oz_operand* b,
                         const gpe_oz_params* p, double* C, int32_t* exa_out, int32_t* exb_out,
                         int8_t* res_out);
+
+/* Test hook for one launch of the plain (non-fused) grouped fp64 GEMM k_gemm on a group of
+ * problems, an addition within ABI 10; the reference has no counterpart.  Descriptors come
+ * from mkprob, split K from split_k, the tile list / CDEF choice from add_launch (on a plan of
+ * the hook's own) and the launch from launch_gemm_range: the routines every production GEMM
+ * goes through.  Device memory is the hook's own and freed on every way out; the context's
+ * resident factor and cached plans are not touched.
+ *
+ * Buffers: nbuf host fp64 arrays bufs[i] of lens[i] doubles, copied to the device as they are
+ * and copied back whole afterwards.  Problem p names its operands by buffer index, element
+ * offset and leading dimension; operands may share a buffer, and C may live in the buffer of
+ * A and B (that the tiles read and the tiles written are disjoint is the caller's business).
+ * With kind = 0..3 (launch_gemm_range: 0 <A M-contiguous, B N-contiguous>, 1 <A K-contiguous>,
+ * 2 <both K-contiguous>, 3 <B K-contiguous>), over 128 x 128 tiles (ti, tj), ti < mt, tj < nt
+ * (tj <= ti only under GPE_G_CLOWER):
+ *   opA(m, k) = A[k + m lda] (K-contiguous) or A[m + k lda];  opB(k, n) likewise with ldb;
+ *   C[m + n ldc] = alpha sum_{kbeg <= k < kend} opA(m, k) opB(k, n) + beta C[m + n ldc],
+ *   kbeg = 128 ti under GPE_G_KBEG_TI (else 0),
+ *   kend = min(K, 128 (ti kti_mul + kti_off + 1)) under GPE_G_KEND_TI (else K);
+ * an empty range leaves C = beta C.  With beta = 0, C is not read.
+ *
+ * launch: kind; split (1: split_k on the group, with scratch and counters of the hook's own,
+ * the counters zeroed once at allocation); listed (1: the tile list of order_tiles where
+ * add_launch finds the group listable; 0: the implicit order); reps >= 1 identical launches
+ * back to back on the context's stream, C's buffers restored from the inputs (on the device)
+ * before every launch after the first.
+ *
+ * Outputs: ksplit_out[nprob] the split each problem got (1: none); info_out[0] 1 if the launch
+ * had a tile list, info_out[1] 1 if the CDEF instance ran, info_out[2] the workgroups of one
+ * launch; tiles_out (tiles_cap entries, may be NULL with tiles_cap 0) the tile list, codes
+ * p << 24 | ti << 12 | tj, when there is one.
+ *
+ * GPE_ERR_ARG, with text and nothing launched, for: a flag other than the three above (the
+ * fused Cholesky's in-launch hand-offs are out of reach); K not a positive multiple of 16;
+ * alpha == 0 or not finite (the kernel forms beta / alpha); an odd or negative offset or an
+ * odd leading dimension (16-byte loads and stores); ldc > 2^21 (the kernel's other path for
+ * C, not reached here); mt or nt outside [1, 4096], more than 65536 tiles, 1024 problems or
+ * 64 buffers; a buffer index that names no buffer;
+ * negative kti_mul / kti_off; a tile whose operand window over its own K range, or whose C
+ * window, leaves its buffer; listed with 256 or more problems; a tile list that does not fit
+ * tiles_cap; kind, split, listed or reps (1..16) out of range. */
+enum { GPE_G_CLOWER = 1, GPE_G_KBEG_TI = 2, GPE_G_KEND_TI = 4 };
+typedef struct gpe_gemm_group_prob {
+    int32_t a_buf, b_buf, c_buf;
+    int32_t mt, nt, K, flags, kti_mul, kti_off;
+    int64_t a_off, lda, b_off, ldb, c_off, ldc;
+    double alpha, beta;
+} gpe_gemm_group_prob;
+typedef struct gpe_gemm_group_launch {
+    int32_t kind, split, listed, reps;
+} gpe_gemm_group_launch;
+int gpe_test_gemm_group(gpe_ctx* ctx, int32_t nbuf, double* const* bufs, const int64_t* lens,
+                        int32_t nprob, const gpe_gemm_group_prob* probs,
+                        const gpe_gemm_group_launch* launch, int32_t* ksplit_out,
+                        int32_t* info_out, uint32_t* tiles_out, int64_t tiles_cap);
 
 /* Benchmark hook: time `reps` launches of the grouped GEMM on device-resident
  * random operands: C (mt*128 x nt*128, lower tiles only if lower) += -A B^T-style
