@@ -10,7 +10,9 @@ The covariance build, Cholesky factorisation, triangular solves, log-marginal-
 likelihood gradient and posterior run in libgpemu.so (hand-written HIP for
 gfx950, C-ABI in include/gpemu.h); there is no CPU fallback.
 """
-from .api import loo, plot, posterior, posterior_gradient, posterior_sample, setup, train  # noqa: F401
+from .api import (loo, plot, posterior, posterior_gradient, posterior_mean, posterior_sample,  # noqa: F401
+                  setup, train)
 
-__all__ = ["setup", "train", "plot", "posterior", "posterior_sample", "loo", "posterior_gradient"]
+__all__ = ["setup", "train", "plot", "posterior", "posterior_sample", "loo", "posterior_gradient",
+           "posterior_mean"]
 __version__ = "0.1.0"

@@ -1,6 +1,6 @@
 """Public API with the reference's signatures (emulatorfunctions.py:13-286):
-setup, train, plot, posterior, posterior_sample; and loo and posterior_gradient, which the
-reference lacks."""
+setup, train, plot, posterior, posterior_sample; and loo, posterior_gradient and
+posterior_mean, which the reference lacks."""
 from __future__ import annotations
 
 import numpy as _np
@@ -99,6 +99,15 @@ def posterior_gradient(E, x, want_var=True):
     x = _as_points(E, x)
     xs = _model.Data(x, None, E.basis, E.par, E.beliefs, E.K)
     return _model.posterior_gradient(xs, E.training, E.par, E.K, want_var=want_var)
+
+
+def posterior_mean(E, x):
+    """The posterior mean alone at x, as ``posterior`` takes it (m values; no counterpart in
+    the reference): no covariance is formed, so millions of points cost what their kernel
+    evaluations cost.  For every kernel family; equal to ``posterior``'s mean to rounding."""
+    x = _as_points(E, x)
+    xs = _model.Data(x, None, E.basis, E.par, E.beliefs, E.K)
+    return _model.posterior_mean(xs, E.training, E.par, E.K)
 
 
 def loo(E):

@@ -30,6 +30,7 @@
 #include "gpemu_ozaki.hpp"
 #include "gpemu_pivchol.hpp"
 #include "gpemu_postgrad.hpp"
+#include "gpemu_postmean.hpp"
 #include "gpemu_host_alloc.hpp"
 
 using namespace gpe;
@@ -277,6 +278,11 @@ struct gpe_ctx {
   // Q^-1, beta, hdim, the results, k_post_grad's partial sums and G padded to the GEMM's K step
   double* dPg = nullptr;
   size_t pg_cap = 0;
+  // the posterior mean alone (gpe_posterior_mean): k_post_mean's segment sums and the chunk's
+  // result; the points of a chunk (GPEMU_MEAN_CHUNK, a multiple of 128)
+  double* dPm = nullptr;
+  size_t pm_cap = 0;
+  long long mean_chunk = 65536;
 
   // resident factor (gpe_factor)
   bool factor_valid = false;
@@ -2105,6 +2111,7 @@ gpe_ctx* gpe_create(int32_t device) {
     if (const char* ep = std::getenv("GPEMU_CHOL_PRIO")) c->chol_prio = std::atoi(ep) != 0;
     if (const char* et = std::getenv("GPEMU_TINY")) c->tiny = std::atoi(et) != 0;
     if (const char* ed = std::getenv("GPEMU_DEBUG_SKIP_WAIT")) c->dbg_skip_wait = std::atoi(ed);
+    if (const char* em = std::getenv("GPEMU_MEAN_CHUNK")) c->mean_chunk = std::max(1, std::atoi(em) / 128) * 128LL;
     if (const char* eo = std::getenv("GPEMU_OZAKI")) c->oz_on = std::atoi(eo) != 0;
     if (const char* en = std::getenv("GPEMU_OZAKI_MIN_NP")) c->oz_min_np = std::max(512, std::atoi(en));
     if (const char* em = std::getenv("GPEMU_OZAKI_MODULI")) c->oz_nmod = std::max(8, std::min(OZ_MAXMOD, std::atoi(em)));
@@ -2179,7 +2186,7 @@ void gpe_destroy(gpe_ctx* c) {
                     c->aux.logdet, c->dinvdelta, c->dZ,
                     c->dR2, c->dWa, c->dskp, c->dgpart, c->dgram, c->dT2, c->dcpart, c->dcsum,
                     c->dW1, c->dW2, c->dW3, c->dXs, c->dXsw, c->dsmall, c->dtiny, c->dsnb, c->dRn, c->dNU,
-                    c->dVall, c->dXall, c->dTall, c->dPc, c->dPcL, c->dPg};
+                    c->dVall, c->dXall, c->dTall, c->dPc, c->dPcL, c->dPg, c->dPm};
   for (double* b : bufs)
     if (b) hipFree(b);
   if (c->dinfo) hipFree(c->dinfo);
@@ -3541,6 +3548,116 @@ int posterior_impl(gpe_ctx* c, const PostReq& r) {
   return S.full ? S.full_var() : S.diag();
 }
 
+// k_post_mean<DMAX, FAM, WIDE> for d inputs (the widths of launch_post_grad_fam)
+template <int FAM>
+void launch_post_mean_fam(int d, dim3 g, hipStream_t st, const PostMeanArgs& a) {
+  const dim3 b(PM_LANES);
+  if (d > 32) hipLaunchKernelGGL((k_post_mean<PM_WIDE, FAM, true>), g, b, 0, st, a);
+  else if (d <= 4) hipLaunchKernelGGL((k_post_mean<4, FAM, false>), g, b, 0, st, a);
+  else if (d <= 8) hipLaunchKernelGGL((k_post_mean<8, FAM, false>), g, b, 0, st, a);
+  else if (d <= 12) hipLaunchKernelGGL((k_post_mean<12, FAM, false>), g, b, 0, st, a);
+  else if (d <= 16) hipLaunchKernelGGL((k_post_mean<16, FAM, false>), g, b, 0, st, a);
+  else hipLaunchKernelGGL((k_post_mean<32, FAM, false>), g, b, 0, st, a);
+}
+
+// The posterior mean alone (gpe_posterior_mean): gamma from Posterior::setup(), then per chunk
+// the points' upload, k_scale_points, k_post_mean and k_post_mean_fin, and the copy of y into a
+// pinned slot; the host adds hs . beta as Posterior::point does.  Two pinned slots of points
+// and two of results: chunk i + 1's upload and kernels are queued before the host finishes
+// chunk i.  Device workspace: the chunk's points twice and its nseg + 1 sums per point.
+int posterior_mean_impl(gpe_ctx* c, int64_t m, const double* Xs, const double* Hs, const double* beta,
+                        double* mean_out) {
+  CHK(check_ready(c));
+  if (!c->factor_valid) return fail(c, GPE_ERR_STATE, "no resident factor (call gpe_factor)");
+  if (m <= 0 || !Xs || !Hs || !beta || !mean_out)
+    return fail(c, GPE_ERR_ARG, "bad posterior_mean args (m >= 1; Xs, Hs, beta and mean_out not NULL)");
+  if (c->prof)   // phase 0: k_post_mean's device time over the chunks, phase 1: the chunks
+    for (int i = 0; i < 8; ++i) c->phase_ms[i] = 0.0;
+  CHK(ensure_linv(c));
+  PostReq r{m, Xs, Hs, beta, 1.0, 64, mean_out, PostVar::DIAG, nullptr};
+  Posterior S(c, r);
+  CHK(S.setup());   // gamma in dWa's first column, coff, fam
+  const int d = c->d, q = c->q;
+  const long long np = c->n_pad, CH = c->mean_chunk;
+  auto pad_pts = [](long long v) { return ((v + PM_PTS - 1) / PM_PTS) * PM_PTS; };
+  const long long mp0 = pad_pts(std::min<long long>(CH, m));
+  const int nrt = (int)(np / PM_RI), nseg = (nrt + PM_SEG - 1) / PM_SEG;
+  CHK(grow_buf(c, &c->dXs, &c->xs_cap, (size_t)mp0 * d));
+  CHK(grow_buf(c, &c->dXsw, &c->xsw_cap, (size_t)mp0 * d));
+  CHK(grow_buf(c, &c->dPm, &c->pm_cap, (size_t)(nseg + 1) * mp0));
+  double* dY = c->dPm + (size_t)nseg * mp0;
+  CHK(ensure_pinned(c, 2 * (size_t)mp0 * d + 2 * (size_t)mp0 + d + 64));
+  double* pin_in[2] = {c->hpin, c->hpin + (size_t)mp0 * d};
+  double* pin_out[2] = {pin_in[1] + (size_t)mp0 * d, pin_in[1] + (size_t)mp0 * d + mp0};
+  double* pin_dl = pin_out[1] + mp0;   // 1 / delta
+  for (int k = 0; k < d; ++k) pin_dl[k] = 1.0 / c->f_delta[k];
+  HIPCHK(c, hipMemcpyAsync(c->dinvdelta, pin_dl, d * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  if (!c->ev_pipe[0])
+    for (hipEvent_t& e : c->ev_pipe) HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  auto dev_chunk = [&](long long s0, int slot) -> int {
+    const long long mc = std::min(CH, m - s0), mp = pad_pts(mc);
+    std::memcpy(pin_in[slot], Xs + s0 * d, (size_t)mc * d * sizeof(double));
+    // (k_scale_points reads the mc points only and writes zeros for the padded ones)
+    HIPCHK(c, hipMemcpyAsync(c->dXs, pin_in[slot], (size_t)mc * d * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_scale_points, dim3((unsigned)((mp * d + 255) / 256)), dim3(256), 0, c->stream, c->dXs,
+                       c->dinvdelta, d, (int)mc, (int)mp, c->dXsw);
+    HIPCHK(c, hipGetLastError());
+    // one workgroup per column of points and segment of rows
+    PostMeanArgs a;
+    a.xw = c->dXw; a.xsw = c->dXsw; a.gam = c->dWa; a.part = c->dPm; a.coff = S.coff;
+    a.n = (int)c->n; a.np = (int)np; a.mp = (int)mp; a.d = d;
+    const dim3 grid((unsigned)(mp / (d > 32 ? PM_LANES : PM_PTS)), (unsigned)nseg);
+    if (c->prof) HIPCHK(c, hipEventRecord(c->ev[4], c->stream));
+    if (S.fam == FAM_MATERN32) launch_post_mean_fam<FAM_MATERN32>(d, grid, c->stream, a);
+    else if (S.fam == FAM_MATERN52) launch_post_mean_fam<FAM_MATERN52>(d, grid, c->stream, a);
+    else launch_post_mean_fam<FAM_GAUSS>(d, grid, c->stream, a);
+    HIPCHK(c, hipGetLastError());
+    if (c->prof) {   // (profiling only: one synchronisation per chunk)
+      float ms = 0.f;
+      HIPCHK(c, hipEventRecord(c->ev[5], c->stream));
+      HIPCHK(c, hipEventSynchronize(c->ev[5]));
+      (void)hipEventElapsedTime(&ms, c->ev[4], c->ev[5]);
+      c->phase_ms[0] += ms;
+      c->phase_ms[1] += 1.0;
+    }
+    hipLaunchKernelGGL(k_post_mean_fin, dim3((unsigned)((mp + 255) / 256)), dim3(256), 0, c->stream, c->dPm, nseg,
+                       (int)mp, dY);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(pin_out[slot], dY, (size_t)mc * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipEventRecord(c->ev_pipe[slot], c->stream));
+    return GPE_OK;
+  };
+  auto host_chunk = [&](long long s0, const double* y) {
+    const long long mc = std::min(CH, m - s0);
+    for (long long s = 0; s < mc; ++s) {
+      const double* hs = Hs + (s0 + s) * q;
+      double mu = y[s];
+      for (int i = 0; i < q; ++i) mu += hs[i] * beta[i];
+      mean_out[s0 + s] = mu;
+    }
+  };
+  auto pipeline = [&]() -> int {
+    int slot = 0;
+    long long prev = -1;
+    for (long long s0 = 0; s0 < m; s0 += CH, slot ^= 1) {
+      CHK(dev_chunk(s0, slot));
+      if (prev >= 0) {
+        HIPCHK(c, hipEventSynchronize(c->ev_pipe[slot ^ 1]));
+        host_chunk(prev, pin_out[slot ^ 1]);
+      }
+      prev = s0;
+    }
+    HIPCHK(c, hipEventSynchronize(c->ev_pipe[slot ^ 1]));
+    host_chunk(prev, pin_out[slot ^ 1]);
+    return GPE_OK;
+  };
+  const int rc = pipeline();
+  // (a failed step may leave copies into the pinned slots queued: drained before the staging
+  // buffer can be reused or regrown)
+  if (rc != GPE_OK) (void)hipStreamSynchronize(c->stream);
+  return rc;
+}
+
 }  // namespace
 
 extern "C" {
@@ -3565,6 +3682,11 @@ int gpe_posterior_grad(gpe_ctx* c, int64_t m, const double* Xs, const double* Hs
   r.dmean_out = dmean_out;
   r.dvar_out = dvar_out;
   return posterior_impl(c, r);
+}
+
+int gpe_posterior_mean(gpe_ctx* c, int64_t m, const double* Xs, const double* Hs, const double* beta,
+                       double* mean_out) {
+  return posterior_mean_impl(c, m, Xs, Hs, beta, mean_out);
 }
 
 int gpe_noise_sample(gpe_ctx* c, int64_t m, const double* Xs, const double* Hs, const double* beta,

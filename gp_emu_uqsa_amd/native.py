@@ -84,6 +84,7 @@ SIGNATURES = {
                                   _D, _D]),
     "gpe_posterior_grad": (_ct.c_int, [_VP, _ct.c_int64, _D, _D, _D, _ct.POINTER(_ct.c_int32), _D, _ct.c_double,
                                        _D, _D, _D, _D]),
+    "gpe_posterior_mean": (_ct.c_int, [_VP, _ct.c_int64, _D, _D, _D, _D]),
     "gpe_noise_sample": (_ct.c_int, [_VP, _ct.c_int64, _D, _D, _D, _ct.c_double, _D, _ct.c_double,
                                      _D, _ct.c_int32, _D, _D, _D]),
     "gpe_posterior_pivchol": (_ct.c_int, [_VP, _ct.c_int64, _D, _D, _D, _ct.c_double, _D, _ct.c_double,
@@ -348,6 +349,22 @@ class Context:
                                                 float(sigma), _ptr(mean), _ptr(var), _ptr(dmean), _ptr(dvar)),
                     "gpe_posterior_grad")
         return mean, var, dmean, dvar
+
+    def posterior_mean(self, Xs, Hs, beta):
+        """The posterior mean alone at Xs (gpe_posterior_mean): hs . beta + sum_i gamma_i K*_i from
+        one fused kernel, without K*, L^-1 K* or the variance.  It agrees with posterior()'s
+        mean to the rounding of an n-term sum (same gamma, same terms, another summation
+        order) and does not depend on the chunk length; any m."""
+        Xs = _f64(Xs)
+        if Xs.ndim == 1:
+            Xs = Xs.reshape(-1, 1)
+        m = Xs.shape[0]
+        Hs = _f64(Hs, (m, self.q))
+        beta = _f64(beta).ravel()
+        mean = _np.zeros(m)
+        self._check(self.lib.gpe_posterior_mean(self._h, m, _ptr(Xs), _ptr(Hs), _ptr(beta), _ptr(mean)),
+                    "gpe_posterior_mean")
+        return mean
 
     def noise_sample(self, Xs, Hs, beta, sigma, t, U, r_new=None, r_scale=0.0):
         """noise_fit's estimation step for the resident factor: the posterior at Xs

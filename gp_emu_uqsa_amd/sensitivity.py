@@ -36,9 +36,10 @@ from __future__ import annotations
 
 import numpy as np
 
-from .model import Data, posterior_gradient, upload_training
+from .model import Data, posterior_gradient, posterior_mean, upload_training
 
-__all__ = ["setup", "sense_table", "Sensitivity", "NonGaussianKernel", "derivative_measures"]
+__all__ = ["setup", "sense_table", "Sensitivity", "NonGaussianKernel", "derivative_measures",
+           "sobol_points", "sobol_estimates", "mc_indices", "mc_main_effect"]
 
 
 class NonGaussianKernel(ValueError):
@@ -50,8 +51,9 @@ def derivative_measures(emul, x):
     points x (m x d, in the coordinates ``posterior`` takes, drawn from the inputs'
     distribution): (nu, nu / sum(nu)) with nu_k = mean over the points of (d mean / d x_k)^2.
 
-    No closed form is involved, so this works for every correlation family, and it is the
-    route for Matern emulators, on which ``setup`` raises ``NonGaussianKernel``.  One
+    No closed form is involved, so this works for every correlation family, and it is a
+    route for Matern emulators, on which ``setup`` raises ``NonGaussianKernel`` (the
+    variance-based one is ``mc_indices`` / ``mc_main_effect``).  One
     gpe_posterior_grad call without the variance gradient (``posterior_gradient`` with
     want_var=False)."""
     x = np.asarray(x, dtype=float)
@@ -64,15 +66,130 @@ def derivative_measures(emul, x):
     return nu, (nu / tot if tot > 0.0 else np.zeros_like(nu))
 
 
+def sobol_points(d, N, seed=0, dist="normal", m=0.0, v=1.0):
+    """The two independent sample matrices (A, B), each N x d, of a Sobol' design, in the
+    coordinates ``posterior`` takes; m and v are the inputs' means and variances (scalars or d
+    values).  Both come from one ``np.random.RandomState(seed)``, A from its first draw and B
+    from the next: dist="normal" gives m + sqrt(v) * standard_normal((N, d)), dist="uniform"
+    random_sample((N, d)) scaled to [m - sqrt(3 v), m + sqrt(3 v)] (mean m, variance v)."""
+    d, N = int(d), int(N)
+    m = np.broadcast_to(np.asarray(m, dtype=float), (d,))
+    v = np.broadcast_to(np.asarray(v, dtype=float), (d,))
+    rs = np.random.RandomState(seed)
+    if dist == "normal":
+        draw = lambda: m + np.sqrt(v) * rs.standard_normal((N, d))
+    elif dist == "uniform":
+        half = np.sqrt(3.0 * v)
+        draw = lambda: (m - half) + 2.0 * half * rs.random_sample((N, d))
+    else:
+        raise ValueError("dist must be 'normal' or 'uniform', not " + repr(dist))
+    A = draw()
+    B = draw()
+    return A, B
+
+
+def sobol_estimates(fA, fB, fAB):
+    """Monte-Carlo variance-based indices from a function's values at a Sobol' design (host
+    only): fA, fB (N) at the rows of A and B, fAB (d x N) with fAB[i] at A with column i taken
+    from B.  Returns a dict:
+      mean, var   mean and mean squared deviation of [fA; fB]
+      V, V_se     V_i = mean(fB (fAB_i - fA)) (Saltelli et al. 2010), the main-effect variance
+      VT, VT_se   VT_i = 1/2 mean((fA - fAB_i)^2) (Jansen 1999), the total-effect variance
+      S, ST       V / var, VT / var
+    The standard errors are the standard deviation (ddof = 1) of the N per-sample terms over
+    sqrt(N)."""
+    fA = np.asarray(fA, dtype=float).ravel()
+    fB = np.asarray(fB, dtype=float).ravel()
+    fAB = np.asarray(fAB, dtype=float).reshape(-1, fA.size)
+    N = fA.size
+    both = np.concatenate([fA, fB])
+    f0 = float(np.mean(both))
+    var = float(np.mean((both - f0) ** 2))
+    tV = fB[None, :] * (fAB - fA[None, :])
+    tT = 0.5 * (fA[None, :] - fAB) ** 2
+    V, VT = tV.mean(axis=1), tT.mean(axis=1)
+    out = {"mean": f0, "var": var, "V": V, "VT": VT,
+           "V_se": tV.std(axis=1, ddof=1) / np.sqrt(N), "VT_se": tT.std(axis=1, ddof=1) / np.sqrt(N)}
+    with np.errstate(divide="ignore", invalid="ignore"):
+        out["S"], out["ST"] = V / var, VT / var
+    return out
+
+
+def _mean_at(emul, x):
+    """The emulator's posterior mean at the rows of x: one gpe_posterior_mean call."""
+    xs = Data(np.ascontiguousarray(x, dtype=float), None, emul.basis, emul.par, emul.beliefs, emul.K)
+    return posterior_mean(xs, emul.training, emul.par, emul.K)
+
+
+def mc_indices(emul, m, v, samples, seed=0, dist="normal"):
+    """Main-effect and total-effect indices of the emulator's posterior mean by Monte Carlo, for
+    inputs with means m and variances v (``sobol_points``): ``sobol_estimates``' dict from the
+    (d + 2) * samples points [A; B; AB_0; ...; AB_d-1], evaluated in ONE posterior-mean call.
+
+    No closed form is involved, so this works for every correlation family and both input
+    distributions; it is the variance-based route for Matern emulators, on which ``setup``
+    raises ``NonGaussianKernel``.  The indices are those of the posterior mean as a function:
+    the emulator's own uncertainty about them (the reference's E*[V_i] terms) is not included."""
+    d = emul.training.inputs.shape[1]
+    N = int(samples)
+    A, B = sobol_points(d, N, seed, dist, m, v)
+    X = np.empty(((d + 2) * N, d))
+    X[:N], X[N:2 * N] = A, B
+    for i in range(d):
+        blk = X[(2 + i) * N:(3 + i) * N]
+        blk[:] = A
+        blk[:, i] = B[:, i]
+    f = _mean_at(emul, X)
+    return sobol_estimates(f[:N], f[N:2 * N], f[2 * N:].reshape(d, N))
+
+
+def mc_main_effect(emul, m, v, points=100, samples=10000, seed=0, w=None, dist="normal", grid_index=None):
+    """Main effects of the posterior mean by Monte Carlo: for each input P in w (None: all)
+    and each of ``points`` values across input_range[P] (the grid of
+    ``Sensitivity.main_effect``), the mean of the posterior mean with input P held at the
+    value and the other inputs drawn from their distribution -- matrix A of ``sobol_points``,
+    drawn once and used for every value and every input.  One posterior-mean call per input.
+
+    Returns a dict: ``mean_effect`` and its standard error ``se`` (d x points; rows of inputs
+    outside w are 0), and ``uE`` and ``uE_se``, the mean of the posterior mean over A itself.
+    grid_index (a slice or an index array) evaluates only those of the ``points`` grid values;
+    the other entries are NaN.
+    For a Gaussian kernel, normal inputs and a linear mean these estimate
+    ``Sensitivity.mean_effect`` and ``uE``; they work for every family and both distributions
+    and, like ``mc_indices``, describe the posterior mean only."""
+    d = emul.training.inputs.shape[1]
+    N, points = int(samples), int(points)
+    A, _ = sobol_points(d, N, seed, dist, m, v)
+    fA = _mean_at(emul, A)
+    out = {"mean_effect": np.zeros((d, points)), "se": np.zeros((d, points)),
+           "uE": float(np.mean(fA)), "uE_se": float(np.std(fA, ddof=1) / np.sqrt(N))}
+    at = np.arange(points) if grid_index is None else np.arange(points)[grid_index]
+    for P in (range(d) if w is None else w):
+        grid = np.linspace(emul.all_data.input_range[P][0], emul.all_data.input_range[P][1], points)
+        X = np.tile(A, (at.size, 1))
+        X[:, P] = np.repeat(grid[at], N)
+        f = _mean_at(emul, X).reshape(at.size, N)
+        for key, val in (("mean_effect", f.mean(axis=1)), ("se", f.std(axis=1, ddof=1) / np.sqrt(N))):
+            out[key][P] = np.nan
+            out[key][P, at] = val
+    return out
+
+
 def setup(emul, m, v, case="case2"):
     """Sensitivity instance for emulator `emul`, input means m and variances v
-    (reference sensitivityfunctions.py:7-54)."""
+    (reference sensitivityfunctions.py:7-54).
+
+    The closed forms are those of the Gaussian kernel: any other family raises
+    ``NonGaussianKernel``.  The variance-based route for such an emulator is Monte Carlo on its
+    posterior mean, ``mc_indices`` and ``mc_main_effect``; ``derivative_measures`` is the
+    derivative-based one."""
     print("\n*** Initialising Sensitivity class ***")
     family = getattr(emul.K, "family", "gaussian")
     if family != "gaussian":
         raise NonGaussianKernel(
             "sensitivity analysis needs a gaussian kernel: its integrals are closed forms of "
-            "exp(-((x-x')/delta)^2), and this emulator's kernel is " + family)
+            "exp(-((x-x')/delta)^2), and this emulator's kernel is " + family
+            + " (mc_indices and mc_main_effect estimate the variance-based measures for any kernel)")
     if not isinstance(m, list) or not isinstance(v, list):
         print("ERROR: 2nd and 3rd arguments must be lists of floats. "
               "Return None.")

@@ -36,7 +36,7 @@ extern "C" {
                                 gpe_device_synchronize, gpe_build_id;
                                 9: gpe_dist_local_rows takes the basis width q;
                                 10: gpe_ozaki_stats (gpe_loo, gpe_posterior_pivchol,
-                                gpe_posterior_grad and the test hooks gpe_test_oz_product and
+                                gpe_posterior_grad, gpe_posterior_mean and the test hooks gpe_test_oz_product and
                                 gpe_test_gemm_group were added within 10: additions, nothing
                                 existing changed) */
 
@@ -194,6 +194,26 @@ int gpe_posterior(gpe_ctx* ctx, int64_t m, const double* Xs, const double* Hs,
 int gpe_posterior_grad(gpe_ctx* ctx, int64_t m, const double* Xs, const double* Hs,
                        const double* dHs, const int32_t* hdim, const double* beta, double sigma,
                        double* mean_out, double* var_out, double* dmean_out, double* dvar_out);
+
+/* Posterior mean alone at m points (an addition within ABI 10; the reference has no entry
+ * that skips the variance).  Xs, Hs, beta as for gpe_posterior; mean_out (m):
+ *   mean_s = hs . beta + sum_i gamma_i K*_is,   gamma = A^-1 (f - H beta),
+ * with gamma bit for bit the one gpe_posterior uses and every term gamma_i K*_is formed with
+ * the arithmetic of gpe_posterior's K*; only the order of the sum over i differs, so the two
+ * means agree to the rounding of an n-term sum.  One fused kernel (gpemu_postmean.hpp) reads
+ * the training rows and sums on the fly: no n x m block is formed and no n^2 m product runs;
+ * the work is n m (2 d + one exp) and the device workspace (2 d + n / 192 + 2) doubles per
+ * point of a chunk.  Any m, in chunks of 65536 points (GPEMU_MEAN_CHUNK, a multiple of 128,
+ * read when the context is created) through two pinned slots: the next chunk's upload is
+ * queued before the host finishes the previous one.  The training rows are summed in segments
+ * of 192 whose sums are added in index order whatever m and the chunk length are: the result
+ * does not depend on the chunk length, repeated calls return the same bits, and there are no
+ * floating-point atomics.  Every family and nugget kind, with or without r; the resident
+ * factor and what other entries keep of it stay as they are.
+ * GPE_ERR_STATE without a resident factor; GPE_ERR_ARG for m <= 0 or a NULL pointer;
+ * GPE_NOT_PD if H^T A^-1 H is not positive definite, as gpe_posterior. */
+int gpe_posterior_mean(gpe_ctx* ctx, int64_t m, const double* Xs, const double* Hs,
+                       const double* beta, double* mean_out);
 
 /* ---- Sensitivity / UQ building blocks, resident factor --------
  * Replace the O(n^2) parts of sensitivity/_sensitivityclasses.py (case2): the
@@ -433,6 +453,8 @@ int gpe_posterior_pivchol(gpe_ctx* ctx, int64_t m, const double* Xs, const doubl
  * After gpe_posterior_pivchol: [0] forming the covariance, [1] the pivot steps, [2] the
  * trailing updates and panel copies, [6] their sum (one synchronisation per panel is added).
  * After gpe_posterior_grad: [0] k_post_grad's device time summed over the chunks, [1] the
+ * number of chunks (one synchronisation per chunk is added).
+ * After gpe_posterior_mean: [0] k_post_mean's device time summed over the chunks, [1] the
  * number of chunks (one synchronisation per chunk is added).
  * Only filled when profiling is on. */
 int gpe_set_profiling(gpe_ctx* ctx, int32_t on);
