@@ -24,6 +24,7 @@
 
 #include "../../include/gpemu.h"
 #include "gpemu_kernels.hpp"
+#include "gpemu_gemm_sched.hpp"
 #include "gpemu_small.hpp"
 #include "gpemu_tiny.hpp"
 #include "gpemu_snb.hpp"
@@ -59,16 +60,6 @@ enum AdhocSlot {
   ADHOC_BENCH = ADHOC_DESC_BASE + 16,     // gpe_bench_gemm
 };
 
-struct Launch {       // one grouped GEMM launch of the cached schedule
-  int kind;           // 0: <0,0>, 1: <1,0>, 2: <1,1>, 3: <0,1>, 4: <0,0> fused Cholesky step
-  int first, count;   // descriptor range
-  int tiles;
-  double flops;       // algorithmic flops
-  long long list = -1;  // offset of its tile list in the device list array (-1: implicit order)
-  bool cdef = false;    // k_gemm's CDEF instance (gemm_cdef of some problem)
-  int* ticket = nullptr;  // fused Cholesky launches: list positions claimed by ticket (k_gemm)
-};
-
 struct Plan {
   long long n_pad = 0;
   const double* a_ptr = nullptr;   // buffers the descriptors point into
@@ -92,7 +83,7 @@ struct Plan {
   // the augmented row's tiles [h, NB) by the first h columns
   int split_h = 0, aug_mid = -1;
   std::vector<int> sfused, sfused_aug, sgrp, sgrp_aug;
-  std::vector<Launch> launches;
+  std::vector<GemmLaunch> launches;
   std::vector<GemmProb> probs;
   std::vector<unsigned> tiles;   // concatenated tile lists
 };
@@ -510,11 +501,8 @@ static void launch_contract(gpe_ctx* c, int d, int P, dim3 gc, int nblk, const d
   }
 }
 
-int launch_gemm_range(gpe_ctx* c, const Launch& L, hipStream_t st = nullptr) {
+int launch_gemm_range(gpe_ctx* c, const GemmLaunch& L, hipStream_t st = nullptr) {
   if (!st) st = c->stream;
-  const size_t lds = G_LDS_LAUNCH_DOUBLES * sizeof(double);
-  const GemmProb* pr = c->dprobs + L.first;
-  const unsigned* tl = (L.list >= 0) ? c->dtiles + L.list : nullptr;
   if (c->prof) {
     if (c->gev_used + 2 > c->gev.size()) {
       for (int i = 0; i < 256; ++i) {
@@ -525,25 +513,7 @@ int launch_gemm_range(gpe_ctx* c, const Launch& L, hipStream_t st = nullptr) {
     }
     HIPCHK(c, hipEventRecord(c->gev[c->gev_used], st));
   }
-  const dim3 g(L.tiles), b(256);
-  if (L.cdef) {
-    switch (L.kind) {
-      case 0: hipLaunchKernelGGL((k_gemm<false, false, false, true>), g, b, lds, st, pr, L.count, tl, c->dinfo, L.ticket); break;
-      case 1: hipLaunchKernelGGL((k_gemm<true, false, false, true>), g, b, lds, st, pr, L.count, tl, c->dinfo, L.ticket); break;
-      case 2: hipLaunchKernelGGL((k_gemm<true, true, false, true>), g, b, lds, st, pr, L.count, tl, c->dinfo, L.ticket); break;
-      case 3: hipLaunchKernelGGL((k_gemm<false, true, false, true>), g, b, lds, st, pr, L.count, tl, c->dinfo, L.ticket); break;
-      default: hipLaunchKernelGGL((k_gemm<false, false, true, true>), g, b, lds, st, pr, L.count, tl, c->dinfo, L.ticket); break;
-    }
-  } else {
-    switch (L.kind) {
-      case 0: hipLaunchKernelGGL((k_gemm<false, false>), g, b, lds, st, pr, L.count, tl, c->dinfo, L.ticket); break;
-      case 1: hipLaunchKernelGGL((k_gemm<true, false>), g, b, lds, st, pr, L.count, tl, c->dinfo, L.ticket); break;
-      case 2: hipLaunchKernelGGL((k_gemm<true, true>), g, b, lds, st, pr, L.count, tl, c->dinfo, L.ticket); break;
-      case 3: hipLaunchKernelGGL((k_gemm<false, true>), g, b, lds, st, pr, L.count, tl, c->dinfo, L.ticket); break;
-      default: hipLaunchKernelGGL((k_gemm<false, false, true>), g, b, lds, st, pr, L.count, tl, c->dinfo, L.ticket); break;
-    }
-  }
-  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, launch_k_gemm(L, c->dprobs, c->dtiles, c->dinfo, st));
   if (c->prof) {
     HIPCHK(c, hipEventRecord(c->gev[c->gev_used + 1], st));
     c->gev_used += 2;
@@ -553,200 +523,22 @@ int launch_gemm_range(gpe_ctx* c, const Launch& L, hipStream_t st = nullptr) {
   return GPE_OK;
 }
 
-// tiles of a problem
-int prob_tiles(const GemmProb& p) {
-  return ((p.flags & G_CLOWER) ? p.mt * (p.mt + 1) / 2 : p.mt * p.nt) * std::max(1, p.ksplit);
-}
-
-// Split K over workgroups for a launch with few tiles (small n, the TRTRI's first levels):
-// there each tile's K loop on one CU is the launch's latency, and the chip has 512
-// workgroup slots.  ks shares of at least 64 K each, at most SPLIT_SLOTS partials; beta = 0
-// problems only.  The launch then takes the implicit tile order (no list).
-constexpr int SPLIT_SLOTS = 512;
-void split_k(std::vector<GemmProb>& probs, double* part, int* tcnt) {
-#ifdef GPE_NO_SPLITK   // dev A/B build (tools/ab_libs.sh)
-  return;
-#endif
-  int T = 0, kmax = 0;
-  for (const GemmProb& p : probs) {
-    if (p.beta != 0.0 || p.ksplit > 1) return;
-    T += prob_tiles(p);
-    kmax = std::max(kmax, p.K);
-  }
-  if (T <= 0 || T >= 256) return;
-  // shares of at least 64 of K (4 stages): one 128 x 128 x 128 tile is ~16 us of fp64
-  // MFMA on one CU, the first TRTRI level's whole launch
-  const int ks = std::min({8, SPLIT_SLOTS / T, kmax / 64});
-  if (ks < 2) return;
-  int off = 0;
-  for (GemmProb& p : probs) {
-    const int tl = prob_tiles(p);
-    p.ksplit = ks;
-    p.part = part + (size_t)off * ks * TILE * TILE;
-    p.tcnt = tcnt + off;
-    off += tl;
-  }
-}
-
-// Order the tiles of one launch: rows (problem, ti) sorted longest-first, greedily
-// packed into 8 bins of equal work (one per XCD under round-robin dispatch, so a
-// row's A panel stays in one XCD's L2), bins interleaved block by block.
-// GPEMU_XCD_BLOCK=b (dev A/B): instead of whole rows, b x b blocks of tiles go to the XCD
-// bins, so the tiles one XCD runs at once share b A panels and b B panels in its L2
-int xcd_block() {
-  static const int b = [] {
-    const char* e = std::getenv("GPEMU_XCD_BLOCK");
-    return e ? std::max(0, std::min(64, std::atoi(e))) : 0;
-  }();
-  return b;
-}
-
-std::vector<unsigned> order_tiles(const std::vector<GemmProb>& probs) {
-  struct Row { int p, ti; double w; std::vector<int> tj; };
-  std::vector<Row> rows;
-  std::vector<unsigned> tail;   // G_PANEL tiles wait on the G_DIAG tile: dispatch them last
-  const int xb = xcd_block();
-  for (int p = 0; p < (int)probs.size(); ++p) {
-    const GemmProb& P = probs[p];
-    if (P.flags & G_PANEL) {
-      for (int ti = 0; ti < P.mt; ++ti)
-        for (int tj = 0; tj < P.nt; ++tj) tail.push_back(((unsigned)p << 24) | ((unsigned)ti << 12) | (unsigned)tj);
-      continue;
-    }
-    for (int ti = 0; ti < P.mt; ++ti) {
-      int kb = 0, ke = P.K;
-      if (P.flags & G_KBEG_TI) kb = ti * TILE;
-      if (P.flags & G_KEND_TI) ke = std::min(ke, (ti * P.kti_mul + P.kti_off + 1) * TILE);
-      const double wt = (double)std::max(ke - kb, 0) + 2.0 * GK;   // + fixed per-tile cost
-      const int tjmax = (P.flags & G_CLOWER) ? ti : P.nt - 1;
-      if (xb > 1 && !(P.flags & (G_DQUAD | G_DIAG))) {   // one "row" per b x b block of tiles
-        for (int tj0 = 0; tj0 <= tjmax; tj0 += xb) {
-          if (ti % xb) {   // rows of a block after its first join the first's entries
-            Row* r0 = nullptr;
-            for (auto it = rows.rbegin(); it != rows.rend(); ++it)
-              if (it->p == p && it->ti == ti - ti % xb && !it->tj.empty() && it->tj.front() / xb == tj0 / xb) {
-                r0 = &*it;
-                break;
-              }
-            if (r0) {
-              for (int tj = tj0; tj <= std::min(tjmax, tj0 + xb - 1); ++tj) r0->tj.push_back(tj + (ti % xb) * 4096);
-              r0->w += wt * (double)(std::min(tjmax, tj0 + xb - 1) - tj0 + 1);
-              continue;
-            }
-          }
-          Row r{p, ti, 0.0, {}};
-          for (int tj = tj0; tj <= std::min(tjmax, tj0 + xb - 1); ++tj) r.tj.push_back(tj);
-          r.w = wt * (double)r.tj.size();
-          rows.push_back(std::move(r));
-        }
-        continue;
-      }
-      Row r{p, ti, 0.0, {}};
-      for (int tj = 0; tj <= tjmax; ++tj) r.tj.push_back(tj);
-      r.w = wt * (double)r.tj.size();
-      if (!r.tj.empty()) rows.push_back(std::move(r));
-    }
-  }
-  std::stable_sort(rows.begin(), rows.end(), [](const Row& a, const Row& b) {
-    return a.w / a.tj.size() > b.w / b.tj.size();   // longest tiles first
-  });
-  constexpr int NX = 8;
-  std::vector<std::vector<unsigned>> bins(NX);
-  std::vector<double> load(NX, 0.0);
-  for (const Row& r : rows) {
-    int x = (int)(std::min_element(load.begin(), load.end()) - load.begin());
-    load[x] += r.w;
-    for (int tj : r.tj)   // (block entries carry their row offset in tj / 4096)
-      bins[x].push_back(((unsigned)r.p << 24) | ((unsigned)(r.ti + tj / 4096) << 12) | (unsigned)(tj % 4096));
-  }
-  std::vector<unsigned> out;
-  // a factored diagonal tile starts first, after the quadrants of its pending update
-  for (int p = 0; p < (int)probs.size(); ++p)
-    if (probs[p].flags & G_DQUAD) {
-      for (int ti = 0; ti < probs[p].mt; ++ti) {
-        const unsigned code = ((unsigned)p << 24) | ((unsigned)ti << 12);
-        out.push_back(code);
-        for (auto& b : bins) b.erase(std::remove(b.begin(), b.end(), code), b.end());
-      }
-    }
-  size_t diag_at = out.size();
-  for (int p = 0; p < (int)probs.size(); ++p)
-    if (probs[p].flags & G_DIAG) {
-      diag_at = out.size();
-      out.push_back((unsigned)p << 24);
-      for (auto& b : bins) b.erase(std::remove(b.begin(), b.end(), (unsigned)p << 24), b.end());
-    }
-  size_t longest = 0;
-  for (auto& b : bins) longest = std::max(longest, b.size());
-  for (size_t j = 0; j < longest; ++j)
-    for (int x = 0; x < NX; ++x)
-      if (j < bins[x].size()) out.push_back(bins[x][j]);
-  // The launch starts on an idle GPU and its first 512 workgroups fill two slots per CU
-  // in order: workgroup 256 + k lands on the CU of workgroup k, here the G_DIAG tile's
-  // (tools/hip/placement_probe.hip: 256 of 256 pairs i, i - 256 share a CU).  Give
-  // that slot the first panel tile: after its own update it waits on the flag and
-  // leaves the SIMDs to the diagonal factorisation, which beside a bulk tile's MFMAs
-  // runs ~1.7x slower.
-  if (diag_at < out.size() && (probs[out[diag_at] >> 24].flags & G_DIAG) && !tail.empty() &&
-      out.size() > diag_at + 256) {
-    out.insert(out.begin() + diag_at + 256, tail.front());
-    tail.erase(tail.begin());
-  }
-  out.insert(out.end(), tail.begin(), tail.end());
-  return out;
-}
-
-void add_launch(Plan& pl, int kind, std::vector<GemmProb> probs, double flops) {
-  Launch L;
-  L.kind = kind;
-  L.first = (int)pl.probs.size();
-  L.count = (int)probs.size();
-  int t = 0;
+// One launch of the cached schedule from its problems: in order_tiles' order, or in the
+// given one (codes into probs), or -- split K, 256 problems or more -- the implicit one.
+void add_launch(Plan& pl, GemmKind kind, const std::vector<GemmProb>& probs, double flops,
+                const std::vector<unsigned>* order = nullptr) {
+  GemmLaunch L = begin_launch(kind, pl.probs, flops);
   bool listable = probs.size() < 256;
-  for (auto& p : probs) {
-    p.tile_begin = t;
-    p.ntiles = prob_tiles(p);
-    t += p.ntiles;
-    L.cdef = L.cdef || gemm_cdef(p);
+  for (const GemmProb& p : probs) {
+    push_prob(L, pl.probs, p, true);
     listable = listable && p.mt <= 4096 && p.nt <= 4096 && p.ksplit <= 1;
-    pl.probs.push_back(p);
   }
-  L.tiles = t;
-  L.flops = flops;
-  if (listable) {
-    std::vector<unsigned> tl = order_tiles(probs);
-    if ((int)tl.size() == t) {
-      L.list = (long long)pl.tiles.size();
-      pl.tiles.insert(pl.tiles.end(), tl.begin(), tl.end());
-    }
+  if (order) {
+    set_list(L, pl.tiles, *order);
+  } else if (listable) {
+    const std::vector<unsigned> tl = order_tiles(probs);
+    if ((int)tl.size() == L.tiles) set_list(L, pl.tiles, tl);
   }
-  pl.launches.push_back(L);
-}
-
-size_t tiles_total_hint(const std::vector<std::vector<unsigned>>& segs) {
-  size_t n = 0;
-  for (const auto& v : segs) n += v.size();
-  return n;
-}
-
-// a launch whose tile order is given (codes p << 24 | ti << 12 | tj, p into probs)
-void add_launch_list(Plan& pl, int kind, std::vector<GemmProb> probs, double flops, const std::vector<unsigned>& order) {
-  Launch L;
-  L.kind = kind;
-  L.first = (int)pl.probs.size();
-  L.count = (int)probs.size();
-  int t = 0;
-  for (auto& p : probs) {
-    p.tile_begin = t;
-    p.ntiles = prob_tiles(p);
-    t += p.ntiles;
-    L.cdef = L.cdef || gemm_cdef(p);
-    pl.probs.push_back(p);
-  }
-  L.tiles = (int)order.size();
-  L.flops = flops;
-  L.list = (long long)pl.tiles.size();
-  pl.tiles.insert(pl.tiles.end(), order.begin(), order.end());
   pl.launches.push_back(L);
 }
 
@@ -762,36 +554,22 @@ struct InflightGuard {
   ~InflightGuard() { g_inflight[dev].fetch_sub(1); }
 };
 
-GemmProb mkprob(const double* A, long long lda, const double* B, long long ldb, double* C,
-                long long ldc, int mt, int nt, int K, int flags, double alpha, double beta) {
-  GemmProb p;
-  p.A = A; p.B = B; p.C = C;
-  p.lda = lda; p.ldb = ldb; p.ldc = ldc;
-  p.mt = mt; p.nt = nt; p.K = K; p.flags = flags;
-  p.alpha = alpha; p.beta = beta;
-  p.tile_begin = 0; p.ntiles = 0;
-  p.X = nullptr; p.ldx = 0; p.logdet = nullptr; p.diag_col0 = 0; p.flag = nullptr;
-  p.Ld = nullptr; p.ldd = 0;
-  p.pre0 = p.pre1 = p.post = nullptr; p.pre0_n = p.pre1_n = 0;
-  p.ksplit = 1; p.part = nullptr; p.tcnt = nullptr;
-  p.cpost = nullptr;
-  p.kti_mul = 1; p.kti_off = 0;
-  return p;
-}
-
-// GEMMs outside the cached plans: g[i] (k_gemm instance `kind` as Launch::kind, every tile of
-// p in the implicit order) takes descriptor slot + i.  The descriptors are uploaded in one
-// copy on the context's stream, then each launch is issued in order, or with `out` handed
-// back (out[i]) for a caller that launches later or more than once.  standalone (the test and
-// bench GEMMs): a blocking upload and k_gemm's CDEF instance where the problem takes it.
-struct AdhocGemm { int kind; GemmProb p; };
-int adhoc_gemm(gpe_ctx* c, AdhocSlot slot, const std::vector<AdhocGemm>& g, Launch* out = nullptr,
+// GEMMs outside the cached plans: g[i] (k_gemm instance `kind`, every tile of p in the
+// implicit order) is a launch of its own and takes descriptor slot + i.  The descriptors are
+// uploaded in one copy on the context's stream, then each launch is issued in order, or with
+// `out` handed back (out[i]) for a caller that launches later or more than once.  standalone
+// (the test and bench GEMMs): a blocking upload and k_gemm's CDEF instance where the problem
+// takes it.
+struct AdhocGemm { GemmKind kind; GemmProb p; };
+int adhoc_gemm(gpe_ctx* c, AdhocSlot slot, const std::vector<AdhocGemm>& g, GemmLaunch* out = nullptr,
                bool standalone = false) {
   std::vector<GemmProb> d;
+  std::vector<GemmLaunch> launches;
   for (const AdhocGemm& e : g) {
-    d.push_back(e.p);
-    d.back().tile_begin = 0;
-    d.back().ntiles = prob_tiles(e.p);
+    GemmLaunch L = begin_launch(e.kind, d);
+    push_prob(L, d, e.p, standalone);
+    L.first += slot;
+    launches.push_back(L);
   }
   if (standalone)
     HIPCHK(c, hipMemcpy(c->dprobs + slot, d.data(), d.size() * sizeof(GemmProb), hipMemcpyHostToDevice));
@@ -799,10 +577,8 @@ int adhoc_gemm(gpe_ctx* c, AdhocSlot slot, const std::vector<AdhocGemm>& g, Laun
     HIPCHK(c, hipMemcpyAsync(c->dprobs + slot, d.data(), d.size() * sizeof(GemmProb), hipMemcpyHostToDevice,
                              c->stream));
   for (size_t i = 0; i < g.size(); ++i) {
-    Launch L{g[i].kind, (int)slot + (int)i, 1, d[i].ntiles, 0.0};
-    L.cdef = standalone && gemm_cdef(d[i]);
-    if (out) out[i] = L;
-    else CHK(launch_gemm_range(c, L));
+    if (out) out[i] = launches[i];
+    else CHK(launch_gemm_range(c, launches[i]));
   }
   return GPE_OK;
 }
@@ -1075,7 +851,7 @@ int build_plan(gpe_ctx* c, Fact& F) {
         for (const Seg& sg : part[h]) bulk(fp, fl, sg.a, sg.b, sg.g0, sg.K);
       }
       fidx[o + t] = (int)pl.launches.size();
-      add_launch(pl, 4, fp, fl);
+      add_launch(pl, GEMM_FUSED, fp, fl);
       pl.launches.back().ticket = flags0 + 3 * NB + t;
     }
   }
@@ -1104,7 +880,7 @@ int build_plan(gpe_ctx* c, Fact& F) {
         const GemmProb& q = fp[pi];
         for (int ti = 0; ti < q.mt; ++ti)
           for (int tj = 0; tj < q.nt && ((q.flags & G_CLOWER) == 0 || tj <= ti); ++tj)
-            out.push_back(((unsigned)pi << 24) | ((unsigned)ti << 12) | (unsigned)tj);
+            out.push_back(tile_code(pi, ti, tj));
       };
       std::vector<unsigned> early, bulkc;
       std::vector<std::vector<unsigned>> seg(W1);
@@ -1186,7 +962,6 @@ int build_plan(gpe_ctx* c, Fact& F) {
       // before the column updates they wait on: the positions do not decrease with h, so
       // the steps stay in order even where they clamp
       std::vector<unsigned> order;
-      order.reserve(base.size() + tiles_total_hint(seg));
       auto pos = [&](int h) {
         size_t at = (size_t)c->grp_p0 + (size_t)h * c->grp_stride;
         at = std::max(at, h >= 1 ? head + early.size() : head);   // after the step's diagonal tile
@@ -1217,24 +992,10 @@ int build_plan(gpe_ctx* c, Fact& F) {
       }
       // every tile may wait only on tiles before it in the list (the dispatch order):
       // then the earliest unfinished tile can always run.  Checked, not assumed.
-      {
-        std::map<const int*, size_t> last_post, diag_at;
-        for (size_t i = 0; i < order.size(); ++i) {
-          const GemmProb& q = fp[order[i] >> 24];
-          if (q.post) last_post[q.post] = i;
-          if (q.cpost) last_post[q.cpost] = i;
-          if (q.flags & G_DIAG) diag_at[q.flag] = i;
-        }
-        for (size_t i = 0; i < order.size(); ++i) {
-          const GemmProb& q = fp[order[i] >> 24];
-          const bool ok = (!q.pre0 || (last_post.count(q.pre0) && last_post[q.pre0] < i)) &&
-                          (!q.pre1 || (last_post.count(q.pre1) && last_post[q.pre1] < i)) &&
-                          (!(q.flags & G_PANEL) || (diag_at.count(q.flag) && diag_at[q.flag] < i));
-          if (!ok) return fail(c, GPE_ERR_HIP, "internal error: group schedule waits on a later tile");
-        }
-      }
+      if (!waits_point_back(fp.data(), order))
+        return fail(c, GPE_ERR_HIP, "internal error: group schedule waits on a later tile");
       gidx[o + gb] = (int)pl.launches.size();
-      add_launch_list(pl, 4, fp, fl, order);
+      add_launch(pl, GEMM_FUSED, fp, fl, &order);
       pl.launches.back().ticket = flags0 + 3 * NB + gb;
     }
   }
@@ -1265,9 +1026,9 @@ int build_plan(gpe_ctx* c, Fact& F) {
     split_k(pa, F.part, F.tcnt);
     split_k(pb, F.part, F.tcnt);
     pl.trtri.push_back((int)pl.launches.size());
-    add_launch(pl, 1, pa, fa);
+    add_launch(pl, GEMM_AK, pa, fa);
     pl.trtri.push_back((int)pl.launches.size());
-    add_launch(pl, 0, pb, fb);
+    add_launch(pl, GEMM_PLAIN, pb, fb);
   }
   // --- A^-1 = X^T X (lower tiles), written over L in A
   pl.lauum = (int)pl.launches.size();
@@ -1275,7 +1036,7 @@ int build_plan(gpe_ctx* c, Fact& F) {
     const double N = (double)F.n_pad;
     std::vector<GemmProb> lp = {mkprob(B, ld, B, ld, A, ld, NB, NB, (int)F.n_pad, G_CLOWER | G_KBEG_TI, 1.0, 0.0)};
     split_k(lp, F.part, F.tcnt);
-    add_launch(pl, 2, lp, N * N * N / 3.0);
+    add_launch(pl, GEMM_AK_BK, lp, N * N * N / 3.0);
   }
   const int limit = (F.desc_base == 0) ? AUX_DESC_BASE : ADHOC_DESC_BASE - AUX_DESC_BASE;
   // --- the split sweep of the training matrix (potrf with split): columns [0, h), the Schur
@@ -1295,7 +1056,7 @@ int build_plan(gpe_ctx* c, Fact& F) {
     CHK(sweep(h, NB - h, NB - h, ix));
     if (pl.aug) {
       pl.aug_mid = (int)pl.launches.size();
-      add_launch(pl, 0, {mkprob(F.Faug, TILE, tile(A, h, 0), ld, F.Faug + (long long)h * TILE * TILE, TILE, 1, NB - h,
+      add_launch(pl, GEMM_PLAIN, {mkprob(F.Faug, TILE, tile(A, h, 0), ld, F.Faug + (long long)h * TILE * TILE, TILE, 1, NB - h,
                                 h * TILE, 0, -1.0, 1.0)}, 0.0);
     }
     pl.split_h = h;
@@ -3222,7 +2983,7 @@ struct Posterior : PostReq {
     if (ozp) return posterior_oz(c, f32, c->dW1, mp, vdst);
     if (!f32)
       return adhoc_gemm(c, ADHOC_POST_V,
-                        {{3, mkprob(c->tr.B, np, c->dW1, np, vdst, np, c->NB, mt, (int)np, G_KEND_TI, 1.0, 0.0)}});
+                        {{GEMM_BK, mkprob(c->tr.B, np, c->dW1, np, vdst, np, c->NB, mt, (int)np, G_KEND_TI, 1.0, 0.0)}});
     CHK(grow_buf(c, &c->dK32, &c->k32_cap, 2 * (size_t)np * mp));
     float *K32 = c->dK32, *V32 = c->dK32 + (size_t)np * mp;
     hipLaunchKernelGGL(k_to_f32, dim3((unsigned)((np * mp + 255) / 256)), dim3(256), 0, c->stream, c->dW1, np,
@@ -3303,8 +3064,8 @@ struct Posterior : PostReq {
                          (int)mc, q, kq, g.Hs, g.Qinv, g.tau);
       HIPCHK(c, hipGetLastError());
       CHK(adhoc_gemm(c, ADHOC_POST_U,
-                     {{2, mkprob(c->tr.B, np, c->dW2, np, c->dW3, np, c->NB, mt, (int)np, G_KBEG_TI, 1.0, 0.0)},
-                      {0, mkprob(g.Gq, np, g.tau, mp, c->dW3, np, c->NB, mt, kq, 0, 1.0, 1.0)}}));
+                     {{GEMM_AK_BK, mkprob(c->tr.B, np, c->dW2, np, c->dW3, np, c->NB, mt, (int)np, G_KBEG_TI, 1.0, 0.0)},
+                      {GEMM_PLAIN, mkprob(g.Gq, np, g.tau, mp, c->dW3, np, c->NB, mt, kq, 0, 1.0, 1.0)}}));
     }
     PostGradArgs a;
     a.xw = c->dXw; a.xsw = c->dXsw; a.gam = c->dWa; a.U = wb ? c->dW3 : nullptr; a.ldu = np;
@@ -3430,8 +3191,8 @@ struct Posterior : PostReq {
     CHK(launch_pairs(c, a, dg ? mt * (mt + 1) / 2 : mt * nt));
     if (t_stage)
       HIPCHK(c, hipMemcpyAsync(R.T, c->hpin, t_stage * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    return adhoc_gemm(c, ADHOC_COV, {{2, mkprob(R.V, np, C.V, np, dst, ld, mt, nt, (int)np, 0, -s2, 1.0)},
-                                     {0, mkprob(R.T, R.ldt, C.T, C.ldt, dst, ld, mt, nt, kq, 0, s2, 1.0)}});
+    return adhoc_gemm(c, ADHOC_COV, {{GEMM_AK_BK, mkprob(R.V, np, C.V, np, dst, ld, mt, nt, (int)np, 0, -s2, 1.0)},
+                                     {GEMM_PLAIN, mkprob(R.T, R.ldt, C.T, C.ldt, dst, ld, mt, nt, kq, 0, s2, 1.0)}});
   }
 
   // Full variance.  One chunk: its block in dW3, copied out unless it stays there.  More:
@@ -3737,7 +3498,7 @@ int gpe_noise_sample(gpe_ctx* c, int64_t m, const double* Xs, const double* Hs, 
   for (long long i = 0; i < m; ++i) c->hpin[i] = t[i] - mean_out[i];
   HIPCHK(c, hipMemcpyAsync(dE, c->hpin, (size_t)mp * sizeof(double), hipMemcpyHostToDevice, c->stream));
   // Y = L U^T: the s draws L.dot(u) of noise_fit.py:135-136 as one MFMA GEMM
-  CHK(adhoc_gemm(c, ADHOC_NOISE, {{3, mkprob(F.A, mp, dU, mp, dY, mp, mt, st, (int)mp, G_KEND_TI, 1.0, 0.0)}}));
+  CHK(adhoc_gemm(c, ADHOC_NOISE, {{GEMM_BK, mkprob(F.A, mp, dU, mp, dY, mp, mt, st, (int)mp, G_KEND_TI, 1.0, 0.0)}}));
   // z_i = sum_j 0.5 (e_i - Y_ij)^2  (noise_fit.py:137)
   hipLaunchKernelGGL(k_noise_sq, dim3((unsigned)(mp / 256 + 1)), dim3(256), 0, c->stream, dY, mp, s, dE,
                      (int)m, dZs);
@@ -3797,9 +3558,9 @@ int gpe_posterior_pivchol(gpe_ctx* c, int64_t m, const double* Xs, const double*
   a.tol = tol;
   static_assert(sizeof(PcState) == 2 * sizeof(double), "PcState");
   // the trailing update's descriptor: S -= W W^T, every tile, K = PC_PANEL (the same for every panel)
-  Launch Lt{};
+  GemmLaunch Lt{};
   if (k > PC_PANEL) {
-    CHK(adhoc_gemm(c, ADHOC_PIVCHOL, {{0, mkprob(W, mp, W, mp, c->dW3, mp, mt, mt, PC_PANEL, 0, -1.0, 1.0)}}, &Lt));
+    CHK(adhoc_gemm(c, ADHOC_PIVCHOL, {{GEMM_PLAIN, mkprob(W, mp, W, mp, c->dW3, mp, mt, mt, PC_PANEL, 0, -1.0, 1.0)}}, &Lt));
     Lt.flops = 2.0 * (double)mp * (double)mp * PC_PANEL;
   }
   hipLaunchKernelGGL(k_pc_init, dim3(G), dim3(PC_ROWS), 0, c->stream, a, (int)k);
@@ -4180,8 +3941,8 @@ int gpe_test_gemm(gpe_ctx* c, int32_t trans_a, int32_t trans_b, int64_t M, int64
     copy_checked(c, rc, db, hb.data(), hb.size() * sizeof(double), hipMemcpyHostToDevice);
     copy_checked(c, rc, dc, hc.data(), hc.size() * sizeof(double), hipMemcpyHostToDevice);
     const GemmProb p = mkprob(da, lda, db, ldb, dc, M, (int)(M / TILE), (int)(N / TILE), (int)K, 0, alpha, beta);
-    const int kind = trans_a ? (trans_b ? 2 : 1) : (trans_b ? 3 : 0);
-    Launch L{};
+    const GemmKind kind = gemm_kind(trans_a != 0, trans_b != 0);
+    GemmLaunch L{};
     if (rc == GPE_OK) rc = adhoc_gemm(c, ADHOC_TEST, {{kind, p}}, &L, true);
     HIPCHK(c, hipMemsetAsync(c->dinfo, 0, sizeof(int), c->stream));
     if (rc == GPE_OK) rc = launch_gemm_range(c, L);
@@ -4396,11 +4157,12 @@ static int gemm_group_test(gpe_ctx* c, int nbuf, double* const* bufs, const int6
   if (nbuf < 1 || nbuf > 64 || nprob < 1 || nprob > 1024) return bad("1 to 64 buffers, 1 to 1024 problems");
   for (int i = 0; i < nbuf; ++i)
     if (!bufs[i] || lens[i] < 1) return bad("NULL or empty buffer " + std::to_string(i));
-  if (gl.kind < 0 || gl.kind > 3 || (gl.split & ~1) || (gl.listed & ~1) || gl.reps < 1 || gl.reps > 16)
+  if (gl.kind < GEMM_PLAIN || gl.kind > GEMM_BK || (gl.split & ~1) || (gl.listed & ~1) || gl.reps < 1 || gl.reps > 16)
     return bad("kind 0..3, split 0 / 1, listed 0 / 1, reps 1..16");
   if (gl.listed && nprob >= 256) return bad("a tile list names at most 255 problems");
   if (tiles_cap < 0 || (tiles_cap > 0 && !tiles_out)) return bad("tiles_out is NULL");
-  const bool AK = gl.kind == 1 || gl.kind == 2, BK = gl.kind == 2 || gl.kind == 3;
+  const GemmKind kind = (GemmKind)gl.kind;
+  const bool AK = gemm_instance(kind).ak, BK = gemm_instance(kind).bk;
   long long total = 0;
   std::vector<char> holds_c(nbuf, 0);
   for (int p = 0; p < nprob; ++p) {
@@ -4466,8 +4228,8 @@ static int gemm_group_test(gpe_ctx* c, int nbuf, double* const* bufs, const int6
     split_k(probs, d.part, d.tcnt);
   }
   Plan pl;
-  add_launch(pl, gl.kind, probs, 0.0);
-  Launch L = pl.launches[0];
+  add_launch(pl, kind, probs, 0.0);
+  GemmLaunch L = pl.launches[0];
   if (!gl.listed) L.list = -1;
   if (L.list >= 0 && (long long)pl.tiles.size() > tiles_cap) return bad("the tile list does not fit tiles_cap");
   CHK(dalloc(c, &d.probs, pl.probs.size()));
@@ -4534,8 +4296,8 @@ int gpe_bench_gemm(gpe_ctx* c, int32_t trans_a, int32_t trans_b, int32_t mt, int
     // resident, every k still reads other values, so the MFMA inputs toggle as when cold)
     if (const char* hot = std::getenv("GPEMU_BENCH_HOT")) lda = ldb = (std::atoi(hot) == 2) ? TILE : 0;
     const GemmProb p = mkprob(da, lda, db, ldb, dc, M, mt, nt, K, lower ? G_CLOWER : 0, -1.0, beta);
-    const int kind = trans_a ? (trans_b ? 2 : 1) : (trans_b ? 3 : 0);
-    Launch L{};
+    const GemmKind kind = gemm_kind(trans_a != 0, trans_b != 0);
+    GemmLaunch L{};
     rc = adhoc_gemm(c, ADHOC_BENCH, {{kind, p}}, &L, true);
     HIPCHK(c, hipMemsetAsync(c->dinfo, 0, sizeof(int), c->stream));
     const bool prof = c->prof;

@@ -55,6 +55,7 @@
 #include "../../include/gpemu.h"
 #include "../../include/gpemu_dist.h"
 #include "gpemu_kernels.hpp"
+#include "gpemu_gemm_sched.hpp"
 #include "gpemu_small.hpp"
 #include "gpemu_ozaki.hpp"
 
@@ -326,19 +327,9 @@ struct Rank {              // one rank's buffers (one per process over RCCL, P i
   size_t bytes = 0;        // device bytes held for this rank
 };
 
-struct DLaunch {           // one grouped k_gemm launch
-  int first = 0, count = 0, tiles = 0;
-  long long list = -1;
-  int kind = 0;            // 0 <false,false> (the fused instance: G_DIAG problems), 1 <false,true>,
-                           // 2 <true,true>, 3 <true,false>, 4 <false,false> (plain)
-  bool cdef = false;       // k_gemm's CDEF instance (gemm_cdef of some problem)
-  int* ticket = nullptr;   // FUSED launches with in-launch waits: list positions by atomic
-                           // ticket (k_gemm), so progress never depends on dispatch order
-};
-
 // one column chunk of one level of the recursive TRTRI (see ensure_grad)
 struct TriChunk {
-  DLaunch m, x;            // M^T = X11^T L21^T ; X21 = -X22 M
+  GemmLaunch m, x;            // M^T = X11^T L21^T ; X21 = -X22 M
   int pack0 = 0, npack = 0, pack_tiles = 0;   // P > 1: move descriptors and their tiles
   int unp1 = 0, nunp1 = 0, unp1_tiles = 0;
   int unp2 = 0, nunp2 = 0, unp2_tiles = 0;
@@ -348,7 +339,7 @@ struct TriChunk {
 };
 
 struct SlabLaunch {        // one slab of a rank's partial of A^-1: GEMM + contraction
-  DLaunch gemm;
+  GemmLaunch gemm;
   int a0 = 0, a1 = 0;      // tile rows [a0, a1)
 };
 
@@ -410,7 +401,7 @@ struct gpe_dist {
   int* dcnt = nullptr;       // [NB][P] panel tiles of rank r at step k
   GemmProb* dprobs = nullptr;
   unsigned* dtiles = nullptr;
-  std::vector<DLaunch> diag, mrow, panel_l, upd_next, upd_near, upd_far;   // per step (updates: group ends)
+  std::vector<GemmLaunch> diag, mrow, panel_l, upd_next, upd_near, upd_far;   // per step (updates: group ends)
   std::vector<int> maxT;                       // per step: max panel tiles over ranks
   size_t recv_tiles = 0;                       // P > 1: tiles per rank segment of the group all-gather
   double* hpin = nullptr;
@@ -429,7 +420,7 @@ struct gpe_dist {
   double* wsplit = nullptr;                    // split-K partials of the W launch
   int* wcnt = nullptr;                         // its per-tile arrival counters
   unsigned* gtiles = nullptr;                  // tile lists of the gradient launches
-  std::vector<DLaunch> wa_l;
+  std::vector<GemmLaunch> wa_l;
   std::vector<TriChunk> tri;                   // the recursive TRTRI, level by level
   MoveDesc* dmoves = nullptr;
   std::vector<std::vector<SlabLaunch>> slabs;  // per local rank
@@ -518,18 +509,6 @@ int pinned(gpe_dist* h, size_t doubles) {
   DCHK_HIP(h, hipHostMalloc((void**)&h->hpin, cap * sizeof(double), hipHostMallocDefault));
   h->hpin_cap = cap;
   return GPE_OK;
-}
-
-GemmProb dprob(const double* A, long long lda, const double* B, long long ldb, double* C, long long ldc,
-               int mt, int nt, int K, int flags, double alpha, double beta) {
-  GemmProb p;
-  std::memset(&p, 0, sizeof(p));
-  p.A = A; p.B = B; p.C = C;
-  p.lda = lda; p.ldb = ldb; p.ldc = ldc;
-  p.mt = mt; p.nt = nt; p.K = K; p.flags = flags;
-  p.alpha = alpha; p.beta = beta;
-  p.kti_mul = 1;
-  return p;
 }
 
 Rank* rank_slot(gpe_dist* h, int r) {   // the local slot of rank r, or null (another process)
@@ -672,62 +651,6 @@ double* panel_of(const gpe_dist* h, const Rank& R, int k) {
   return R.panel + (size_t)(h->gid[k] & 1) * h->panel_sz;
 }
 
-// XCD-aware order of a launch's tiles (as gpemu.hip order_tiles): rows (problem, ti) -- one
-// A panel each -- longest tiles first, greedily packed into 8 bins of equal work, the bins
-// interleaved tile by tile.  Under round-robin dispatch each row's tiles then run on one
-// XCD and its A panel stays in that XCD's L2: in implicit order (ti fastest) every XCD
-// streams every panel, and a K = 8192 TRTRI level ran 2.7x over its MFMA time.
-std::vector<unsigned> xcd_order(const GemmProb* probs, const std::vector<unsigned>& tiles) {
-  struct Row { double w = 0.0, tw = 0.0; std::vector<unsigned> t; };
-  std::map<std::pair<int, int>, Row> rows;
-  for (unsigned code : tiles) {
-    const int p = (int)(code >> 24), ti = (int)((code >> 12) & 0xfff);
-    const GemmProb& P = probs[p];
-    int kb = 0, ke = P.K;
-    if (P.flags & G_KBEG_TI) kb = ti * TILE;
-    if (P.flags & G_KEND_TI) ke = std::min(ke, (ti * P.kti_mul + P.kti_off + 1) * TILE);
-    Row& r = rows[{p, ti}];
-    r.tw = (double)std::max(ke - kb, 0) + 2.0 * GK;   // + fixed per-tile cost
-    r.w += r.tw;
-    r.t.push_back(code);
-  }
-  std::vector<const Row*> order;
-  for (const auto& kv : rows) order.push_back(&kv.second);
-  std::stable_sort(order.begin(), order.end(), [](const Row* a, const Row* b) { return a->tw > b->tw; });
-  constexpr int NX = 8;
-  std::vector<std::vector<unsigned>> bins(NX);
-  std::vector<double> load(NX, 0.0);
-  for (const Row* r : order) {
-    const int x = (int)(std::min_element(load.begin(), load.end()) - load.begin());
-    load[x] += r->w;
-    bins[x].insert(bins[x].end(), r->t.begin(), r->t.end());
-  }
-  std::vector<unsigned> out;
-  size_t longest = 0;
-  for (auto& b : bins) longest = std::max(longest, b.size());
-  for (size_t j = 0; j < longest; ++j)
-    for (int x = 0; x < NX; ++x)
-      if (j < bins[x].size()) out.push_back(bins[x][j]);
-  return out;
-}
-
-// every tile of a plain launch's problems, XCD-ordered, appended to tiles as L's list
-// (launches of more than 256 problems, which the list code cannot name, keep the
-// implicit order)
-void list_launch(DLaunch& L, const std::vector<GemmProb>& probs, std::vector<unsigned>& tiles) {
-  if (L.count == 0 || L.count > 256) return;
-  std::vector<unsigned> all;
-  for (int p = 0; p < L.count; ++p) {
-    const GemmProb& P = probs[L.first + p];
-    for (int tj = 0; tj < P.nt; ++tj)
-      for (int ti = 0; ti < P.mt; ++ti)
-        if (!(P.flags & G_CLOWER) || tj <= ti) all.push_back(((unsigned)p << 24) | ((unsigned)ti << 12) | (unsigned)tj);
-  }
-  const std::vector<unsigned> ord = xcd_order(probs.data() + L.first, all);
-  L.list = (long long)tiles.size();
-  tiles.insert(tiles.end(), ord.begin(), ord.end());
-}
-
 // P = 1 (round-6 verdict item 4): the first step of each group after the first is started
 // inside the update launch before it (the previous group's update of the group's columns, A),
 // on tile counts, as the single-GPU fused sweep does: that launch's tiles of column ge count
@@ -742,13 +665,11 @@ int fuse_next_factor(gpe_dist* h, std::vector<GemmProb>& probs, std::vector<unsi
   for (int k = 0; k + 1 < NB; ++k) {
     const int ge = k + 1;
     if (group_end(h, k) != ge) continue;
-    DLaunch& ul = h->upd_next[k];
-    DLaunch& dl = h->diag[ge];
+    GemmLaunch& ul = h->upd_next[k];
+    GemmLaunch& dl = h->diag[ge];
     if (ul.count != 1 || ul.tiles == 0 || ul.list < 0 || dl.count == 0 || dl.list >= 0) continue;
     int* cnt = h->dq + 5 * NB + ge;
-    DLaunch f;
-    f.kind = 0;
-    f.first = (int)probs.size();
+    GemmLaunch f = begin_launch(GEMM_FUSED, probs);
     GemmProb pc = probs[ul.first], pr = probs[ul.first];
     pc.post = cnt;
     std::vector<unsigned> col, rest;
@@ -757,8 +678,8 @@ int fuse_next_factor(gpe_dist* h, std::vector<GemmProb>& probs, std::vector<unsi
       (tj == (unsigned)ge ? col : rest).push_back((tj == (unsigned)ge ? 0u : 1u << 24) | (code & 0xffffffu));
     }
     if (col.empty()) continue;
-    probs.push_back(pc);
-    probs.push_back(pr);
+    push_prob(f, probs, pc, true);
+    push_prob(f, probs, pr, true);
     std::vector<unsigned> fac, halves;
     for (int p = 0; p < dl.count; ++p) {
       GemmProb q = probs[dl.first + p];
@@ -770,37 +691,19 @@ int fuse_next_factor(gpe_dist* h, std::vector<GemmProb>& probs, std::vector<unsi
       const unsigned pi = (unsigned)(2 + p);
       for (int ti = 0; ti < q.mt; ++ti)
         ((q.flags & G_DIAG) ? fac : halves).push_back((pi << 24) | ((unsigned)ti << 12));
-      f.cdef = f.cdef || gemm_cdef(q);
-      probs.push_back(q);
+      push_prob(f, probs, q, true);
     }
-    f.count = 2 + dl.count;
-    f.cdef = f.cdef || gemm_cdef(pc);
     std::vector<unsigned> order = col;
     order.insert(order.end(), fac.begin(), fac.end());
     order.insert(order.end(), rest.begin(), rest.end());
     order.insert(order.end(), halves.begin(), halves.end());
-    {   // every wait on an earlier position (counts complete before the waiter's slot)
-      std::map<const int*, size_t> last_post;
-      size_t diag_at = order.size();
-      for (size_t i = 0; i < order.size(); ++i) {
-        const GemmProb& q = probs[f.first + (order[i] >> 24)];
-        if (q.post) last_post[q.post] = i;
-        if (q.cpost) last_post[q.cpost] = i;
-        if (q.flags & G_DIAG) diag_at = i;
-      }
-      for (size_t i = 0; i < order.size(); ++i) {
-        const GemmProb& q = probs[f.first + (order[i] >> 24)];
-        const bool ok = (!q.pre0 || (last_post.count(q.pre0) && last_post[q.pre0] < i)) &&
-                        (!(q.flags & G_PANEL) || diag_at < i);
-        if (!ok) return dfail(h, GPE_ERR_STATE, "internal error: fused launch waits on a later tile");
-      }
-    }
-    f.list = (long long)tiles.size();
-    tiles.insert(tiles.end(), order.begin(), order.end());
-    f.tiles = (int)order.size();
+    // every wait on an earlier position (counts complete before the waiter's slot)
+    if (!waits_point_back(probs.data() + f.first, order))
+      return dfail(h, GPE_ERR_STATE, "internal error: fused launch waits on a later tile");
+    set_list(f, tiles, order);
     f.ticket = h->dq + 4 * NB + k;
     ul = f;
-    dl = DLaunch();   // (step ge launches nothing for its factor)
+    dl = GemmLaunch();   // (step ge launches nothing for its factor)
   }
   return GPE_OK;
 }
@@ -811,12 +714,12 @@ int build_schedule(gpe_dist* h) {
   const long long ldp = (long long)NT * TILE;
   std::vector<GemmProb> probs;
   std::vector<unsigned> tiles;
-  h->diag.assign(NB, DLaunch());
-  h->mrow.assign(NB, DLaunch());
-  h->panel_l.assign(NB, DLaunch());
-  h->upd_next.assign(NB, DLaunch());
-  h->upd_near.assign(NB, DLaunch());
-  h->upd_far.assign(NB, DLaunch());
+  h->diag.assign(NB, GemmLaunch());
+  h->mrow.assign(NB, GemmLaunch());
+  h->panel_l.assign(NB, GemmLaunch());
+  h->upd_next.assign(NB, GemmLaunch());
+  h->upd_near.assign(NB, GemmLaunch());
+  h->upd_far.assign(NB, GemmLaunch());
   h->maxT.assign(NB, 0);
   std::vector<int> li0((size_t)NB * P), cnt((size_t)NB * P);
   for (int k = 0; k < NB; ++k) {
@@ -831,24 +734,19 @@ int build_schedule(gpe_dist* h) {
     // L(k, gb:k) L(k, gb:k)^T from its own row; then factored and inverted into its Dinv
     // (the Dinv block of the step's broadcast block)
     const bool gath = gather_panels(h);
-    DLaunch dl;
-    dl.first = (int)probs.size();
+    GemmLaunch dl = begin_launch(GEMM_FUSED, probs);
     if (Rank* R = rank_slot(h, k % P)) {
       double* Ckk = R->A + (long long)(k / P) * TILE + (long long)k * TILE * R->ld;
       const double* Lk = R->A + (long long)(k / P) * TILE + (long long)gb * TILE * R->ld;
       // the pending update as DQ_N 32 x 32-block workgroups (as the single-GPU sweep), which
       // the G_DIAG workgroup waits for (they precede it in the launch)
       if (Kp > 0) {
-        GemmProb q = dprob(Lk, R->ld, nullptr, 0, Ckk, R->ld, DQ_N, 1, Kp, G_DQUAD, -1.0, 1.0);
+        GemmProb q = mkprob(Lk, R->ld, nullptr, 0, Ckk, R->ld, DQ_N, 1, Kp, G_DQUAD, -1.0, 1.0);
         q.post = h->dq + k;
         q.diag_col0 = k * TILE;
-        q.tile_begin = dl.tiles;
-        q.ntiles = DQ_N;
-        dl.tiles += DQ_N;
-        probs.push_back(q);
-        ++dl.count;
+        push_prob(dl, probs, q, false);
       }
-      GemmProb p = dprob(nullptr, R->ld, nullptr, R->ld, Ckk, R->ld, 1, 1, 0, G_DIAG, 1.0, 1.0);
+      GemmProb p = mkprob(nullptr, R->ld, nullptr, R->ld, Ckk, R->ld, 1, 1, 0, G_DIAG, 1.0, 1.0);
       if (Kp > 0) {
         p.pre0 = h->dq + k;
         p.pre0_n = DQ_N;
@@ -860,12 +758,7 @@ int build_schedule(gpe_dist* h) {
       // P = 1: the factor releases this launch's panel tiles through a flag once L and
       // the leaf inverses are stored (X is assembled after the sweep, k_xasm)
       if (!gath) p.flag = h->dq + NB + k;
-      p.tile_begin = dl.tiles;
-      p.ntiles = 1;
-      dl.tiles += 1;
-      dl.cdef = dl.cdef || gemm_cdef(p);
-      probs.push_back(p);
-      ++dl.count;
+      push_prob(dl, probs, p, true);
     }
     // P = 1 (the rank holds every row): the panel tiles ride in the same launch, as the
     // single-GPU fused sweep's: each G_PHALF0 workgroup applies the pending update
@@ -879,10 +772,10 @@ int build_schedule(gpe_dist* h) {
       const int a = li0_of(k, P, R.rank), c = std::max(0, R.nloc - a);
       if (c > 0) {
         double* Ckk = R.A + (long long)k * TILE + (long long)k * TILE * R.ld;
-        GemmProb q = dprob(Kp ? R.A + (long long)a * TILE + (long long)gb * TILE * R.ld : nullptr, R.ld,
-                           Kp ? R.A + (long long)k * TILE + (long long)gb * TILE * R.ld : nullptr, R.ld,
-                           R.A + (long long)a * TILE + (long long)k * TILE * R.ld, R.ld, c, 1, Kp,
-                           G_PANEL | G_PHALF0, Kp ? -1.0 : 1.0, 1.0);
+        GemmProb q = mkprob(Kp ? R.A + (long long)a * TILE + (long long)gb * TILE * R.ld : nullptr, R.ld,
+                            Kp ? R.A + (long long)k * TILE + (long long)gb * TILE * R.ld : nullptr, R.ld,
+                            R.A + (long long)a * TILE + (long long)k * TILE * R.ld, R.ld, c, 1, Kp,
+                            G_PANEL | G_PHALF0, Kp ? -1.0 : 1.0, 1.0);
         q.cpost = h->dq + 2 * NB + k;
         q.X = R.dinv + (long long)k * TILE * TILE;
         q.ldx = TILE;
@@ -890,12 +783,7 @@ int build_schedule(gpe_dist* h) {
         q.diag_col0 = -TILE;   // (no GEMM_TRACE slot)
         q.Ld = Ckk;
         q.ldd = R.ld;
-        q.tile_begin = dl.tiles;
-        q.ntiles = c;
-        dl.tiles += c;
-        dl.cdef = dl.cdef || gemm_cdef(q);
-        probs.push_back(q);
-        ++dl.count;
+        push_prob(dl, probs, q, true);
         GemmProb q1 = q;
         q1.flags = G_PANEL | G_PHALF1;
         q1.A = q1.B = nullptr;
@@ -905,10 +793,7 @@ int build_schedule(gpe_dist* h) {
         q1.pre0 = q.cpost;
         q1.pre0_n = c;
         q1.cpost = nullptr;
-        q1.tile_begin = dl.tiles;
-        dl.tiles += c;
-        probs.push_back(q1);
-        ++dl.count;
+        push_prob(dl, probs, q1, false);
       }
     }
     // in-launch waits (quadrants -> factor, factor -> panel halves, halves -> halves): the
@@ -918,39 +803,28 @@ int build_schedule(gpe_dist* h) {
     // P > 1, Kp > 0: the owner's M block of the broadcast, -Dinv L(k, gb:k) (its own row)
     if (gath && Kp > 0)
       if (Rank* R = rank_slot(h, k % P)) {
-        DLaunch ml;
-        ml.first = (int)probs.size();
-        GemmProb p = dprob(R->dinv + (long long)Kp * TILE, TILE,
-                           R->A + (long long)(k / P) * TILE + (long long)gb * TILE * R->ld, R->ld, R->dinv, TILE,
-                           1, Kp / TILE, TILE, 0, -1.0, 0.0);
-        p.tile_begin = 0;
-        p.ntiles = Kp / TILE;
-        ml.tiles = p.ntiles;
-        ml.count = 1;
-        ml.kind = 1;
-        probs.push_back(p);
+        GemmLaunch ml = begin_launch(GEMM_BK, probs);
+        push_prob(ml, probs,
+                  mkprob(R->dinv + (long long)Kp * TILE, TILE,
+                         R->A + (long long)(k / P) * TILE + (long long)gb * TILE * R->ld, R->ld, R->dinv, TILE,
+                         1, Kp / TILE, TILE, 0, -1.0, 0.0),
+                  false);
         h->mrow[k] = ml;
       }
     // panel over each local rank's rows i > k: P = 1, L(i,k) = A(i,k) Dinv^T (pending update
     // applied in the diagonal launch); P > 1, L(i,k) = [L(i, gb:k) A(i,k)] [-M Dinv]^T =
     // (A(i,k) - L(i, gb:k) L(k, gb:k)^T) Dinv^T, one product with K = Kp + 128 over the
     // row's columns gb..k (in place: each tile reads only its own rows before storing)
-    DLaunch pl;
-    pl.first = (int)probs.size();
+    GemmLaunch pl = begin_launch(GEMM_PLAIN, probs);
     for (Rank& R : h->ranks) {
       const int a = li0_of(k, P, R.rank), c = std::max(0, R.nloc - a);
       if (c == 0 || !gath) continue;
       double* Aik = R.A + (long long)a * TILE + (long long)k * TILE * R.ld;
-      GemmProb p = gath ? dprob(R.A + (long long)a * TILE + (long long)gb * TILE * R.ld, R.ld, R.dinv, TILE, Aik,
-                                R.ld, c, 1, Kp + TILE, 0, 1.0, 0.0)
-                        : dprob(Aik, R.ld, R.dinv + (long long)Kp * TILE, TILE, Aik, R.ld, c, 1, TILE, 0, 1.0, 0.0);
-      p.tile_begin = pl.tiles;
-      p.ntiles = c;
-      pl.tiles += c;
-      probs.push_back(p);
-      ++pl.count;
+      push_prob(pl, probs,
+                mkprob(R.A + (long long)a * TILE + (long long)gb * TILE * R.ld, R.ld, R.dinv, TILE, Aik, R.ld, c, 1,
+                       Kp + TILE, 0, 1.0, 0.0),
+                false);
     }
-    pl.kind = 4;
     h->panel_l[k] = pl;
     // the step closing a group: trailing update of each local rank's rows by the
     // whole group, columns ge <= j <= i, K = 128 (ge - gb), in three launches: the next
@@ -961,33 +835,21 @@ int build_schedule(gpe_dist* h) {
     const int ge3 = ge2 < NB ? next_group_end(h, ge2 - 1) : NB;
     for (int part = 0; part < 3; ++part) {
       const int j0 = part == 0 ? ge : (part == 1 ? ge2 : ge3), j1 = part == 0 ? ge2 : (part == 1 ? ge3 : NT);
-      DLaunch ul;
-      ul.first = (int)probs.size();
-      ul.list = (long long)tiles.size();
-      int pi = 0;
+      GemmLaunch ul = begin_launch(GEMM_PLAIN, probs);
+      std::vector<unsigned> mine;   // (at most 256 problems: one per local rank)
       for (Rank& R : h->ranks) {
         const int a = li0_of(k, P, R.rank);
         if (a >= R.nloc) continue;
-        GemmProb p = dprob(R.A + (long long)gb * TILE * R.ld, R.ld, panel_of(h, R, k), ldp, R.A, R.ld,
-                           R.nloc, NT, (ge - gb) * TILE, 0, -1.0, 1.0);
+        GemmProb p = mkprob(R.A + (long long)gb * TILE * R.ld, R.ld, panel_of(h, R, k), ldp, R.A, R.ld,
+                            R.nloc, NT, (ge - gb) * TILE, 0, -1.0, 1.0);
         for (int li = a; li < R.nloc; ++li) {
           const int gt = li * P + R.rank;
           for (int j = j0; j < j1 && j <= gt; ++j)
-            tiles.push_back(((unsigned)pi << 24) | ((unsigned)li << 12) | (unsigned)j);
+            mine.push_back(tile_code(ul.count, li, j));
         }
-        ul.cdef = ul.cdef || gemm_cdef(p);
-        probs.push_back(p);
-        ++pi;
-        ++ul.count;
+        push_prob(ul, probs, p, true);
       }
-      ul.tiles = (int)(tiles.size() - ul.list);
-      if (ul.tiles == 0) ul.count = 0;
-      if (ul.tiles > 0) {   // (at most 256 problems: one per local rank)
-        const std::vector<unsigned> mine(tiles.begin() + ul.list, tiles.end());
-        const std::vector<unsigned> ord = xcd_order(probs.data() + ul.first, mine);
-        std::copy(ord.begin(), ord.end(), tiles.begin() + ul.list);
-      }
-      ul.kind = 4;
+      set_list(ul, tiles, xcd_order(probs.data() + ul.first, mine));   // (no tile: nothing is launched)
       (part == 0 ? h->upd_next : (part == 1 ? h->upd_near : h->upd_far))[k] = ul;
     }
   }
@@ -1006,33 +868,8 @@ int build_schedule(gpe_dist* h) {
 }
 
 // the sweep's launches (dprobs / dtiles), or the gradient's (gprobs / gtiles) with grad
-int launch(gpe_dist* h, const DLaunch& L, bool grad = false) {
-  if (L.count == 0 || L.tiles == 0) return GPE_OK;
-  const size_t lds = G_LDS_LAUNCH_DOUBLES * sizeof(double);
-  const unsigned* tl = L.list >= 0 ? (grad ? h->gtiles : h->dtiles) + L.list : nullptr;
-  const GemmProb* pr = (grad ? h->gprobs : h->dprobs) + L.first;
-  const dim3 g(L.tiles);
-  const dim3 b(256);
-  if (L.cdef) {
-    switch (L.kind) {
-      case 1: hipLaunchKernelGGL((k_gemm<false, true, false, true>), g, b, lds, h->cs, pr, L.count, tl, h->dinfo, nullptr); break;
-      case 2: hipLaunchKernelGGL((k_gemm<true, true, false, true>), g, b, lds, h->cs, pr, L.count, tl, h->dinfo, nullptr); break;
-      case 3: hipLaunchKernelGGL((k_gemm<true, false, false, true>), g, b, lds, h->cs, pr, L.count, tl, h->dinfo, nullptr); break;
-      case 4: hipLaunchKernelGGL((k_gemm<false, false, false, true>), g, b, lds, h->cs, pr, L.count, tl, h->dinfo, nullptr); break;
-      default:   // kind 0 launches may carry G_DIAG / G_PANEL problems
-        hipLaunchKernelGGL((k_gemm<false, false, true, true>), g, b, lds, h->cs, pr, L.count, tl, h->dinfo, L.ticket); break;
-    }
-  } else {
-    switch (L.kind) {
-      case 1: hipLaunchKernelGGL((k_gemm<false, true>), g, b, lds, h->cs, pr, L.count, tl, h->dinfo, nullptr); break;
-      case 2: hipLaunchKernelGGL((k_gemm<true, true>), g, b, lds, h->cs, pr, L.count, tl, h->dinfo, nullptr); break;
-      case 3: hipLaunchKernelGGL((k_gemm<true, false>), g, b, lds, h->cs, pr, L.count, tl, h->dinfo, nullptr); break;
-      case 4: hipLaunchKernelGGL((k_gemm<false, false>), g, b, lds, h->cs, pr, L.count, tl, h->dinfo, nullptr); break;
-      default:   // kind 0 launches may carry G_DIAG / G_PANEL problems
-        hipLaunchKernelGGL((k_gemm<false, false, true>), g, b, lds, h->cs, pr, L.count, tl, h->dinfo, L.ticket); break;
-    }
-  }
-  DCHK_HIP(h, hipGetLastError());
+int launch(gpe_dist* h, const GemmLaunch& L, bool grad = false) {
+  DCHK_HIP(h, launch_k_gemm(L, grad ? h->gprobs : h->dprobs, grad ? h->gtiles : h->dtiles, h->dinfo, h->cs));
   return GPE_OK;
 }
 
@@ -1270,8 +1107,7 @@ int ensure_grad(gpe_dist* h) {
       }
       // M^T(c0:c0+cw, the rank's rows of h:t1) = X11(c0:h, c0:c0+cw)^T L21(rows, c0:h)^T
       // (X11 triangular: K from the output's row tile, G_KBEG_TI)
-      tc.m.kind = 3;
-      tc.m.first = (int)probs.size();
+      tc.m = begin_launch(GEMM_AK, probs);
       for (Rank& R : h->ranks)
         for (size_t p = 0; p < pairs.size(); ++p) {
           const int c0 = pairs[p].t0 + j0, ls = lstart_of(pairs[p].h, P, R.rank);
@@ -1279,14 +1115,10 @@ int ensure_grad(gpe_dist* h) {
           if (n2 <= 0) continue;
           const double* A = P == 1 ? R.X + (long long)c0 * TILE + (long long)c0 * TILE * R.ld : R.g1 + og1[p];
           double* C = P == 1 ? R.slab + og2[p] : R.trecv + R.rank * tc.seg2 + o2[p];
-          GemmProb q = dprob(A, P == 1 ? R.ld : (long long)rows1 * TILE,
-                             R.A + (long long)ls * TILE + (long long)c0 * TILE * R.ld, R.ld, C, (long long)cw * TILE,
-                             cw, n2, rows1 * TILE, G_KBEG_TI, 1.0, 0.0);
-          q.tile_begin = tc.m.tiles;
-          q.ntiles = cw * n2;
-          tc.m.tiles += q.ntiles;
-          ++tc.m.count;
-          probs.push_back(q);
+          GemmProb q = mkprob(A, P == 1 ? R.ld : (long long)rows1 * TILE,
+                              R.A + (long long)ls * TILE + (long long)c0 * TILE * R.ld, R.ld, C, (long long)cw * TILE,
+                              cw, n2, rows1 * TILE, G_KBEG_TI, 1.0, 0.0);
+          push_prob(tc.m, probs, q, false);
         }
       if (P > 1) {   // M^T's columns out of the segments, in global row order
         tc.unp2 = (int)moves.size();
@@ -1299,8 +1131,7 @@ int ensure_grad(gpe_dist* h) {
       // X21(i, c0:c0+cw) = -X22(i, h:i+1) M(h:i+1, c0:c0+cw) for the rank's rows i of
       // [h, t1): one problem per pair, local row ti = global row (ls + ti) P + rank with K
       // up to its diagonal (G_KEND_TI with kti_mul = P)
-      tc.x.kind = 4;
-      tc.x.first = (int)probs.size();
+      tc.x = begin_launch(GEMM_PLAIN, probs);
       for (Rank& R : h->ranks)
         for (size_t p = 0; p < pairs.size(); ++p) {
           const int c0 = pairs[p].t0 + j0, hh = pairs[p].h;
@@ -1308,16 +1139,12 @@ int ensure_grad(gpe_dist* h) {
           const int le = std::min(R.nlx, lstart_of(pairs[p].t1, P, R.rank));
           if (le <= ls) continue;
           double* row = R.X + (long long)ls * TILE;
-          GemmProb q = dprob(row + (long long)hh * TILE * R.ld, R.ld, R.slab + og2[p], (long long)cw * TILE,
-                             row + (long long)c0 * TILE * R.ld, R.ld, le - ls, cw, (pairs[p].t1 - hh) * TILE,
-                             G_KEND_TI, -1.0, 0.0);
+          GemmProb q = mkprob(row + (long long)hh * TILE * R.ld, R.ld, R.slab + og2[p], (long long)cw * TILE,
+                              row + (long long)c0 * TILE * R.ld, R.ld, le - ls, cw, (pairs[p].t1 - hh) * TILE,
+                              G_KEND_TI, -1.0, 0.0);
           q.kti_mul = P;
           q.kti_off = ls * P + R.rank - hh;
-          q.tile_begin = tc.x.tiles;
-          q.ntiles = (le - ls) * cw;
-          tc.x.tiles += q.ntiles;
-          ++tc.x.count;
-          probs.push_back(q);
+          push_prob(tc.x, probs, q, false);
         }
       h->tri.push_back(tc);
     }
@@ -1339,13 +1166,11 @@ int ensure_grad(gpe_dist* h) {
       DCHK_HIP(h, hipMemset(h->wcnt, 0, (size_t)ntw * sizeof(int)));
     }
   }
-  h->wa_l.assign(h->ranks.size(), DLaunch());
+  h->wa_l.assign(h->ranks.size(), GemmLaunch());
   h->slabs.assign(h->ranks.size(), std::vector<SlabLaunch>());
   for (size_t s = 0; s < h->ranks.size(); ++s) {
     Rank& R = h->ranks[s];
-    DLaunch wl;
-    wl.kind = 2;
-    wl.first = (int)probs.size();
+    GemmLaunch wl = begin_launch(GEMM_AK_BK, probs);
     // W(a) = X_r(:, a)^T R2_r over its rows >= a: one tile row of W per a, K up to n -- a
     // launch of NB tiles, so K is split over up to 8 workgroups per tile (last-arriver
     // reduction in index order, as the single-GPU split_k)
@@ -1354,21 +1179,16 @@ int ensure_grad(gpe_dist* h) {
     for (int a = 0; a < NB; ++a) {
       const int ls = lstart_of(a, P, R.rank), K = (R.nlx - ls) * TILE;
       if (K <= 0) continue;
-      GemmProb p = dprob(R.X + (long long)ls * TILE + (long long)a * TILE * R.ld, R.ld,
-                         R.r2loc + (long long)ls * TILE, R.ld, R.wpart + (long long)a * TILE, np,
-                         1, h->NA, K, 0, 1.0, 0.0);
-      if (ks > 1) {
+      GemmProb p = mkprob(R.X + (long long)ls * TILE + (long long)a * TILE * R.ld, R.ld,
+                          R.r2loc + (long long)ls * TILE, R.ld, R.wpart + (long long)a * TILE, np,
+                          1, h->NA, K, 0, 1.0, 0.0);
+      if (ks > 1) {   // (offsets in unsplit tiles: wl.tiles counts every share)
         p.ksplit = ks;
-        p.part = h->wsplit + (size_t)wl.tiles * ks * TILE * TILE;
-        p.tcnt = h->wcnt + wl.tiles;
+        p.part = h->wsplit + (size_t)wl.tiles * TILE * TILE;
+        p.tcnt = h->wcnt + wl.tiles / ks;
       }
-      p.tile_begin = wl.tiles * ks;
-      p.ntiles = h->NA * ks;
-      wl.tiles += h->NA;
-      ++wl.count;
-      probs.push_back(p);
+      push_prob(wl, probs, p, false);
     }
-    wl.tiles *= ks;
     h->wa_l[s] = wl;
     // partial of A^-1 by slabs of tile rows [a0, a1): P_r(a, 0:a+1) = X_r(:, a)^T X_r(:, 0:a+1)
     // over its rows >= a (K = 0 writes zeros), into slab row a - a0
@@ -1376,18 +1196,13 @@ int ensure_grad(gpe_dist* h) {
       SlabLaunch sl;
       sl.a0 = a0;
       sl.a1 = std::min(NB, a0 + h->slab_rows);
-      sl.gemm.kind = 2;
-      sl.gemm.first = (int)probs.size();
+      sl.gemm = begin_launch(GEMM_AK_BK, probs);
       for (int a = sl.a0; a < sl.a1; ++a) {
         const int ls = lstart_of(a, P, R.rank), K = std::max(0, (R.nlx - ls) * TILE);
-        GemmProb p = dprob(R.X + (long long)ls * TILE + (long long)a * TILE * R.ld, R.ld,
-                           R.X + (long long)ls * TILE, R.ld, R.slab + (long long)(a - a0) * TILE, lds,
-                           1, a + 1, K, 0, 1.0, 0.0);
-        p.tile_begin = sl.gemm.tiles;
-        p.ntiles = a + 1;
-        sl.gemm.tiles += a + 1;
-        ++sl.gemm.count;
-        probs.push_back(p);
+        GemmProb p = mkprob(R.X + (long long)ls * TILE + (long long)a * TILE * R.ld, R.ld,
+                            R.X + (long long)ls * TILE, R.ld, R.slab + (long long)(a - a0) * TILE, lds,
+                            1, a + 1, K, 0, 1.0, 0.0);
+        push_prob(sl.gemm, probs, p, false);
       }
       h->slabs[s].push_back(sl);
     }

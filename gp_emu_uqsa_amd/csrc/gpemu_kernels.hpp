@@ -1030,12 +1030,14 @@ __device__ __forceinline__ void panel_subst(const PanelAddr& pa, const double* L
 // inside the register budget and use the 16-byte C preload and epilogue.
 // ticket (FUSED launches with a tile list and in-launch waits): each workgroup claims its
 // list position with an atomic ticket when it starts, instead of taking blockIdx.x.  A
-// tile waits only on tiles earlier in the list (build_plan checks it), and every earlier
+// tile waits only on tiles earlier in the list (waits_point_back, gpemu_gemm_sched.hpp, checks
+// every such list when it is built), and every earlier
 // position was claimed by a workgroup that is already running, so the earliest unfinished
 // tile can always make progress whatever order the hardware dispatches the workgroups in
 // and whatever else occupies the CUs (other streams, other contexts' launches).
-// What every problem of a launch must satisfy (nothing here checks it; the test hook
-// gpe_test_gemm_group refuses what it can see):
+// What every problem of a launch must satisfy (nothing here checks it; push_prob of
+// gpemu_gemm_sched.hpp keeps the tile_begin rule, and the test hook gpe_test_gemm_group refuses
+// what it can see):
 // - K a multiple of GK = 16: the K loop runs (kend - kbeg) / GK whole stages and would drop a
 //   remainder silently; the range flags keep kbeg and kend on multiples of 128.
 // - alpha != 0: C enters the accumulators as (beta / alpha) C and alpha scales the store.

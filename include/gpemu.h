@@ -344,16 +344,17 @@ int gpe_test_oz_product(gpe_ctx* ctx, const gpe_oz_operand* a, const gpe_oz_oper
 
 /* Test hook for one launch of the plain (non-fused) grouped fp64 GEMM k_gemm on a group of
  * problems, an addition within ABI 10; the reference has no counterpart.  Descriptors come
- * from mkprob, split K from split_k, the tile list / CDEF choice from add_launch (on a plan of
- * the hook's own) and the launch from launch_gemm_range: the routines every production GEMM
- * goes through.  Device memory is the hook's own and freed on every way out; the context's
+ * from mkprob and push_prob, split K from split_k, the tile list from order_tiles
+ * (csrc/gpemu_gemm_sched.hpp, through add_launch on a plan of the hook's own) and the launch
+ * from launch_gemm_range, so launch_k_gemm: the routines every production GEMM, single-GPU or
+ * row-block, goes through.  Device memory is the hook's own and freed on every way out; the context's
  * resident factor and cached plans are not touched.
  *
  * Buffers: nbuf host fp64 arrays bufs[i] of lens[i] doubles, copied to the device as they are
  * and copied back whole afterwards.  Problem p names its operands by buffer index, element
  * offset and leading dimension; operands may share a buffer, and C may live in the buffer of
  * A and B (that the tiles read and the tiles written are disjoint is the caller's business).
- * With kind = 0..3 (launch_gemm_range: 0 <A M-contiguous, B N-contiguous>, 1 <A K-contiguous>,
+ * With kind = 0..3 (GemmKind: 0 <A M-contiguous, B N-contiguous>, 1 <A K-contiguous>,
  * 2 <both K-contiguous>, 3 <B K-contiguous>), over 128 x 128 tiles (ti, tj), ti < mt, tj < nt
  * (tj <= ti only under GPE_G_CLOWER):
  *   opA(m, k) = A[k + m lda] (K-contiguous) or A[m + k lda];  opB(k, n) likewise with ldb;

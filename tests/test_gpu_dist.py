@@ -103,6 +103,27 @@ def test_loopback_gradient_matches_single_gpu(ctx, variant, kernel, use_r, d, P)
     dc.close()
 
 
+def test_loopback_gradient_smallest_two_ranks(ctx):
+    """P = 2 at n = 300 (3 ragged tile rows): the smallest shape whose gradient runs every
+    k_gemm instance of the row-block path -- the M row <0,1>, the TRTRI's M^T <1,0>, W and the
+    slabs <1,1>, the plain panels and updates, the fused diagonal launch -- so a launch that
+    takes the wrong instance (csrc/gpemu_gemm_sched.hpp GemmKind) reads the wrong panels here,
+    not only at P = 3 and n >= 1000.  Against the single-GPU gradient."""
+    n, d = 300, 3
+    X, f, H = orc.synthetic_problem(n, d, seed=6)
+    hp = _hp(d)
+    ctx.set_data(X, f, H)
+    ref, gref, s2ref = ctx.objective(native.GP4ML, native.KERNEL_STD, hp, want_grad=True)
+    dc = native.DistContext(0, 2)
+    dc.set_data(X, f, H)
+    llh, g, s2 = dc.objective(native.GP4ML, native.KERNEL_STD, hp, want_grad=True)
+    dc.close()
+    assert abs(llh - ref) <= 1e-10 * abs(ref), (llh, ref)
+    assert abs(s2 - s2ref) <= 1e-10 * abs(s2ref)
+    ok, err = _grad_ok(g, gref)
+    assert ok, (g, gref, err)
+
+
 def test_loopback_not_pd():
     X, f, H = orc.synthetic_problem(400, 2, seed=3)
     X[1] = X[0]                                   # duplicate point, no nugget

@@ -1,6 +1,7 @@
 """The grouped fp64 GEMM (k_gemm, csrc/gpemu_kernels.hpp) launch by launch against exact sums:
-one launch at a time through gpe_test_gemm_group -- mkprob, split_k, add_launch (order_tiles,
-the CDEF choice) and launch_gemm_range, on buffers of the hook's own -- compared with
+one launch at a time through gpe_test_gemm_group -- mkprob, split_k, add_launch (push_prob,
+order_tiles, the CDEF choice) and launch_gemm_range (launch_k_gemm), the launch layer of
+csrc/gpemu_gemm_sched.hpp that the row-block path shares, on buffers of the hook's own -- compared with
 tests/gemm_group_ref.py.  Operands lie on a grid where every partial sum is exact in fp64, so
 the comparison is bit for bit (np.array_equal) unless a case says `bound`; everything outside
 the covered C tiles must come back unchanged, bit for bit.  Every C tile written with
