@@ -1648,7 +1648,7 @@ int oz_gemm_crt(gpe_ctx* c, const OzConst& k, const OzGemm& g, const OzCrt& r, i
     }
     HIPCHK(c, hipEventRecord(c->oev[c->oev_used], st));
   }
-  hipLaunchKernelGGL(k_oz_gemm, dim3(k.nmod * g.list_len), dim3(256), OZ_LDS, st, g, k);
+  oz_gemm_launch(st, g, k);
   if (c->prof) {
     HIPCHK(c, hipEventRecord(c->oev[c->oev_used + 1], st));
     c->oev_used += 2;
@@ -2565,7 +2565,7 @@ static int posterior_oz(gpe_ctx* c, bool f32, const double* Ks, long long mp, do
   g.ntj = ntj;
   g.res = c->dpres;
   g.res_bytes = rb;
-  hipLaunchKernelGGL(k_oz_gemm, dim3(N * g.list_len), dim3(256), OZ_LDS, st, g, k);
+  oz_gemm_launch(st, g, k);
   OzCrt r{c->dpres, rb, 0, ntj, c->dpxe, c->dpke, V, (long long)np, np, (int)mp, 0, 1.0};
   hipLaunchKernelGGL(k_oz_crt, dim3((unsigned)(nti * ntj * 16)), dim3(256), 0, st, r, k);
   HIPCHK(c, hipGetLastError());

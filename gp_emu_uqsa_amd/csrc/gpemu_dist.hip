@@ -960,7 +960,7 @@ int oz_slab(gpe_dist* h, const Rank& R, const SlabLaunch& sl, size_t si) {
   g.res = h->ozr;
   g.res_bytes = h->oz_res_bytes;
   g.ti0 = ti0;
-  hipLaunchKernelGGL(k_oz_gemm, dim3(k.nmod * g.list_len), dim3(256), OZ_LDS, h->stream, g, k);
+  oz_gemm_launch(h->stream, g, k);
   const int rows = sl.a1 * TILE;
   OzCrt r{h->ozr, h->oz_res_bytes, 1, 0, h->ozx, h->ozx, R.slab, (long long)h->slab_rows * TILE, rows, rows, 1, 1.0, ti0};
   const long long nt = (long long)ti1 * (ti1 + 1) / 2 - (long long)ti0 * (ti0 + 1) / 2;
@@ -1239,7 +1239,7 @@ int trtri_all(gpe_dist* h) {
         oz_tri_pair_launches(h->stream, k, q, h->ozl, tile(R.A, q.h, q.t0), tile(R.X, q.t0, q.t0), tile(R.X, q.h, q.h),
                              tile(R.X, q.h, q.t0), R.ld, R.slab, h->ozp, h->ozr, h->ozx, false,
                              [&](const OzGemm& g, const OzCrt& r, int nti, double, double) {
-                               hipLaunchKernelGGL(k_oz_gemm, dim3(k.nmod * g.list_len), dim3(256), OZ_LDS, h->stream, g, k);
+                               oz_gemm_launch(h->stream, g, k);
                                hipLaunchKernelGGL(k_oz_crt, dim3((unsigned)(nti * g.ntj * 16)), dim3(256), 0, h->stream,
                                                   r, k);
                              });

@@ -28,6 +28,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -35,7 +36,7 @@ namespace gpe {
 
 constexpr int OZ_T = 256;                  // output tile, and the planes' column panels
 constexpr int OZ_SK = 64;                  // k (bytes) per LDS stage: two 32-deep k-steps
-constexpr int OZ_NBUF = 4;                 // stage ring (loads issued 3 stages ahead)
+constexpr int OZ_NBUF = 4;                 // stage ring (stage s + 4 is issued from stage s's barrier on)
 constexpr int OZ_OPND = OZ_T * OZ_SK;      // one operand's stage image (16 KB)
 constexpr int OZ_LDS = OZ_NBUF * 2 * OZ_OPND;   // 128 KB: one workgroup per CU
 constexpr int OZ_MAXMOD = 16;
@@ -141,6 +142,13 @@ __device__ __forceinline__ void oz_glds16(const int8_t* src, int8_t* dst) {
   __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
                                    (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
 }
+// p, the same in every lane, held in scalar registers: what is added to it per stage is then
+// scalar arithmetic, and a load's address one vector add of the lane's offset
+__device__ __forceinline__ const int8_t* oz_uniform(const int8_t* p) {
+  const unsigned long long u = (unsigned long long)p;
+  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)u), hi = __builtin_amdgcn_readfirstlane((unsigned)(u >> 32));
+  return (const int8_t*)(((unsigned long long)hi << 32) | lo);
+}
 template <int N> __device__ __forceinline__ void oz_vmwait() { asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N) : "memory"); }
 
 // One operand of a product, as int8 planes (one per modulus, plane_bytes apart): row r of
@@ -188,12 +196,81 @@ __device__ __forceinline__ long long oz_res_tile(int tri, int ntj, int ti, int t
   return tri ? (long long)ti * (ti + 1) / 2 + tj : (long long)ti * ntj + tj;
 }
 
+// wait until at most `stages` whole stages (8 direct loads each) of this wave are in flight
+__device__ __forceinline__ void oz_vmwait_stages(int stages) {
+  static_assert(OZ_NBUF <= 5, "one case per stage that can be in flight");
+  if (stages >= 4) oz_vmwait<32>();
+  else if (stages == 3) oz_vmwait<24>();
+  else if (stages == 2) oz_vmwait<16>();
+  else if (stages == 1) oz_vmwait<8>();
+  else oz_vmwait<0>();
+}
+
+// The tile end: the centred residue of each of a lane's 256 accumulators as one byte, 16 bytes
+// per MFMA block in the block's own order.  Only the low byte of a result is kept, so every
+// step needs to be right modulo 256 only, except the quotient q:
+//   t = (a >> 16) (2^16 mod m) + (a & 0xffff) = a + (a >> 16) (c16 - 2^16): one 24-bit
+//       multiply-add (|a >> 16| <= K / 4 < 2^15 and |c16 - 2^16| <= 2^16; |t| < 2^23 for
+//       K <= OZ_MAX_K < 2^17: |a| <= K 2^14, so |a >> 16| (2^16 mod m) <= (K / 4) 252, plus 2^16),
+//       so t is exact in fp32;
+//   q = rint(t / m) to within 3e-4, as p = fl(t (1 / m)) rounded to an integer by adding
+//       1.5 2^23: |p| < 2^22, so the sum lies in [2^23, 2^24) where fp32 numbers are the
+//       integers and the addition itself rounds p to nearest, ties to even (the constant is
+//       even, so the tie goes where rintf(p) puts it: the same q, bit for bit).  The sum's low
+//       24 bits are 2^22 + q.  The product and the sum are two roundings: no contraction here;
+//   r = t - q m in [-m/2 - 1, m/2 + 1], formed as t + (2^22 + q)(-m) by a second 24-bit
+//       multiply-add: off by 2^22 m, a multiple of 256.
+// M256: m = 256, the low byte of a itself.
+template <bool M256>
+__device__ __forceinline__ void oz_store_residues(const oz_v16i (&acc)[4][4], int m, int c16, float inv, int8_t* out) {
+#pragma clang fp contract(off)
+  const int cm = c16 - 65536, nm = -m;
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      unsigned v[16];
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int a = acc[i][j][r];
+        if constexpr (M256) {
+          v[r] = (unsigned)a;
+        } else {
+          const int t = __mul24(a >> 16, cm) + a;
+          const float qf = (float)t * inv + 12582912.0f;
+          v[r] = (unsigned)(__mul24(__float_as_int(qf), nm) + t);
+        }
+      }
+      oz_v4i w;
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {   // bytes 0 of v[4 u .. 4 u + 3], lowest first
+        const unsigned lo = __builtin_amdgcn_perm(v[4 * u + 1], v[4 * u], 0x0c0c0400u);
+        const unsigned hi = __builtin_amdgcn_perm(v[4 * u + 3], v[4 * u + 2], 0x0c0c0400u);
+        w[u] = (int)__builtin_amdgcn_perm(hi, lo, 0x05040100u);
+      }
+      *reinterpret_cast<oz_v4i*>(out + (long long)(4 * i + j) * 64 * 16) = w;
+    }
+}
+
 // 4 waves of 128 x 128 (4 x 4 blocks of the 32 x 32 x 32 i8 MFMA, operands swapped so lane &
-// 31 runs along the tile's rows); stages of 64 k through a 4-deep LDS ring filled by direct
-// global -> LDS loads.  The stage image of each operand is [row][64 B] with granule g of row
-// r at slot g ^ ((r >> 2) & 3): conflict-free for ds_read_b128's lane groups.  Output: the
-// centred residue of every entry, one byte, in the MFMA's own order (lane l of block b of
-// wave w: 16 bytes at ((w 16 + b) 64 + l) 16 of the tile's 64 KB).
+// 31 runs along the tile's rows); stages of 64 k (two 32-deep k-steps) through a 4-deep LDS
+// ring filled by direct global -> LDS loads.  The stage image of each operand is [row][64 B]
+// with granule g of row r at slot g ^ ((r >> 2) & 3): conflict-free for ds_read_b128's lane
+// groups.  Steady state, stage s in buffer s % 4, nothing but the barrier between two MFMAs:
+//   k-step 0: 16 MFMAs; a fragment read of (s, k-step 1) behind each of the first 8, a direct
+//             load of stage s + 3 (its second half) behind every other one of the last 8;
+//   boundary: vmcnt(16) (this wave's loads of stage s + 1 have landed; s + 2 and s + 3 stay
+//             in flight), lgkmcnt(0), s_barrier: every wave is done reading buffer s % 4 and
+//             stage s + 1 is whole;
+//   k-step 1: 16 MFMAs; the reads of (s + 1, k-step 0) behind the first 8, the first half of
+//             the loads of stage s + 4, into buffer s % 4, behind the last 8.
+// So a k-step's reads have 8 MFMAs to land before the next k-step needs them, and no k-step
+// carries more than one direct load per four MFMAs.  The last 4 stages (and a tile shorter than
+// the ring) run the same step without the loads that no longer exist and with the count of what
+// is still in flight (tests/test_gpu_oz_pipeline.py).  Output: the centred residue of every entry, one
+// byte, in the MFMA's own order (lane l of block b of wave w: 16 bytes at ((w 16 + b) 64 + l)
+// 16 of the tile's 64 KB).  Precondition besides OzGemm's: 256 rows of an operand span less
+// than 2^32 bytes (ld < 2^24: every call site's is a padded order or K, at most 2^17).
 static __global__ void __launch_bounds__(256, 1) k_oz_gemm(OzGemm g, OzConst cst) {
   extern __shared__ __attribute__((aligned(16))) double lds_d[];
   int8_t* lds = reinterpret_cast<int8_t*>(lds_d);
@@ -211,19 +288,23 @@ static __global__ void __launch_bounds__(256, 1) k_oz_gemm(OzGemm g, OzConst cst
   ob.p += (long long)l * ob.plane_bytes;
   long long lda, ldb;
   const int kp = (lane & 3) ^ ((lane >> 4) & 3);
-  const int8_t* sa = oz_tile_rows(oa, ti, kb, lda);
-  const int8_t* sb = oz_tile_rows(ob, tj, kb, ldb);
-  sa += (long long)(16 * wave + (lane >> 2)) * lda + 16 * kp;
-  sb += (long long)(16 * wave + (lane >> 2)) * ldb + 16 * kp;
-  auto stage = [&](int s) {
-    int8_t* As = lds + (s & (OZ_NBUF - 1)) * 2 * OZ_OPND;
-    int8_t* Bs = As + OZ_OPND;
+  // a direct load's source: the tile's first row at the stage's k (the same for every lane, so
+  // it advances in scalar registers) plus this lane's 32-bit offset, fixed for the tile
+  const int8_t* ua = oz_tile_rows(oa, ti, kb, lda);
+  const int8_t* ub = oz_tile_rows(ob, tj, kb, ldb);
+  unsigned va[4], vb[4];
 #pragma unroll
-    for (int p = 0; p < 4; ++p) {
-      const int w = wave + 4 * p;   // wave-instruction index: rows 16 w .. 16 w + 15
-      oz_glds16(sa + (long long)p * 64 * lda + (long long)s * OZ_SK, As + 16 * w * OZ_SK);
-      oz_glds16(sb + (long long)p * 64 * ldb + (long long)s * OZ_SK, Bs + 16 * w * OZ_SK);
-    }
+  for (int p = 0; p < 4; ++p) {
+    const unsigned row = (unsigned)(16 * wave + (lane >> 2) + 64 * p);
+    va[p] = row * (unsigned)lda + 16u * (unsigned)kp;
+    vb[p] = row * (unsigned)ldb + 16u * (unsigned)kp;
+  }
+  // load u of stage s: 16 rows of A (u even) or B (u odd), rows 16 w .. 16 w + 15 with w the
+  // wave-instruction index wave + 4 (u / 2)
+  auto load1 = [&](int s, int u) {
+    int8_t* dst = lds + ((unsigned)s % OZ_NBUF) * 2 * OZ_OPND + (u & 1) * OZ_OPND + 16 * (wave + 4 * (u >> 1)) * OZ_SK;
+    const int8_t* src = oz_uniform(((u & 1) ? ub : ua) + (long long)s * OZ_SK);
+    oz_glds16(src + ((u & 1) ? vb[u >> 1] : va[u >> 1]), dst);
   };
   oz_v16i acc[4][4];
 #pragma unroll
@@ -232,15 +313,17 @@ static __global__ void __launch_bounds__(256, 1) k_oz_gemm(OzGemm g, OzConst cst
     for (int j = 0; j < 4; ++j) acc[i][j] = oz_v16i{};
   const int ns = max(0, ke - kb) / OZ_SK;
   const int r32 = lane & 31, h = lane >> 5, sw = (r32 >> 2) & 3;
-  // the 8 fragments (4 of A, 4 of B) of k-step ks of stage s
-  auto frags = [&](int s, int ks, oz_v4i (&af)[4], oz_v4i (&bf)[4]) {
-    const int8_t* As = lds + (s & (OZ_NBUF - 1)) * 2 * OZ_OPND;
+  // fragment u of k-step ks of stage s: A's (u < 4) or B's
+  auto frag1 = [&](int s, int ks, int u, oz_v4i (&af)[4], oz_v4i (&bf)[4]) {
+    const int8_t* As = lds + ((unsigned)s % OZ_NBUF) * 2 * OZ_OPND;
     const int8_t* Bs = As + OZ_OPND;
     const int slot = ((2 * ks + h) ^ sw) * 16;
+    if (u < 4) af[u] = *reinterpret_cast<const oz_v4i*>(As + (wm + 32 * u + r32) * OZ_SK + slot);
+    else bf[u - 4] = *reinterpret_cast<const oz_v4i*>(Bs + (wn + 32 * (u - 4) + r32) * OZ_SK + slot);
+  };
+  auto frags = [&](int s, int ks, oz_v4i (&af)[4], oz_v4i (&bf)[4]) {
 #pragma unroll
-    for (int i = 0; i < 4; ++i) af[i] = *reinterpret_cast<const oz_v4i*>(As + (wm + 32 * i + r32) * OZ_SK + slot);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) bf[j] = *reinterpret_cast<const oz_v4i*>(Bs + (wn + 32 * j + r32) * OZ_SK + slot);
+    for (int u = 0; u < 8; ++u) frag1(s, ks, u, af, bf);
   };
   auto mfmas = [&](const oz_v4i (&af)[4], const oz_v4i (&bf)[4]) {
 #pragma unroll
@@ -248,75 +331,95 @@ static __global__ void __launch_bounds__(256, 1) k_oz_gemm(OzGemm g, OzConst cst
 #pragma unroll
       for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_i32_32x32x32_i8(bf[j], af[i], acc[i][j], 0, 0, 0);
   };
-  // wait until stage s has landed (this wave's loads; the barrier makes it every wave's):
-  // the stages issued after it, up to s + 3, may stay in flight (loads retire in order)
-  auto wait_stage = [&](int s) {
-    const int later = min(ns - 1, s + 2) - s;
-    if (later >= 2) oz_vmwait<16>();
-    else if (later == 1) oz_vmwait<8>();
-    else oz_vmwait<0>();
+  if (ns > 0) {
+    oz_v4i ca[4], cb[4], na[4], nb[4];
+    // One k-step: the 16 MFMAs on (xa, xb); with READ, the 8 fragment reads of k-step rks of
+    // stage rs into (ya, yb), one behind each of the first 8 MFMAs (an MFMA leaves the wave's
+    // issue free for most of its 32 cycles, and the reads have the last 8 MFMAs to land); with
+    // LOAD, the direct loads u0 .. u0 + 3 of stage ls, one behind every other of the last 8.
+    auto kstep = [&](const oz_v4i (&xa)[4], const oz_v4i (&xb)[4], auto READ, int rs, int rks, oz_v4i (&ya)[4],
+                     oz_v4i (&yb)[4], auto LOAD, int ls, int u0) {
+      mfmas(xa, xb);
+      if constexpr (decltype(READ)::value) {
+        frags(rs, rks, ya, yb);
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);   // one MFMA
+          __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);   // one LDS read
+        }
+      } else {
+        __builtin_amdgcn_sched_group_barrier(0x008, 8, 0);
+      }
+      if constexpr (decltype(LOAD)::value) {
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          load1(ls, u0 + u);
+          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+          __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);   // one direct load
+          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+        }
+      } else {
+        __builtin_amdgcn_sched_group_barrier(0x008, 8, 0);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+    };
+    // One stage, s in buffer s % OZ_NBUF.  Its first k-step carries the second half of the
+    // loads of stage s + OZ_NBUF - 1 (LOADA: that stage exists and the ring is full), its second
+    // k-step the first half of those of stage s + OZ_NBUF (LOADB): one direct load per four
+    // MFMAs throughout.  Between the two, if stage s + 1 exists (NEXT), the one barrier.
+    // Hazards: loads go into buffer s % OZ_NBUF only after the barrier of stage s, which every
+    // wave passes with its reads of stage s retired (lgkmcnt(0)); stage s + 1 is read after
+    // that same barrier, which every wave passes with its own loads of stage s + 1 landed.
+    // Loads retire in order, so the count is that of the loads issued after them: the stages
+    // up to s + OZ_NBUF - 1, or to the tile's last.
+    auto step = [&](int s, auto NEXT, auto LOADA, auto LOADB) {
+      kstep(ca, cb, std::true_type{}, s, 1, na, nb, LOADA, s + OZ_NBUF - 1, 4);
+      if constexpr (decltype(NEXT)::value) {
+        if constexpr (decltype(LOADB)::value) oz_vmwait<8 * (OZ_NBUF - 2)>();
+        else oz_vmwait_stages(ns - s - 2);
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      kstep(na, nb, NEXT, s + 1, 0, ca, cb, LOADB, s + OZ_NBUF, 0);
+    };
+    constexpr std::true_type Y{};
+    constexpr std::false_type N{};
+    // prologue: a tile shorter than the ring whole; else the ring less the second half of its
+    // last stage, which the first step brings (20 loads may stay in flight behind stage 0)
+    if (ns < OZ_NBUF) {
+      for (int s = 0; s < ns; ++s)
+#pragma unroll
+        for (int u = 0; u < 8; ++u) load1(s, u);
+      oz_vmwait_stages(ns - 1);
+    } else {
+#pragma unroll
+      for (int s = 0; s < OZ_NBUF; ++s)
+#pragma unroll
+        for (int u = 0; u < (s == OZ_NBUF - 1 ? 4 : 8); ++u) load1(s, u);
+      oz_vmwait<8 * (OZ_NBUF - 2) + 4>();
+    }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
-  };
-  if (ns > 0) {
-    // Software pipeline, one barrier per stage: the next k-step's fragments are read while
-    // the current k-step's 16 MFMAs issue.  Stage s + 4 goes into the buffer of stage s,
-    // whose last fragment reads every wave finished before the barrier of stage s + 1.
-    for (int s = 0; s < min(ns, 3); ++s) stage(s);
-    oz_v4i ca[4], cb[4], na[4], nb[4];
-    wait_stage(0);
-    if (ns > 3) stage(3);
     frags(0, 0, ca, cb);
-    for (int s = 0; s < ns; ++s) {
-      // this k-step's MFMAs with the next k-step's 8 fragment reads between the first 8 (an
-      // MFMA leaves the wave's issue free for most of its 32 cycles; the reads issued ahead
-      // of the MFMAs made the first MFMA wait for all of them: lgkmcnt(0))
-      mfmas(ca, cb);
-      frags(s, 1, na, nb);
-#pragma unroll
-      for (int u = 0; u < 8; ++u) {
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);   // one MFMA
-        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);   // one LDS read
-      }
-      __builtin_amdgcn_sched_group_barrier(0x008, 8, 0);
-      __builtin_amdgcn_sched_barrier(0);
-      if (s + 1 < ns) {
-        wait_stage(s + 1);
-        if (s + 4 < ns) stage(s + 4);
-        frags(s + 1, 0, ca, cb);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-      mfmas(na, nb);
-      __builtin_amdgcn_sched_barrier(0);
-    }
+    int s = 0;
+    for (; s + OZ_NBUF < ns; ++s) step(s, Y, Y, Y);
+    if (ns >= OZ_NBUF) step(s++, Y, Y, N);   // (OZ_NBUF >= 2: stage s + 1 exists)
+    for (; s + 1 < ns; ++s) step(s, Y, N, N);
+    if (s < ns) step(s, N, N, N);
   }
-  // centred residues: t = (acc >> 16) (2^16 mod m) + (acc & 0xffff) is exact in fp32
-  // (|t| < 2^23 for K <= OZ_MAX_K < 2^17: |acc| <= K 2^14, so |acc >> 16| <= K / 4, times
-  // 2^16 mod m <= 252, plus 2^16), q = rint(t / m) to within 3e-4, r = t - q m in
-  // [-m/2 - 1, m/2 + 1]; m = 256: the low byte itself
-  const int m = cst.m[l], c16 = cst.c16[l];
-  const float inv = cst.inv[l];
+  const int m = cst.m[l];
   int8_t* out = g.res + (long long)l * g.res_bytes +
                 (oz_res_tile(g.tri, g.ntj, ti, tj) - oz_res_tile(g.tri, g.ntj, g.ti0, 0)) * (OZ_T * OZ_T) +
                 ((long long)(wave * 16) * 64 + lane) * 16;
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      unsigned w[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int a = acc[i][j][r];
-        int v = a;
-        if (m != 256) {
-          const int t = __mul24(a >> 16, c16) + (a & 0xffff);
-          const int q = (int)rintf((float)t * inv);
-          v = t - __mul24(q, m);
-        }
-        w[r >> 2] |= ((unsigned)v & 0xffu) << (8 * (r & 3));
-      }
-      *reinterpret_cast<oz_v4i*>(out + (long long)(4 * i + j) * 64 * 16) = oz_v4i{(int)w[0], (int)w[1], (int)w[2], (int)w[3]};
-    }
+  if (m == 256) oz_store_residues<true>(acc, m, 0, 0.0f, out);
+  else oz_store_residues<false>(acc, m, cst.c16[l], cst.inv[l], out);
+}
+
+// The one launch of k_oz_gemm: a workgroup per modulus and list position, the whole ring as
+// dynamic LDS (one workgroup per CU)
+static inline void oz_gemm_launch(hipStream_t st, const OzGemm& g, const OzConst& k) {
+  hipLaunchKernelGGL(k_oz_gemm, dim3((unsigned)(k.nmod * g.list_len)), dim3(256), OZ_LDS, st, g, k);
 }
 
 // fp64 entries from the residues: C(r, c) = alpha v M 2^-(exr[r] + exc[c]), v = C'/M the
