@@ -10,9 +10,9 @@ The covariance build, Cholesky factorisation, triangular solves, log-marginal-
 likelihood gradient and posterior run in libgpemu.so (hand-written HIP for
 gfx950, C-ABI in include/gpemu.h); there is no CPU fallback.
 """
-from .api import (loo, plot, posterior, posterior_gradient, posterior_mean, posterior_sample,  # noqa: F401
-                  setup, train)
+from .api import (loo, plot, posterior, posterior_gradient, posterior_groups, posterior_mean,  # noqa: F401
+                  posterior_sample, setup, train)
 
 __all__ = ["setup", "train", "plot", "posterior", "posterior_sample", "loo", "posterior_gradient",
-           "posterior_mean"]
+           "posterior_mean", "posterior_groups"]
 __version__ = "0.1.0"

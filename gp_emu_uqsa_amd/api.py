@@ -110,6 +110,21 @@ def posterior_mean(E, x):
     return _model.posterior_mean(xs, E.training, E.par, E.K)
 
 
+def posterior_groups(E, x, group):
+    """(mean (m), cov (m // group, group, group)) at x, as ``posterior`` takes it: the posterior
+    covariance inside groups of ``group`` consecutive points, i.e. the block diagonal of
+    ``posterior``'s covariance without its other entries (no counterpart in the reference; the
+    points' own r is not added).  For every kernel family and any number of points;
+    1 <= group <= 64 and the number of points a multiple of it, else ValueError."""
+    x = _as_points(E, x)
+    if isinstance(group, bool) or int(group) != group or not 1 <= group <= 64:
+        raise ValueError("group must be an integer in 1..64")
+    if x.shape[0] % int(group) != 0:
+        raise ValueError("the number of points (%d) is not a multiple of group (%d)" % (x.shape[0], group))
+    xs = _model.Data(x, None, E.basis, E.par, E.beliefs, E.K)
+    return _model.posterior_groups(xs, E.training, E.par, E.K, int(group))
+
+
 def loo(E):
     """Leave-one-out validation of E on its own training set with its current
     hyperparameters: a ``LeaveOneOut`` with mean, var, var_obs, error, score and

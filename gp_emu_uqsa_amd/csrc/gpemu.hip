@@ -32,6 +32,7 @@
 #include "gpemu_pivchol.hpp"
 #include "gpemu_postgrad.hpp"
 #include "gpemu_postmean.hpp"
+#include "gpemu_postgroup.hpp"
 #include "gpemu_host_alloc.hpp"
 
 using namespace gpe;
@@ -274,6 +275,9 @@ struct gpe_ctx {
   double* dPm = nullptr;
   size_t pm_cap = 0;
   long long mean_chunk = 65536;
+  // the covariance inside groups (gpe_posterior_groups): k_post_groupgram's segment sums
+  double* dPgc = nullptr;
+  size_t pgc_cap = 0;
 
   // resident factor (gpe_factor)
   bool factor_valid = false;
@@ -1947,7 +1951,7 @@ void gpe_destroy(gpe_ctx* c) {
                     c->aux.logdet, c->dinvdelta, c->dZ,
                     c->dR2, c->dWa, c->dskp, c->dgpart, c->dgram, c->dT2, c->dcpart, c->dcsum,
                     c->dW1, c->dW2, c->dW3, c->dXs, c->dXsw, c->dsmall, c->dtiny, c->dsnb, c->dRn, c->dNU,
-                    c->dVall, c->dXall, c->dTall, c->dPc, c->dPcL, c->dPg, c->dPm};
+                    c->dVall, c->dXall, c->dTall, c->dPc, c->dPcL, c->dPg, c->dPm, c->dPgc};
   for (double* b : bufs)
     if (b) hipFree(b);
   if (c->dinfo) hipFree(c->dinfo);
@@ -2783,6 +2787,7 @@ enum class PostVar {
   FULL,       // m x m to var_out
   FULL_DW3,   // m x m left in c->dW3: one chunk (m <= POST_CHUNK_FULL)
   FULL_DEV,   // m x m into dev_out, beyond one chunk: the lower triangle of chunk blocks
+  GROUPS,     // the group x group blocks of consecutive points to var_out (m / group of them)
 };
 
 struct PostReq {
@@ -2806,6 +2811,7 @@ struct PostReq {
   const int32_t* hdim = nullptr;
   double* dmean_out = nullptr;    // m x d
   double* dvar_out = nullptr;     // m x d, or NULL: the second product is skipped
+  int group = 0;                  // GROUPS: points per group (m a multiple of it)
 };
 
 // k_post_grad<DMAX, FAM, WIDE, WB> for d inputs: the register widths of d <= 32, beyond that
@@ -2841,6 +2847,7 @@ struct CovSide {
 struct Posterior : PostReq {
   gpe_ctx* c;
   const bool full, f32, ozp;   // full variance; fp32 product; V on the int8 cores (posterior_oz)
+  const bool groups;           // the blocks of groups of points, through the diagonal pipeline
   const int d, q, P, kq;       // kq: q rounded up to the GEMM's K step
   const long long np, CHUNK;
   const bool big;              // a full variance of more than one chunk
@@ -2859,10 +2866,12 @@ struct Posterior : PostReq {
   } g = {};
 
   Posterior(gpe_ctx* ctx, const PostReq& r)
-      : PostReq(r), c(ctx), full(var != PostVar::DIAG), f32(precision == 32),
+      : PostReq(r), c(ctx), full(var != PostVar::DIAG && var != PostVar::GROUPS), f32(precision == 32),
         ozp(c->oz_on && c->n_pad >= std::min(c->oz_min_np, OZ_POST_MIN_NP) && c->n_pad <= OZ_POST_MAX_NP),
-        d(c->d), q(c->q), P(q + 1), kq(((q + 15) / 16) * 16), np(c->n_pad),
-        CHUNK(full ? POST_CHUNK_FULL : POST_CHUNK_DIAG), big(full && m > CHUNK), mtot(pad_tile(m)),
+        groups(var == PostVar::GROUPS), d(c->d), q(c->q), P(q + 1), kq(((q + 15) / 16) * 16), np(c->n_pad),
+        // (whole groups per chunk: a group never straddles two)
+        CHUNK(full ? POST_CHUNK_FULL : groups ? (POST_CHUNK_DIAG / group) * group : POST_CHUNK_DIAG),
+        big(full && m > CHUNK), mtot(pad_tile(m)),
         mp0(pad_tile(std::min<long long>(CHUNK, m))), grad(r.dmean_out != nullptr) {}
 
   // Setup: the fp32 copy of L^-1 where the fp32 product needs it, [gamma, G] =
@@ -2916,7 +2925,10 @@ struct Posterior : PostReq {
     CHK(grow_buf(c, &c->dW2, &c->w2_cap, (size_t)np * mp0));
     CHK(grow_buf(c, &c->dXs, &c->xs_cap, (size_t)mp0 * d));
     CHK(grow_buf(c, &c->dXsw, &c->xsw_cap, (size_t)mp0 * d));
-    rs = (size_t)mp0 * P + mp0;
+    // (the groups' blocks take the place of the column norms: group values per point)
+    rs = (size_t)mp0 * P + (groups ? (size_t)std::min<long long>(CHUNK, m) * group : (size_t)mp0);
+    if (groups)
+      CHK(grow_buf(c, &c->dPgc, &c->pgc_cap, (size_t)pgc_nseg(np) * std::min<long long>(CHUNK, m) * group));
     CHK(ensure_small(c, 2 * rs + 64));
     // (the full covariance also stages T Kq^-T, mp x kq, at the front: the capacity is set
     // here once, so the slots never move)
@@ -3169,6 +3181,89 @@ struct Posterior : PostReq {
     return rc;
   }
 
+  // k_post_groupgram<NT> for items of cw columns
+  void launch_groupgram(int cw, dim3 g, const GroupGramArgs& a) {
+    const dim3 b(256);
+    if (cw <= 16) hipLaunchKernelGGL(k_post_groupgram<1>, g, b, 0, c->stream, a);
+    else if (cw <= 32) hipLaunchKernelGGL(k_post_groupgram<2>, g, b, 0, c->stream, a);
+    else if (cw <= 48) hipLaunchKernelGGL(k_post_groupgram<3>, g, b, 0, c->stream, a);
+    else hipLaunchKernelGGL(k_post_groupgram<4>, g, b, 0, c->stream, a);
+  }
+
+  // The blocks of groups of points, through diag()'s pipeline: behind a chunk's dev_chunk the
+  // two kernels of gpemu_postgroup.hpp leave coff rho - v_a . v_b (cdiag - |v_a|^2 on the
+  // diagonal) behind Y in the result slot; the host adds t_a . t_b, t = T Kq^-T of point(),
+  // and scales by s2, keeping the rows of T of one group at a time.
+  int group_blocks() {
+    const int G = group;
+    const long long GG = (long long)G * G;
+    std::vector<double> Tg((size_t)G * q);
+    auto host_chunk = [&](long long s0, const double* out) {
+      const long long mc = std::min(CHUNK, m - s0), mp = pad_tile(mc);
+      const double* cv = out + (size_t)mp * P;
+      for (long long g = 0; g < mc / G; ++g) {
+        for (int a = 0; a < G; ++a)
+          point(out, mp, s0, g * G + a, [&](int o, double acc) { Tg[(size_t)a * q + o] = acc; });
+        const double* src = cv + g * GG;
+        double* dst = var_out + (s0 / G + g) * GG;
+        for (int a = 0; a < G; ++a)
+          for (int b = 0; b <= a; ++b) {
+            double tt = 0.0;
+            for (int o = 0; o < q; ++o) tt += Tg[(size_t)a * q + o] * Tg[(size_t)b * q + o];
+            const double v = s2 * (src[a * G + b] + tt);
+            dst[a * G + b] = v;
+            dst[b * G + a] = v;
+          }
+      }
+    };
+    int slot = 0;
+    long long prev = -1;
+    auto pipeline = [&]() -> int {
+      for (long long s0 = 0; s0 < m; s0 += CHUNK, slot ^= 1) {
+        const long long mc = std::min(CHUNK, m - s0), mp = pad_tile(mc);
+        double* dY = c->dsmall + slot * rs;
+        double* dcov = dY + (size_t)mp * P;
+        CHK(dev_chunk(s0, pin_in[slot], dY, c->dW2));
+        GroupGramArgs a;
+        a.V = c->dW2; a.ldv = np; a.part = c->dPgc; a.np = (int)np; a.G = G; a.gpi = pgc_gpi(G);
+        a.ngroups = (int)(mc / G);
+        GroupCovArgs f;
+        f.part = c->dPgc; f.xsw = c->dXsw; f.cov = dcov; f.coff = coff; f.cdiag = cdiag;
+        f.nseg = pgc_nseg(np); f.ngroups = a.ngroups; f.G = G; f.d = d;
+        if (c->prof) HIPCHK(c, hipEventRecord(c->ev[4], c->stream));
+        launch_groupgram(a.gpi * G, dim3((unsigned)((a.ngroups + a.gpi - 1) / a.gpi), (unsigned)f.nseg), a);
+        HIPCHK(c, hipGetLastError());
+        const dim3 fg((unsigned)((a.ngroups * GG + 255) / 256));
+        if (fam == FAM_MATERN32) hipLaunchKernelGGL(k_post_groupcov<FAM_MATERN32>, fg, dim3(256), 0, c->stream, f);
+        else if (fam == FAM_MATERN52) hipLaunchKernelGGL(k_post_groupcov<FAM_MATERN52>, fg, dim3(256), 0, c->stream, f);
+        else hipLaunchKernelGGL(k_post_groupcov<FAM_GAUSS>, fg, dim3(256), 0, c->stream, f);
+        HIPCHK(c, hipGetLastError());
+        if (c->prof) {   // (profiling only: one synchronisation per chunk)
+          float ms = 0.f;
+          HIPCHK(c, hipEventRecord(c->ev[5], c->stream));
+          HIPCHK(c, hipEventSynchronize(c->ev[5]));
+          (void)hipEventElapsedTime(&ms, c->ev[4], c->ev[5]);
+          c->phase_ms[0] += ms;
+          c->phase_ms[1] += 1.0;
+        }
+        HIPCHK(c, hipMemcpyAsync(pin_out[slot], dY, ((size_t)mp * P + (size_t)mc * G) * sizeof(double),
+                                 hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipEventRecord(c->ev_pipe[slot], c->stream));
+        if (prev >= 0) {
+          HIPCHK(c, hipEventSynchronize(c->ev_pipe[slot ^ 1]));
+          host_chunk(prev, pin_out[slot ^ 1]);
+        }
+        prev = s0;
+      }
+      HIPCHK(c, hipEventSynchronize(c->ev_pipe[slot ^ 1]));
+      host_chunk(prev, pin_out[slot ^ 1]);
+      return GPE_OK;
+    };
+    const int rc = pipeline();
+    if (rc != GPE_OK) (void)hipStreamSynchronize(c->stream);   // (as diag())
+    return rc;
+  }
+
   // One block of the covariance, dst (ld) = s2 (A** - V_R^T V_C + T_R T_C^T) for the points R
   // (rows) and C (columns): the pair kernel (dg: a diagonal block, its lower tiles mirrored,
   // identity padding and s2 * rnew_scale * rnew on the diagonal), then the two products.
@@ -3286,12 +3381,14 @@ struct Posterior : PostReq {
 int posterior_impl(gpe_ctx* c, const PostReq& r) {
   CHK(check_ready(c));
   if (!c->factor_valid) return fail(c, GPE_ERR_STATE, "no resident factor (call gpe_factor)");
-  const bool to_host = r.var == PostVar::DIAG || r.var == PostVar::FULL;
+  const bool to_host = r.var == PostVar::DIAG || r.var == PostVar::FULL || r.var == PostVar::GROUPS;
   if (r.m <= 0 || !r.Xs || !r.Hs || !r.beta || !r.mean_out || (to_host && !r.var_out))
     return fail(c, GPE_ERR_ARG, "bad posterior args");
   if ((r.var == PostVar::FULL_DW3 && r.m > POST_CHUNK_FULL) ||
       (r.var == PostVar::FULL_DEV && (r.m <= POST_CHUNK_FULL || !r.dev_out)))
     return fail(c, GPE_ERR_ARG, "device-resident variance: one chunk in place, beyond one chunk a device target");
+  if (r.var == PostVar::GROUPS && (r.group < 1 || r.group > PGC_MAXG || r.m % r.group != 0 || r.precision != 64))
+    return fail(c, GPE_ERR_ARG, "bad posterior_groups args (1 <= G <= 64, m a multiple of G)");
   if (r.precision != 64 && r.precision != 32) return fail(c, GPE_ERR_ARG, "precision must be 64 or 32");
   if (r.precision == 32 && r.var != PostVar::DIAG)
     return fail(c, GPE_ERR_UNSUPPORTED, "precision 32 is for the diagonal variance");
@@ -3306,7 +3403,7 @@ int posterior_impl(gpe_ctx* c, const PostReq& r) {
   Posterior S(c, r);
   CHK(S.setup());
   CHK(S.workspace());
-  return S.full ? S.full_var() : S.diag();
+  return S.full ? S.full_var() : S.groups ? S.group_blocks() : S.diag();
 }
 
 // k_post_mean<DMAX, FAM, WIDE> for d inputs (the widths of launch_post_grad_fam)
@@ -3448,6 +3545,16 @@ int gpe_posterior_grad(gpe_ctx* c, int64_t m, const double* Xs, const double* Hs
 int gpe_posterior_mean(gpe_ctx* c, int64_t m, const double* Xs, const double* Hs, const double* beta,
                        double* mean_out) {
   return posterior_mean_impl(c, m, Xs, Hs, beta, mean_out);
+}
+
+int gpe_posterior_groups(gpe_ctx* c, int64_t m, int32_t G, const double* Xs, const double* Hs, const double* beta,
+                         double sigma, double* mean_out, double* cov_out) {
+  CHK(check_ready(c));
+  if (c->prof)   // phase 0: the group kernels' device time over the chunks, phase 1: the chunks
+    for (int i = 0; i < 8; ++i) c->phase_ms[i] = 0.0;
+  PostReq r{m, Xs, Hs, beta, sigma, 64, mean_out, PostVar::GROUPS, cov_out};
+  r.group = G;
+  return posterior_impl(c, r);
 }
 
 int gpe_noise_sample(gpe_ctx* c, int64_t m, const double* Xs, const double* Hs, const double* beta,

@@ -385,6 +385,17 @@ def posterior_mean(Dnew, Dold, par, K):
     return ctx.posterior_mean(Dnew.inputs, Dnew.H, par.beta)
 
 
+def posterior_groups(Dnew, Dold, par, K, group):
+    """(mean (m), cov (m // group, group, group)): the posterior covariance of the emulated
+    function inside groups of ``group`` consecutive points of Dnew given Dold, on the GPU
+    (gpe_posterior_groups): the block diagonal of ``Posterior``'s full covariance without the
+    other m^2 entries, for every correlation family and any m.  Dnew's own r is not added: the
+    blocks describe the emulated function, not observations of it."""
+    ctx = upload_training(Dold)
+    ctx.ensure_factor(K.kind, K.d, float(K.n), 1.0, Dold.r_scale())
+    return ctx.posterior_groups(Dnew.inputs, Dnew.H, par.beta, float(par.sigma), group)
+
+
 class Posterior:
     """Posterior mean and variance at Dnew given Dold (reference :588-676).
 

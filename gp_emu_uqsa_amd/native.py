@@ -85,6 +85,7 @@ SIGNATURES = {
     "gpe_posterior_grad": (_ct.c_int, [_VP, _ct.c_int64, _D, _D, _D, _ct.POINTER(_ct.c_int32), _D, _ct.c_double,
                                        _D, _D, _D, _D]),
     "gpe_posterior_mean": (_ct.c_int, [_VP, _ct.c_int64, _D, _D, _D, _D]),
+    "gpe_posterior_groups": (_ct.c_int, [_VP, _ct.c_int64, _ct.c_int32, _D, _D, _D, _ct.c_double, _D, _D]),
     "gpe_noise_sample": (_ct.c_int, [_VP, _ct.c_int64, _D, _D, _D, _ct.c_double, _D, _ct.c_double,
                                      _D, _ct.c_int32, _D, _D, _D]),
     "gpe_posterior_pivchol": (_ct.c_int, [_VP, _ct.c_int64, _D, _D, _D, _ct.c_double, _D, _ct.c_double,
@@ -365,6 +366,26 @@ class Context:
         self._check(self.lib.gpe_posterior_mean(self._h, m, _ptr(Xs), _ptr(Hs), _ptr(beta), _ptr(mean)),
                     "gpe_posterior_mean")
         return mean
+
+    def posterior_groups(self, Xs, Hs, beta, sigma, group):
+        """(mean (m), cov (m // group, group, group)): the posterior covariance inside groups of
+        `group` consecutive points (gpe_posterior_groups), the block diagonal of
+        posterior(full_var=True)'s matrix without its other entries; any m that is a multiple
+        of group, 1 <= group <= 64.  Blocks are exactly symmetric, a group's block does not
+        depend on the other groups, and repeated calls return the same bits."""
+        Xs = _f64(Xs)
+        if Xs.ndim == 1:
+            Xs = Xs.reshape(-1, 1)
+        m = Xs.shape[0]
+        group = int(group)
+        Hs = _f64(Hs, (m, self.q))
+        beta = _f64(beta).ravel()
+        mean = _np.zeros(m)
+        ng = m // group if group >= 1 and m % group == 0 else 0   # (the library rejects the rest)
+        cov = _np.zeros((ng, max(group, 0), max(group, 0)))
+        self._check(self.lib.gpe_posterior_groups(self._h, m, group, _ptr(Xs), _ptr(Hs), _ptr(beta), float(sigma),
+                                                  _ptr(mean), _ptr(cov)), "gpe_posterior_groups")
+        return mean, cov
 
     def noise_sample(self, Xs, Hs, beta, sigma, t, U, r_new=None, r_scale=0.0):
         """noise_fit's estimation step for the resident factor: the posterior at Xs

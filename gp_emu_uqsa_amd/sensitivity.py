@@ -31,15 +31,22 @@ with b = 1/v, c = 1/delta^2, P1 = b/(b+2c), P2 = c b/(b+2c), P4 = sqrt(b/(b+4c))
 The reference's totaleffectvariance (:405-463) forms Qw/Sw/Pw/Uw for w = [P]
 before swapping w and wb, so its E(V) is senseindex[P] and EVTw[P] = uEV -
 senseindex[P]. This is reproduced as is.
+
+Without closed forms (any correlation family, normal or uniform inputs), by Monte Carlo on a
+Sobol' design: ``mc_indices`` / ``mc_main_effect`` for the posterior mean as a function (one
+gpe_posterior_mean call), and ``mc_emulator_indices`` for the measures that carry the
+emulator's own uncertainty (var*[E f], E*[Var f], E*[V_i] and the true E*[V_Ti]), from the
+posterior covariance inside the design's groups of d + 2 points (one gpe_posterior_groups call).
 """
 from __future__ import annotations
 
 import numpy as np
 
-from .model import Data, posterior_gradient, posterior_mean, upload_training
+from .model import Data, posterior_gradient, posterior_groups, posterior_mean, upload_training
 
 __all__ = ["setup", "sense_table", "Sensitivity", "NonGaussianKernel", "derivative_measures",
-           "sobol_points", "sobol_estimates", "mc_indices", "mc_main_effect"]
+           "sobol_points", "sobol_estimates", "mc_indices", "mc_main_effect",
+           "sobol_group_estimates", "mc_emulator_indices"]
 
 
 class NonGaussianKernel(ValueError):
@@ -173,6 +180,77 @@ def mc_main_effect(emul, m, v, points=100, samples=10000, seed=0, w=None, dist="
             out[key][P] = np.nan
             out[key][P, at] = val
     return out
+
+
+def sobol_group_estimates(f, C):
+    """Uncertainty and sensitivity measures WITH the emulator's own uncertainty, by Monte Carlo
+    from the posterior mean and the posterior covariance inside the groups of a Sobol' design
+    (host only).  f is N x (d + 2) and C is N x (d + 2) x (d + 2): the mean and covariance at
+    the points [A_a, B_a, AB_0_a, ..., AB_d-1_a] of sample a, AB_i being A with column i taken
+    from B.  Two points of a group are independent draws (A, B), share one coordinate (B, AB_i)
+    or share all but one (A, AB_i), which is every pair the integrals below range over.
+
+    Every term is the mean of its N per-sample values, with ``*_se`` = std(ddof = 1) / sqrt(N):
+      uE      E*[E f]       1/2 (fA + fB)
+      uV      var*[E f]     c(A, B)
+      uEV     E*[Var f]     1/2 (fA - fB)^2 + 1/2 (c(A, A) + c(B, B)) - c(A, B)
+      EV[i]   E*[V_i]       fB (fAB_i - fA) + c(B, AB_i) - c(A, B)
+      EVT[i]  E*[V_Ti]      1/2 (fA - fAB_i)^2 + 1/2 (c(A, A) + c(AB_i, AB_i)) - c(A, AB_i)
+      S, ST                 EV / uEV, EVT / uEV
+      V, VT (and _se)       the mean-only terms of ``sobol_estimates``: the above without c
+    EVT is the true total-effect variance E*[E[Var(f | x_-i)]], not the reference's
+    ``uEV - senseindex[P]`` (see the module docstring)."""
+    f = np.asarray(f, dtype=float)
+    C = np.asarray(C, dtype=float)
+    if f.ndim != 2 or f.shape[1] < 3 or C.shape != (f.shape[0], f.shape[1], f.shape[1]):
+        raise ValueError("f must be N x (d + 2) and C N x (d + 2) x (d + 2)")
+    N = f.shape[0]
+    fA, fB, fAB = f[:, 0], f[:, 1], f[:, 2:].T                 # (N), (N), (d x N)
+    cAA, cBB, cAB = C[:, 0, 0], C[:, 1, 1], C[:, 0, 1]
+    cii = np.diagonal(C, axis1=1, axis2=2)[:, 2:].T            # c(AB_i, AB_i)
+    cBi, cAi = C[:, 1, 2:].T, C[:, 0, 2:].T                    # c(B, AB_i), c(A, AB_i)
+    tV = fB[None, :] * (fAB - fA[None, :])
+    tT = 0.5 * (fA[None, :] - fAB) ** 2
+    terms = {"uE": 0.5 * (fA + fB), "uV": cAB,
+             "uEV": 0.5 * (fA - fB) ** 2 + 0.5 * (cAA + cBB) - cAB,
+             "EV": tV + cBi - cAB[None, :],
+             "EVT": tT + 0.5 * (cAA[None, :] + cii) - cAi,
+             "V": tV, "VT": tT}
+    out = {}
+    for key, t in terms.items():
+        val, se = t.mean(axis=-1), t.std(axis=-1, ddof=1) / np.sqrt(N)
+        out[key], out[key + "_se"] = (float(val), float(se)) if t.ndim == 1 else (val, se)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        out["S"], out["ST"] = out["EV"] / out["uEV"], out["EVT"] / out["uEV"]
+    return out
+
+
+def mc_emulator_indices(emul, m, v, samples, seed=0, dist="normal"):
+    """The uncertainty and sensitivity measures that carry the emulator's own uncertainty --
+    var*[E f], E*[Var f], E*[V_i], E*[V_Ti] -- by Monte Carlo, for inputs with means m and
+    variances v: ``sobol_group_estimates``' dict on the design of ``sobol_points`` (the one
+    ``mc_indices`` uses at the same seed), interleaved sample by sample into groups
+    [A_a, B_a, AB_0_a, ..., AB_d-1_a] of d + 2 points and evaluated in ONE posterior-groups call
+    (gpe_posterior_groups: the covariance inside each group and nothing else).
+
+    No closed form is involved, so this works for every correlation family and both input
+    distributions: it gives a Matern emulator, on which ``setup`` raises ``NonGaussianKernel``,
+    what ``uncertainty()``, ``sensitivity()`` and ``totaleffectvariance()`` report for the
+    Gaussian kernel.  EVT is the true total-effect variance, not the reference's
+    ``uEV - senseindex[P]``.  d + 2 <= 64, else ValueError."""
+    d = emul.training.inputs.shape[1]
+    if d + 2 > 64:
+        raise ValueError("mc_emulator_indices takes at most 62 inputs (groups of d + 2 <= 64 points), not %d" % d)
+    N = int(samples)
+    A, B = sobol_points(d, N, seed, dist, m, v)
+    X = np.empty((N, d + 2, d))
+    X[:, 0], X[:, 1] = A, B
+    for i in range(d):
+        X[:, 2 + i] = A
+        X[:, 2 + i, i] = B[:, i]
+    xs = Data(X.reshape(N * (d + 2), d), None, emul.basis, emul.par, emul.beliefs, emul.K)
+    f, C = posterior_groups(xs, emul.training, emul.par, emul.K, d + 2)
+    return sobol_group_estimates(f.reshape(N, d + 2), C)
 
 
 def setup(emul, m, v, case="case2"):

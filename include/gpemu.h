@@ -36,9 +36,9 @@ extern "C" {
                                 gpe_device_synchronize, gpe_build_id;
                                 9: gpe_dist_local_rows takes the basis width q;
                                 10: gpe_ozaki_stats (gpe_loo, gpe_posterior_pivchol,
-                                gpe_posterior_grad, gpe_posterior_mean and the test hooks gpe_test_oz_product and
-                                gpe_test_gemm_group were added within 10: additions, nothing
-                                existing changed) */
+                                gpe_posterior_grad, gpe_posterior_mean, gpe_posterior_groups and the test
+                                hooks gpe_test_oz_product and gpe_test_gemm_group were added within 10:
+                                additions, nothing existing changed) */
 
 enum gpe_status {
     GPE_OK = 0,
@@ -214,6 +214,32 @@ int gpe_posterior_grad(gpe_ctx* ctx, int64_t m, const double* Xs, const double* 
  * GPE_NOT_PD if H^T A^-1 H is not positive definite, as gpe_posterior. */
 int gpe_posterior_mean(gpe_ctx* ctx, int64_t m, const double* Xs, const double* Hs,
                        const double* beta, double* mean_out);
+
+/* Posterior covariance inside groups of G consecutive points (an addition within ABI 10): the
+ * block diagonal of the m x m covariance in blocks of G, which the m^2 entries of full_var = 1
+ * cannot give at the 10^5 .. 10^6 points of a Sobol' design.  The m points form m / G groups;
+ * mean_out (m); cov_out (m / G) x G x G row-major, block g entry (a, b) = the posterior
+ * covariance of points g G + a and g G + b with gpe_posterior(full_var = 1, precision = 64)'s
+ * conventions:
+ *   a == b   s2 (cdiag - |v_a|^2 + |t_a|^2)
+ *   a != b   s2 (coff rho(s_ab) - v_a . v_b + t_a . t_b),   v = L^-1 K*, t = T Kq^-T
+ * "diagonal" by index, never by coordinates: two different points of a group with equal
+ * coordinates get the off-diagonal form.  The lower triangle is formed and mirrored, so every
+ * block is exactly symmetric.  fp64 accuracy only (V from the int8 product where gpe_posterior
+ * would take it there, from the fp64 GEMM otherwise); every family and nugget kind, with or
+ * without r.  Any m: chunks of floor(8192 / G) G points (a group never straddles two) go
+ * through the diagonal pipeline's two slots, the host part of one chunk beside the device work
+ * of the next.  Per chunk two kernels (gpemu_postgroup.hpp) read V once in place of the
+ * column norms: the G x G Grams on the fp64 matrix cores, then their finish with rho from the
+ * scaled points.  Every Gram sum runs over the training rows in segments of 1024 added in
+ * index order whatever m, G and the group's place are: a group's block does not depend on the
+ * other groups of the call, repeated calls return the same bits, there are no floating-point
+ * atomics and no waits between workgroups.  The resident factor and what other entries keep
+ * of it stay as they are.
+ * GPE_ERR_STATE without a resident factor; GPE_ERR_ARG for m <= 0, G outside [1, 64], m not a
+ * multiple of G or a NULL pointer; GPE_NOT_PD as gpe_posterior. */
+int gpe_posterior_groups(gpe_ctx* ctx, int64_t m, int32_t G, const double* Xs, const double* Hs,
+                         const double* beta, double sigma, double* mean_out, double* cov_out);
 
 /* ---- Sensitivity / UQ building blocks, resident factor --------
  * Replace the O(n^2) parts of sensitivity/_sensitivityclasses.py (case2): the
@@ -457,6 +483,8 @@ int gpe_posterior_pivchol(gpe_ctx* ctx, int64_t m, const double* Xs, const doubl
  * number of chunks (one synchronisation per chunk is added).
  * After gpe_posterior_mean: [0] k_post_mean's device time summed over the chunks, [1] the
  * number of chunks (one synchronisation per chunk is added).
+ * After gpe_posterior_groups: [0] the device time of k_post_groupgram and k_post_groupcov
+ * summed over the chunks, [1] the number of chunks (one synchronisation per chunk is added).
  * Only filled when profiling is on. */
 int gpe_set_profiling(gpe_ctx* ctx, int32_t on);
 int gpe_phase_times(gpe_ctx* ctx, double* ms_out, int32_t n);
