@@ -1589,14 +1589,13 @@ int oz_prepare(gpe_ctx* c, Fact& F) {
   c->oz_chol_ready = false;
   c->oz_l21_valid = false;
   CHK(build_plan(c, F));
-  const int NT2 = np2 / OZ_T, N = c->oz_nmod;
+  const int N = c->oz_nmod;
   size_t planes = (size_t)oz_plane_bytes(np2) * N;
-  size_t resid = (size_t)NT2 * (NT2 + 1) / 2 * OZ_T * OZ_T * N;
+  size_t resid = (size_t)oz_lauum_shape(np2).res_bytes() * N;
   size_t scratch = 0, nex = (size_t)np2;
-  std::vector<unsigned> all = oz_list(NT2, NT2, true, [&](int ti, int) { return (double)(np2 - OZ_T * ti); });
+  std::vector<unsigned> all = oz_lauum_shape(np2).list();
   c->oz_list_len = (int)all.size();
-  c->oz_lauum_ops = 0.0;
-  for (int ti = 0; ti < NT2; ++ti) c->oz_lauum_ops += 2.0 * OZ_T * OZ_T * (ti + 1) * (double)(np2 - OZ_T * ti) * N;
+  c->oz_lauum_ops = oz_lauum_shape(np2).ops(N);
   c->oz_tri.clear();
   for (const auto& prs : F.plan.tri_pairs) {
     if (!oz_tri_level(c, prs)) continue;
@@ -1616,15 +1615,14 @@ int oz_prepare(gpe_ctx* c, Fact& F) {
     for (const OzTriPair& q : c->oz_tri)
       if (q.t0 == 0 && q.h == hs && q.t1 == F.NB) have = &q;
     const OzTriPair q = have ? *have : oz_tri_pair_plan(0, hs, F.NB, N, all);
-    const int nts = q.Pb / OZ_T;
-    const std::vector<unsigned> ls = oz_list(nts, nts, true, [&](int, int) { return (double)q.Pa; });
+    const std::vector<unsigned> ls = q.shape_schur().list();
     c->oz_chol_q = q;
     c->oz_chol_loff = (long long)all.size();
     c->oz_chol_llen = (int)ls.size();
     all.insert(all.end(), ls.begin(), ls.end());
-    c->oz_chol_ops = 2.0 * OZ_T * OZ_T * (double)q.Pa * N * (nts * (nts + 1) / 2);
+    c->oz_chol_ops = q.shape_schur().ops(N);
     planes = std::max(planes, (size_t)N * q.Pb * q.Pa);
-    resid = std::max(resid, (size_t)N * (nts * (size_t)(nts + 1) / 2) * OZ_T * OZ_T);
+    resid = std::max(resid, (size_t)q.shape_schur().res_bytes() * N);
     nex = std::max(nex, (size_t)q.Pb);
     c->oz_chol_ready = true;
   }
@@ -1640,36 +1638,29 @@ int oz_prepare(gpe_ctx* c, Fact& F) {
   return GPE_OK;
 }
 
-// one k_oz_gemm + k_oz_crt pair with the constants k: tile rows [r.ti0, r.ti0 + nti)
-int oz_gemm_crt(gpe_ctx* c, const OzConst& k, const OzGemm& g, const OzCrt& r, int nti, double ops, double flops64,
+// one product (oz_product_launch) on stream st (null: the context's); while profiling, between
+// two events of the pool, and counted in gpe_ozaki_stats
+int oz_gemm_crt(gpe_ctx* c, const OzConst& k, const OzProduct& p, double ops, double flops64,
                 hipStream_t st = nullptr) {
   if (!st) st = c->stream;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
   if (c->prof) {
     while (c->oev_used + 2 > c->oev.size()) {
       hipEvent_t e;
       HIPCHK(c, hipEventCreate(&e));
       c->oev.push_back(e);
     }
-    HIPCHK(c, hipEventRecord(c->oev[c->oev_used], st));
+    e0 = c->oev[c->oev_used];
+    e1 = c->oev[c->oev_used + 1];
   }
-  oz_gemm_launch(st, g, k);
+  HIPCHK(c, oz_product_launch(st, k, p, e0, e1));
   if (c->prof) {
-    HIPCHK(c, hipEventRecord(c->oev[c->oev_used + 1], st));
     c->oev_used += 2;
     c->oz_launches += 1.0;
     c->oz_ops += ops;
     c->oz_flops64 += flops64;
   }
-  const int t1 = r.ti0 + nti;   // (lower tiles of the rows from ti0: those up to t1 less those above ti0)
-  hipLaunchKernelGGL(k_oz_crt, dim3((g.tri ? t1 * (t1 + 1) / 2 - r.ti0 * (r.ti0 + 1) / 2 : nti * g.ntj) * 16), dim3(256),
-                     0, st, r, k);
-  HIPCHK(c, hipGetLastError());
   return GPE_OK;
-}
-// ... with the context's constants (oz_prepare)
-int oz_gemm_crt(gpe_ctx* c, const OzGemm& g, const OzCrt& r, int nti, double ops, double flops64,
-                hipStream_t st = nullptr) {
-  return oz_gemm_crt(c, c->oz_c, g, r, nti, ops, flops64, st);
 }
 
 // Between the phases of the split sweep (potrf), in its stream order on st: L11 and L21 are
@@ -1684,24 +1675,14 @@ int chol_schur(gpe_ctx* c, Fact& F, hipStream_t st, bool with_aug) {
   if (!c->oz_chol_ready || q.h != pl.split_h) return fail(c, GPE_ERR_STATE, "internal error: split Cholesky without an int8 plan");
   if (with_aug) CHK(launch_gemm_range(c, pl.launches[pl.aug_mid], st));
   const long long ld = F.n_pad;
-  oz_l21_launch(st, c->oz_c, q, F.A + (long long)q.h * TILE, ld, c->dozp, c->dozx);
+  oz_operand(st, c->oz_c, q.l21(F.A + (long long)q.h * TILE, ld), q.Pb, q.Pa, c->dozx, c->dozp);
   HIPCHK(c, hipGetLastError());
-  const int nts = q.Pb / OZ_T;
-  const long long pA = (long long)q.Pb * q.Pa, rb = (long long)nts * (nts + 1) / 2 * OZ_T * OZ_T;
-  OzGemm g;
-  g.a = g.b = OzOpnd{c->dozp, pA, q.Pa, 0};
-  g.list = c->dozl + c->oz_chol_loff;
-  g.list_len = c->oz_chol_llen;
-  g.K = q.Pa;
-  g.kbeg = 0;
-  g.kend = 0;
-  g.tri = 1;
-  g.ntj = 0;
-  g.res = c->dozr;
-  g.res_bytes = rb;
-  OzCrt r{c->dozr, rb, 1, 0, c->dozx, c->dozx, F.A + (long long)q.h * TILE * (ld + 1), ld, q.Rb, q.Rb, 1, -1.0};
-  r.acc = 1;
-  CHK(oz_gemm_crt(c, g, r, nts, c->oz_chol_ops, (double)q.Rb * q.Rb * q.Ra, st));
+  const OzShape s = q.shape_schur();
+  const OzOpnd l21{c->dozp, (long long)q.Pb * q.Pa, q.Pa, 0};
+  CHK(oz_gemm_crt(c, c->oz_c,
+                  OzProduct{s, l21, l21, c->dozl + c->oz_chol_loff, c->oz_chol_llen, c->dozr, s.res_bytes(),
+                            OzOut{c->dozx, c->dozx, F.A + (long long)q.h * TILE * (ld + 1), ld, q.Rb, q.Rb, 1, -1.0, 1}},
+                  c->oz_chol_ops, (double)q.Rb * q.Rb * q.Ra, st));
   c->oz_l21_valid = true;
   return GPE_OK;
 }
@@ -1709,27 +1690,15 @@ int chol_schur(gpe_ctx* c, Fact& F, hipStream_t st, bool with_aug) {
 // A^-1 = X^T X (lower 128-tiles) of the workspace's X = L^-1 (F.B) into F.A
 int lauum_ozaki(gpe_ctx* c, Fact& F) {
   CHK(oz_prepare(c, F));
-  const int np = (int)F.n_pad, np2 = c->oz_np2, NT2 = np2 / OZ_T;
-  const OzConst& k = c->oz_c;
-  const long long pb = oz_plane_bytes(np2), rb = (long long)NT2 * (NT2 + 1) / 2 * OZ_T * OZ_T;
+  const int np = (int)F.n_pad, np2 = c->oz_np2;
   c->oz_l21_valid = false;
-  hipLaunchKernelGGL(k_oz_colexp, dim3((np2 + 3) / 4), dim3(256), 0, c->stream, F.B, (long long)F.n_pad, np, np2,
-                     k.beta, c->dozx);
-  hipLaunchKernelGGL(k_oz_split, dim3(np2, (np2 + 256 * OZ_SPLIT_ROWS - 1) / (256 * OZ_SPLIT_ROWS)), dim3(256), 0,
-                     c->stream, F.B, (long long)F.n_pad, np, np2, c->dozx, c->dozp, pb, k);
-  OzGemm g;
-  g.a = g.b = OzOpnd{c->dozp, pb, 0, np2};
-  g.list = c->dozl;
-  g.list_len = c->oz_list_len;
-  g.K = np2;
-  g.kbeg = 1;
-  g.kend = 0;
-  g.tri = 1;
-  g.ntj = 0;
-  g.res = c->dozr;
-  g.res_bytes = rb;
-  OzCrt r{c->dozr, rb, 1, 0, c->dozx, c->dozx, F.A, (long long)F.n_pad, np, np, 1, 1.0};
-  return oz_gemm_crt(c, g, r, NT2, c->oz_lauum_ops, (double)np * np * np / 3.0);
+  oz_operand_packed(c->stream, c->oz_c, F.B, (long long)F.n_pad, np, np2, c->dozx, c->dozp);
+  const OzShape s = oz_lauum_shape(np2);
+  const OzOpnd x{c->dozp, oz_plane_bytes(np2), 0, np2};
+  return oz_gemm_crt(c, c->oz_c,
+                     OzProduct{s, x, x, c->dozl, c->oz_list_len, c->dozr, s.res_bytes(),
+                               OzOut{c->dozx, c->dozx, F.A, (long long)F.n_pad, np, np, 1, 1.0}},
+                     c->oz_lauum_ops, (double)np * np * np / 3.0);
 }
 
 // the int8 plan of TRTRI pair (t0, h, t1) (oz_prepare)
@@ -1739,10 +1708,11 @@ const OzTriPair* oz_pair(const gpe_ctx* c, int t0, int h, int t1) {
   return nullptr;
 }
 
-// the first product's L21 side (oz_l21_launch) on stream st
+// the first product's L21 side (OzTriPair::l21) on stream st
 int oz_l21(gpe_ctx* c, Fact& F, const OzTriPair& q, hipStream_t st) {
   c->oz_l21_valid = false;
-  oz_l21_launch(st, c->oz_c, q, F.A + (long long)q.h * TILE + (long long)q.t0 * TILE * F.n_pad, F.n_pad, c->dozp, c->dozx);
+  oz_operand(st, c->oz_c, q.l21(F.A + (long long)q.h * TILE + (long long)q.t0 * TILE * F.n_pad, F.n_pad), q.Pb, q.Pa,
+             c->dozx, c->dozp);
   HIPCHK(c, hipGetLastError());
   return GPE_OK;
 }
@@ -1774,8 +1744,8 @@ int trtri_pair_ozaki(gpe_ctx* c, Fact& F, int t0, int h, int t1, int l21) {
   int rc = GPE_OK;
   oz_tri_pair_launches(c->stream, c->oz_c, *qp, c->dozl, tile(F.A, h, t0), tile(F.B, t0, t0), tile(F.B, h, h),
                        tile(F.B, h, t0), ld, c->dozt, c->dozp, c->dozr, c->dozx, l21 != 0,
-                       [&](const OzGemm& g, const OzCrt& r, int nti, double ops, double fl) {
-                         if (rc == GPE_OK) rc = oz_gemm_crt(c, g, r, nti, ops, fl);
+                       [&](const OzProduct& p, double ops, double fl) {
+                         if (rc == GPE_OK) rc = oz_gemm_crt(c, c->oz_c, p, ops, fl);
                        });
   CHK(rc);
   HIPCHK(c, hipGetLastError());
@@ -2521,28 +2491,24 @@ static int posterior_oz(gpe_ctx* c, bool f32, const double* Ks, long long mp, do
   const int mp2 = (int)((mp + OZ_T - 1) / OZ_T * OZ_T);
   const int N = posterior_nmod(np2, f32), nti = np2 / OZ_T, ntj = mp2 / OZ_T;
   const OzConst k = oz_consts(N, np2);
+  const OzShape s = OzShape::rect(nti, ntj, np2, 0, 1);
   hipStream_t st = c->stream;
   if (!c->px_valid || c->px_nmod != N) {
     CHK(grow_buf(c, &c->dpxp, &c->pxp_cap, (size_t)N * np2 * np2));
     CHK(grow_buf(c, &c->dpxe, &c->pxe_cap, (size_t)np2));
-    HIPCHK(c, hipMemsetAsync(c->dpxe, 0, (size_t)np2 * sizeof(int), st));
-    hipLaunchKernelGGL(k_oz_rowexp<true>, dim3(np2 / 64, (np + 255) / 256), dim3(256), 0, st, c->tr.B, (long long)np,
-                       np, np2, np, 2, k.beta, c->dpxe);
-    hipLaunchKernelGGL(k_oz_il_to_ex, dim3((np2 + 255) / 256), dim3(256), 0, st, c->dpxe, np2, k.beta);
-    hipLaunchKernelGGL(k_oz_split_rect<true>, dim3(np2 / 64, np2 / 64), dim3(256), 0, st, c->tr.B, (long long)np, np,
-                       np, 2, c->dpxe, c->dpxp, (long long)np2 * np2, (long long)np2, np2, k);
+    oz_operand(st, k, OzSrc{c->tr.B, (long long)np, np, np, 2, true}, np2, np2, c->dpxe, c->dpxp);
     HIPCHK(c, hipGetLastError());
     c->px_valid = true;
     c->px_nmod = N;
   }
-  const long long pB = (long long)mp2 * np2, rb = (long long)nti * ntj * OZ_T * OZ_T;
+  const long long pB = (long long)mp2 * np2, rb = s.res_bytes();
   // (the diagonal posterior queues chunk i + 1 while chunk i runs: a new tile list or larger
   // buffers wait for it)
   if (c->pl_nti != nti || c->pl_ntj != ntj || (size_t)N * pB > c->pkp_cap || (size_t)mp2 > c->pke_cap ||
       (size_t)N * rb > c->pres_cap)
     HIPCHK(c, hipStreamSynchronize(st));
   if (c->pl_nti != nti || c->pl_ntj != ntj) {
-    const std::vector<unsigned> l = oz_list(nti, ntj, false, [&](int ti, int) { return (double)(OZ_T * (ti + 1)); });
+    const std::vector<unsigned> l = s.list();
     c->pl_nti = c->pl_ntj = 0;
     CHK(grow_buf(c, &c->dpl, &c->pl_cap, l.size()));
     HIPCHK(c, hipMemcpy(c->dpl, l.data(), l.size() * sizeof(unsigned), hipMemcpyHostToDevice));
@@ -2553,26 +2519,12 @@ static int posterior_oz(gpe_ctx* c, bool f32, const double* Ks, long long mp, do
   CHK(grow_buf(c, &c->dpkp, &c->pkp_cap, (size_t)N * pB));
   CHK(grow_buf(c, &c->dpke, &c->pke_cap, (size_t)mp2));
   CHK(grow_buf(c, &c->dpres, &c->pres_cap, (size_t)N * rb));
-  hipLaunchKernelGGL(k_oz_rowexp<false>, dim3(mp2 / 4), dim3(256), 0, st, Ks, (long long)np, (int)mp, mp2, np, 0, k.beta,
-                     c->dpke);
-  hipLaunchKernelGGL(k_oz_split_rect<false>, dim3(mp2, (np2 + 2047) / 2048), dim3(256), 0, st, Ks, (long long)np,
-                     (int)mp, np, 0, c->dpke, c->dpkp, pB, (long long)np2, np2, k);
-  OzGemm g;
-  g.a = OzOpnd{c->dpxp, (long long)np2 * np2, np2, 0};
-  g.b = OzOpnd{c->dpkp, pB, np2, 0};
-  g.list = c->dpl;
-  g.list_len = c->pl_len;
-  g.K = np2;
-  g.kbeg = 0;
-  g.kend = 1;
-  g.tri = 0;
-  g.ntj = ntj;
-  g.res = c->dpres;
-  g.res_bytes = rb;
-  oz_gemm_launch(st, g, k);
-  OzCrt r{c->dpres, rb, 0, ntj, c->dpxe, c->dpke, V, (long long)np, np, (int)mp, 0, 1.0};
-  hipLaunchKernelGGL(k_oz_crt, dim3((unsigned)(nti * ntj * 16)), dim3(256), 0, st, r, k);
-  HIPCHK(c, hipGetLastError());
+  oz_operand(st, k, OzSrc{Ks, (long long)np, (int)mp, np, 0, false}, mp2, np2, c->dpke, c->dpkp);
+  // (no events: not a product of the objective, kept out of gpe_ozaki_stats)
+  const OzOpnd linv{c->dpxp, (long long)np2 * np2, np2, 0}, kstar{c->dpkp, pB, np2, 0};
+  HIPCHK(c, oz_product_launch(st, k,
+                              OzProduct{s, linv, kstar, c->dpl, c->pl_len, c->dpres, rb,
+                                        OzOut{c->dpxe, c->dpke, V, (long long)np, np, (int)mp, 0, 1.0}}));
   return GPE_OK;
 }
 
@@ -4088,29 +4040,14 @@ static long long oz_test_extent(const gpe_oz_operand& o, int R, int Kv) {
 }
 
 // a rectangular operand: source to the device, row exponents, planes (P rows of Kp bytes per
-// modulus), with the launch lines of oz_l21_launch / oz_tri_pair_launches / posterior_oz
+// modulus) by oz_operand, the call every production site converts its operands with
 static int oz_test_operand(gpe_ctx* c, const gpe_oz_operand& o, const OzConst& k, int P, int Kp, double** dsrc, int** dex,
                            int8_t** dpl) {
-  hipStream_t st = c->stream;
   CHK(dalloc(c, dsrc, (size_t)o.len));
   CHK(dalloc(c, dex, (size_t)P));
   CHK(dalloc(c, dpl, (size_t)k.nmod * P * Kp));
   HIPCHK(c, hipMemcpy(*dsrc, o.src, (size_t)o.len * sizeof(double), hipMemcpyHostToDevice));
-  const double* s = *dsrc + o.offset;
-  const long long pb = (long long)P * Kp;
-  if (o.trans) {
-    HIPCHK(c, hipMemsetAsync(*dex, 0, (size_t)P * sizeof(int), st));
-    hipLaunchKernelGGL(k_oz_rowexp<true>, dim3(P / 64, (o.Kv + 255) / 256), dim3(256), 0, st, s, (long long)o.ld, o.R, P,
-                       o.Kv, o.mask, k.beta, *dex);
-    hipLaunchKernelGGL(k_oz_il_to_ex, dim3((P + 255) / 256), dim3(256), 0, st, *dex, P, k.beta);
-    hipLaunchKernelGGL(k_oz_split_rect<true>, dim3(P / 64, Kp / 64), dim3(256), 0, st, s, (long long)o.ld, o.R, o.Kv,
-                       o.mask, *dex, *dpl, pb, (long long)Kp, Kp, k);
-  } else {
-    hipLaunchKernelGGL(k_oz_rowexp<false>, dim3(P / 4), dim3(256), 0, st, s, (long long)o.ld, o.R, P, o.Kv, o.mask,
-                       k.beta, *dex);
-    hipLaunchKernelGGL(k_oz_split_rect<false>, dim3(P, (Kp + 2047) / 2048), dim3(256), 0, st, s, (long long)o.ld, o.R,
-                       o.Kv, o.mask, *dex, *dpl, pb, (long long)Kp, Kp, k);
-  }
+  oz_operand(c->stream, k, OzSrc{*dsrc + o.offset, (long long)o.ld, o.R, o.Kv, o.mask, o.trans != 0}, P, Kp, *dex, *dpl);
   HIPCHK(c, hipGetLastError());
   return GPE_OK;
 }
@@ -4146,58 +4083,38 @@ static int oz_test_product(gpe_ctx* c, const gpe_oz_operand& a, const gpe_oz_ope
   if (p.rows <= OZ_T * p.ti0 || p.rows > Pa || p.cols < 1 || p.cols > Pb) return bad("rows / cols outside the product");
   if (!C || p.ldc < 1 || p.c_len < 1 || (long long)(p.rows - 1 - OZ_T * p.ti0) + (long long)(p.cols - 1) * p.ldc >= p.c_len)
     return bad("C too small for rows x cols at ldc");
-  const int K = p.K, ti0 = p.ti0, nti = Pa / OZ_T - ti0, ntj = Pb / OZ_T, t1 = ti0 + nti;
+  const int K = p.K, ti0 = p.ti0, nti = Pa / OZ_T - ti0, ntj = Pb / OZ_T;
   const OzConst k = oz_consts(p.nmod, K);
+  const OzShape s{nti, p.tri ? 0 : ntj, ti0, p.tri ? 1 : 0, K, p.kbeg, p.kend, p.kdiv};
   OzTestBufs d;
   hipStream_t st = c->stream;
-  OzGemm g;
+  OzOpnd oa, ob;
   if (p.packed) {
-    const long long pbytes = oz_plane_bytes(Pa);
     CHK(dalloc(c, &d.sa, (size_t)a.len));
     CHK(dalloc(c, &d.exa, (size_t)Pa));
-    CHK(dalloc(c, &d.pa, (size_t)k.nmod * pbytes));
+    CHK(dalloc(c, &d.pa, (size_t)k.nmod * oz_plane_bytes(Pa)));
     HIPCHK(c, hipMemcpy(d.sa, a.src, (size_t)a.len * sizeof(double), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_oz_colexp, dim3((Pa + 3) / 4), dim3(256), 0, st, d.sa + a.offset, (long long)a.ld, a.R, Pa,
-                       k.beta, d.exa);
-    hipLaunchKernelGGL(k_oz_split, dim3(Pa, (Pa + 256 * OZ_SPLIT_ROWS - 1) / (256 * OZ_SPLIT_ROWS)), dim3(256), 0, st,
-                       d.sa + a.offset, (long long)a.ld, a.R, Pa, d.exa, d.pa, pbytes, k);
+    oz_operand_packed(st, k, d.sa + a.offset, (long long)a.ld, a.R, Pa, d.exa, d.pa);
     HIPCHK(c, hipGetLastError());
-    g.a = g.b = OzOpnd{d.pa, pbytes, 0, Pa};
+    oa = ob = OzOpnd{d.pa, oz_plane_bytes(Pa), 0, Pa};
   } else {
     CHK(oz_test_operand(c, a, k, Pa, K, &d.sa, &d.exa, &d.pa));
-    g.a = g.b = OzOpnd{d.pa, (long long)Pa * K, K, 0};
+    oa = ob = OzOpnd{d.pa, (long long)Pa * K, K, 0};
     if (b) {
       CHK(oz_test_operand(c, *b, k, Pb, K, &d.sb, &d.exb, &d.pb));
-      g.b = OzOpnd{d.pb, (long long)Pb * K, K, 0};
+      ob = OzOpnd{d.pb, (long long)Pb * K, K, 0};
     }
   }
-  const std::vector<unsigned> list = oz_list(nti, p.tri ? t1 : ntj, p.tri != 0, [&](int ti, int tj) {
-    const int kb = p.kbeg == 1 ? OZ_T * ti : (p.kbeg == 2 ? OZ_T * tj : (p.kbeg == 3 ? 128 * ((2 * ti) / p.kdiv) : 0));
-    return (double)std::max(0, (p.kend ? std::min(K, OZ_T * (ti + 1)) : K) - kb);
-  }, ti0);
-  const long long ntiles = p.tri ? (long long)t1 * (t1 + 1) / 2 - (long long)ti0 * (ti0 + 1) / 2 : (long long)nti * ntj;
-  const long long rb = ntiles * OZ_T * OZ_T;
+  const std::vector<unsigned> list = s.list();
+  const long long rb = s.res_bytes();
   CHK(dalloc(c, &d.list, list.size()));
   CHK(dalloc(c, &d.res, (size_t)k.nmod * rb));
   CHK(dalloc(c, &d.C, (size_t)p.c_len));
   HIPCHK(c, hipMemcpy(d.list, list.data(), list.size() * sizeof(unsigned), hipMemcpyHostToDevice));
   HIPCHK(c, hipMemcpy(d.C, C, (size_t)p.c_len * sizeof(double), hipMemcpyHostToDevice));
   HIPCHK(c, hipMemsetAsync(d.res, 0, (size_t)k.nmod * rb, st));
-  g.list = d.list;
-  g.list_len = (int)list.size();
-  g.K = K;
-  g.kbeg = p.kbeg;
-  g.kend = p.kend;
-  g.tri = p.tri ? 1 : 0;
-  g.ntj = p.tri ? 0 : ntj;
-  g.res = d.res;
-  g.res_bytes = rb;
-  g.kdiv = p.kdiv;
-  g.ti0 = ti0;
-  OzCrt r{d.res, rb, g.tri, g.ntj, d.exa, b ? d.exb : d.exa, d.C, (long long)p.ldc, p.rows, p.cols, p.lower128 ? 1 : 0,
-          p.alpha, ti0};
-  r.acc = p.acc ? 1 : 0;
-  CHK(oz_gemm_crt(c, k, g, r, nti, 0.0, 0.0));
+  const OzOut out{d.exa, b ? d.exb : d.exa, d.C, (long long)p.ldc, p.rows, p.cols, p.lower128 ? 1 : 0, p.alpha, p.acc ? 1 : 0};
+  CHK(oz_gemm_crt(c, k, OzProduct{s, oa, ob, d.list, (int)list.size(), d.res, rb, out}, 0.0, 0.0));
   HIPCHK(c, hipStreamSynchronize(st));
   HIPCHK(c, hipMemcpy(C, d.C, (size_t)p.c_len * sizeof(double), hipMemcpyDeviceToHost));
   if (exa_out) HIPCHK(c, hipMemcpy(exa_out, d.exa, (size_t)Pa * sizeof(int), hipMemcpyDeviceToHost));

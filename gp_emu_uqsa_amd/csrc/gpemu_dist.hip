@@ -890,17 +890,14 @@ int oz_prepare(gpe_dist* h) {
   h->oz_c = oz_consts(N, Kp);
   std::vector<unsigned> all;
   h->oz_lists.clear();
-  long long maxt = 0;
+  h->oz_res_bytes = 0;
   for (const SlabLaunch& sl : h->slabs[0]) {   // (the same slab bounds on every rank)
-    const int ti0 = sl.a0 / 2, ti1 = (sl.a1 + 1) / 2;
-    const std::vector<unsigned> l = oz_list(ti1 - ti0, ti1, true, [&](int ti, int) {
-      return (double)std::max(0, Kp - 128 * ((2 * ti) / P));
-    }, ti0);
+    const OzShape s = oz_slab_shape(sl.a0, sl.a1, Kp, P);
+    const std::vector<unsigned> l = s.list();
     h->oz_lists.push_back({(long long)all.size(), (int)l.size()});
     all.insert(all.end(), l.begin(), l.end());
-    maxt = std::max(maxt, (long long)ti1 * (ti1 + 1) / 2 - (long long)ti0 * (ti0 + 1) / 2);
+    h->oz_res_bytes = std::max(h->oz_res_bytes, s.res_bytes());
   }
-  h->oz_res_bytes = maxt * OZ_T * OZ_T;
   // P = 1: the TRTRI levels whose blocks have at least oz_tri_min rows, each in one chunk,
   // as the single-GPU path's int8 pairs (oz_tri_pair_launches: T in the slab, in place of
   // the M^T blocks); the partial's buffers are the larger
@@ -932,40 +929,21 @@ int oz_prepare(gpe_dist* h) {
 
 // rank R's column exponents and planes of X_r^T (rows past n_pad and k past its rows: zero)
 int oz_split_rank(gpe_dist* h, const Rank& R) {
-  const int np2 = h->oz_np2, Kp = h->oz_kp, Kv = R.nlx * TILE;
-  const OzConst& k = h->oz_c;
-  hipLaunchKernelGGL(k_oz_rowexp<false>, dim3(np2 / 4), dim3(256), 0, h->stream, R.X, R.ld, (int)h->n_pad, np2, Kv,
-                     0, k.beta, h->ozx);
-  hipLaunchKernelGGL(k_oz_split_rect<false>, dim3(np2, (Kp + 2047) / 2048), dim3(256), 0, h->stream, R.X, R.ld,
-                     (int)h->n_pad, Kv, 0, h->ozx, h->ozp, (long long)np2 * Kp, (long long)Kp, Kp, k);
+  oz_operand(h->stream, h->oz_c, OzSrc{R.X, R.ld, (int)h->n_pad, R.nlx * TILE, 0, false}, h->oz_np2, h->oz_kp, h->ozx,
+             h->ozp);
   DCHK_HIP(h, hipGetLastError());
   return GPE_OK;
 }
 
 // slab si of rank R's partial: tile rows [a0, a1) (a0 even), their lower tiles into R.slab
+// (the residues of every slab oz_res_bytes, the largest slab's, apart)
 int oz_slab(gpe_dist* h, const Rank& R, const SlabLaunch& sl, size_t si) {
-  const int np2 = h->oz_np2, Kp = h->oz_kp;
-  const int ti0 = sl.a0 / 2, ti1 = (sl.a1 + 1) / 2;
-  const OzConst& k = h->oz_c;
-  OzGemm g;
-  g.a = g.b = OzOpnd{h->ozp, (long long)np2 * Kp, (long long)Kp, 0};
-  g.list = h->ozl + h->oz_lists[si].first;
-  g.list_len = h->oz_lists[si].second;
-  g.K = Kp;
-  g.kbeg = 3;
-  g.kdiv = h->P;
-  g.kend = 0;
-  g.tri = 1;
-  g.ntj = 0;
-  g.res = h->ozr;
-  g.res_bytes = h->oz_res_bytes;
-  g.ti0 = ti0;
-  oz_gemm_launch(h->stream, g, k);
+  const OzOpnd x{h->ozp, (long long)h->oz_np2 * h->oz_kp, (long long)h->oz_kp, 0};
   const int rows = sl.a1 * TILE;
-  OzCrt r{h->ozr, h->oz_res_bytes, 1, 0, h->ozx, h->ozx, R.slab, (long long)h->slab_rows * TILE, rows, rows, 1, 1.0, ti0};
-  const long long nt = (long long)ti1 * (ti1 + 1) / 2 - (long long)ti0 * (ti0 + 1) / 2;
-  hipLaunchKernelGGL(k_oz_crt, dim3((unsigned)(nt * 16)), dim3(256), 0, h->stream, r, k);
-  DCHK_HIP(h, hipGetLastError());
+  const OzProduct p{oz_slab_shape(sl.a0, sl.a1, h->oz_kp, h->P), x, x, h->ozl + h->oz_lists[si].first,
+                    h->oz_lists[si].second, h->ozr, h->oz_res_bytes,
+                    OzOut{h->ozx, h->ozx, R.slab, (long long)h->slab_rows * TILE, rows, rows, 1, 1.0}};
+  DCHK_HIP(h, oz_product_launch(h->stream, h->oz_c, p));
   return GPE_OK;
 }
 
@@ -1234,16 +1212,14 @@ int trtri_all(gpe_dist* h) {
     if (!tc.oz.empty()) {   // P = 1, int8 pairs (oz_prepare)
       Rank& R = h->ranks[0];
       auto tile = [&](double* M, int i, int j) { return M + (long long)i * TILE + (long long)j * TILE * R.ld; };
-      const OzConst& k = h->oz_c;
+      hipError_t err = hipSuccess;
       for (const OzTriPair& q : tc.oz)
-        oz_tri_pair_launches(h->stream, k, q, h->ozl, tile(R.A, q.h, q.t0), tile(R.X, q.t0, q.t0), tile(R.X, q.h, q.h),
-                             tile(R.X, q.h, q.t0), R.ld, R.slab, h->ozp, h->ozr, h->ozx, false,
-                             [&](const OzGemm& g, const OzCrt& r, int nti, double, double) {
-                               oz_gemm_launch(h->stream, g, k);
-                               hipLaunchKernelGGL(k_oz_crt, dim3((unsigned)(nti * g.ntj * 16)), dim3(256), 0, h->stream,
-                                                  r, k);
+        oz_tri_pair_launches(h->stream, h->oz_c, q, h->ozl, tile(R.A, q.h, q.t0), tile(R.X, q.t0, q.t0),
+                             tile(R.X, q.h, q.h), tile(R.X, q.h, q.t0), R.ld, R.slab, h->ozp, h->ozr, h->ozx, false,
+                             [&](const OzProduct& p, double, double) {
+                               if (err == hipSuccess) err = oz_product_launch(h->stream, h->oz_c, p);
                              });
-      DCHK_HIP(h, hipGetLastError());
+      DCHK_HIP(h, err);
       continue;
     }
     if (h->P > 1) {

@@ -195,6 +195,12 @@ struct OzGemm {
 __device__ __forceinline__ long long oz_res_tile(int tri, int ntj, int ti, int tj) {
   return tri ? (long long)ti * (ti + 1) / 2 + tj : (long long)ti * ntj + tj;
 }
+// the k range [kb, ke) of tile (ti, tj) (above): the one statement of the rule, for k_oz_gemm
+// and for the host's tile weights and operation counts (OzShape::klen)
+__host__ __device__ __forceinline__ void oz_k_range(int kbeg, int kend, int kdiv, int K, int ti, int tj, int& kb, int& ke) {
+  kb = kbeg == 1 ? OZ_T * ti : (kbeg == 2 ? OZ_T * tj : (kbeg == 3 ? 128 * ((2 * ti) / kdiv) : 0));
+  ke = kend == 1 ? (K < OZ_T * (ti + 1) ? K : OZ_T * (ti + 1)) : K;
+}
 
 // wait until at most `stages` whole stages (8 direct loads each) of this wave are in flight
 __device__ __forceinline__ void oz_vmwait_stages(int stages) {
@@ -278,8 +284,8 @@ static __global__ void __launch_bounds__(256, 1) k_oz_gemm(OzGemm g, OzConst cst
   const unsigned ent = g.list[(int)blockIdx.x - l * g.list_len];
   if (ent == 0xffffffffu) return;
   const int ti = (int)(ent >> 16), tj = (int)(ent & 0xffffu);
-  const int kb = g.kbeg == 1 ? OZ_T * ti : (g.kbeg == 2 ? OZ_T * tj : (g.kbeg == 3 ? 128 * ((2 * ti) / g.kdiv) : 0));
-  const int ke = g.kend == 1 ? min(g.K, OZ_T * (ti + 1)) : g.K;
+  int kb, ke;
+  oz_k_range(g.kbeg, g.kend, g.kdiv, g.K, ti, tj, kb, ke);
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = (wave >> 1) * 128, wn = (wave & 1) * 128;
@@ -414,12 +420,6 @@ static __global__ void __launch_bounds__(256, 1) k_oz_gemm(OzGemm g, OzConst cst
                 ((long long)(wave * 16) * 64 + lane) * 16;
   if (m == 256) oz_store_residues<true>(acc, m, 0, 0.0f, out);
   else oz_store_residues<false>(acc, m, cst.c16[l], cst.inv[l], out);
-}
-
-// The one launch of k_oz_gemm: a workgroup per modulus and list position, the whole ring as
-// dynamic LDS (one workgroup per CU)
-static inline void oz_gemm_launch(hipStream_t st, const OzGemm& g, const OzConst& k) {
-  hipLaunchKernelGGL(k_oz_gemm, dim3((unsigned)(k.nmod * g.list_len)), dim3(256), OZ_LDS, st, g, k);
 }
 
 // fp64 entries from the residues: C(r, c) = alpha v M 2^-(exr[r] + exc[c]), v = C'/M the
@@ -729,6 +729,127 @@ std::vector<unsigned> oz_list(int nti, int ntj, bool lower, W work, int ti0 = 0)
   return list;
 }
 
+// ---- the launch layer: every int8 product of gpemu.hip and gpemu_dist.hip (and the test hook
+// gpe_test_oz_product) converts its operands, builds its tile list and launches through here.
+
+// A rectangular operand's source (op(r, k), R, Kv, mask as above k_oz_rowexp; trans = TRANS)
+struct OzSrc {
+  const double* src;
+  long long ld;
+  int R, Kv, mask;
+  bool trans;
+};
+// its row exponents into ex[0, P) (P = R padded to 256) ...
+inline void oz_operand_exp(hipStream_t st, const OzConst& k, const OzSrc& o, int P, int* ex) {
+  if (o.trans) {
+    (void)hipMemsetAsync(ex, 0, (size_t)P * sizeof(int), st);
+    hipLaunchKernelGGL(k_oz_rowexp<true>, dim3(P / 64, (o.Kv + 255) / 256), dim3(256), 0, st, o.src, o.ld, o.R, P, o.Kv,
+                       o.mask, k.beta, ex);
+    hipLaunchKernelGGL(k_oz_il_to_ex, dim3((P + 255) / 256), dim3(256), 0, st, ex, P, k.beta);
+  } else {
+    hipLaunchKernelGGL(k_oz_rowexp<false>, dim3(P / 4), dim3(256), 0, st, o.src, o.ld, o.R, P, o.Kv, o.mask, k.beta, ex);
+  }
+}
+// ... and its planes: P rows of Kp bytes (a multiple of 64) per modulus, P Kp bytes apart
+inline void oz_operand_split(hipStream_t st, const OzConst& k, const OzSrc& o, int P, int Kp, const int* ex, int8_t* planes) {
+  if (o.trans)
+    hipLaunchKernelGGL(k_oz_split_rect<true>, dim3(P / 64, Kp / 64), dim3(256), 0, st, o.src, o.ld, o.R, o.Kv, o.mask, ex,
+                       planes, (long long)P * Kp, (long long)Kp, Kp, k);
+  else
+    hipLaunchKernelGGL(k_oz_split_rect<false>, dim3(P, (Kp + 2047) / 2048), dim3(256), 0, st, o.src, o.ld, o.R, o.Kv,
+                       o.mask, ex, planes, (long long)P * Kp, (long long)Kp, Kp, k);
+}
+inline void oz_operand(hipStream_t st, const OzConst& k, const OzSrc& o, int P, int Kp, int* ex, int8_t* planes) {
+  oz_operand_exp(st, k, o, P, ex);
+  oz_operand_split(st, k, o, P, Kp, ex, planes);
+}
+// the packed operand (the LAUUM's): column exponents and the lower column panels of X (np x np
+// of the padded order np2, ld ldx), oz_plane_bytes(np2) per modulus
+inline void oz_operand_packed(hipStream_t st, const OzConst& k, const double* X, long long ldx, int np, int np2, int* ex,
+                              int8_t* planes) {
+  hipLaunchKernelGGL(k_oz_colexp, dim3((np2 + 3) / 4), dim3(256), 0, st, X, ldx, np, np2, k.beta, ex);
+  hipLaunchKernelGGL(k_oz_split, dim3(np2, (np2 + 256 * OZ_SPLIT_ROWS - 1) / (256 * OZ_SPLIT_ROWS)), dim3(256), 0, st, X,
+                     ldx, np, np2, ex, planes, oz_plane_bytes(np2), k);
+}
+
+// A product's shape, stated once: tile rows [ti0, ti0 + nti) against ntj tile columns, or (tri)
+// against the lower triangle's tj <= ti; K, kbeg, kend, kdiv as OzGemm's
+struct OzShape {
+  int nti, ntj, ti0, tri, K, kbeg, kend, kdiv;
+  static OzShape lower(int nti, int ti0, int K, int kbeg, int kdiv = 1) { return {nti, 0, ti0, 1, K, kbeg, 0, kdiv}; }
+  static OzShape rect(int nti, int ntj, int K, int kbeg, int kend) { return {nti, ntj, 0, 0, K, kbeg, kend, 1}; }
+  // length of tile (ti, tj)'s k range: its weight in the list, its share of the operations
+  int klen(int ti, int tj) const {
+    int kb, ke;
+    oz_k_range(kbeg, kend, kdiv, K, ti, tj, kb, ke);
+    return std::max(0, ke - kb);
+  }
+  std::vector<unsigned> list() const {
+    return oz_list(nti, tri ? ti0 + nti : ntj, tri != 0, [&](int ti, int tj) { return (double)klen(ti, tj); }, ti0);
+  }
+  // residue tiles (tri: the lower tiles of the rows up to ti0 + nti less those above ti0)
+  long long tiles() const {
+    const long long t1 = ti0 + nti;
+    return tri ? t1 * (t1 + 1) / 2 - (long long)ti0 * (ti0 + 1) / 2 : (long long)nti * ntj;
+  }
+  long long res_bytes() const { return tiles() * OZ_T * OZ_T; }   // per modulus
+  // int8 operations with N moduli
+  double ops(int N) const {
+    double s = 0.0;
+    for (int ti = ti0; ti < ti0 + nti; ++ti)
+      for (int tj = 0; tj < (tri ? ti + 1 : ntj); ++tj) s += klen(ti, tj);
+    return 2.0 * OZ_T * OZ_T * s * N;
+  }
+};
+
+// the LAUUM's X^T X at the padded order np2: the lower tiles, tile row ti's sums from its
+// diagonal block on
+inline OzShape oz_lauum_shape(int np2) { return OzShape::lower(np2 / OZ_T, 0, np2, 1); }
+// the row-block A^-1 partial's slab of 128-tile rows [a0, a1) (a0 even) over Kp local rows of
+// one of P ranks: 256-tile row ti's sums from local row 128 floor(2 ti / P) on
+inline OzShape oz_slab_shape(int a0, int a1, int Kp, int P) {
+  return OzShape::lower((a1 + 1) / 2 - a0 / 2, a0 / 2, Kp, 3, P);
+}
+
+// where a product's reconstruction goes (as OzCrt)
+struct OzOut {
+  const int* exr;
+  const int* exc;
+  double* C;
+  long long ldc;
+  int rows, cols, lower128;
+  double alpha;
+  int acc = 0;
+};
+// One product: its shape, the operands' planes, the shape's list on the device, the residue
+// buffer (res_bytes per modulus, at least s.res_bytes()) and the output
+struct OzProduct {
+  OzShape s;
+  OzOpnd a, b;
+  const unsigned* list;
+  int list_len;
+  int8_t* res;
+  long long res_bytes;
+  OzOut out;
+};
+// The one launch of k_oz_gemm (a workgroup per modulus and list position, the whole ring as
+// dynamic LDS: one workgroup per CU) and of k_oz_crt (16 workgroups per residue tile) behind
+// it.  e0, e1: events recorded just before and after k_oz_gemm (gpe_ozaki_stats times it alone).
+inline hipError_t oz_product_launch(hipStream_t st, const OzConst& k, const OzProduct& p, hipEvent_t e0 = nullptr,
+                                    hipEvent_t e1 = nullptr) {
+  const OzShape& s = p.s;
+  const int ntj = s.tri ? 0 : s.ntj;
+  const OzGemm g{p.a, p.b, p.list, p.list_len, s.K, s.kbeg, s.kend, s.tri, ntj, p.res, p.res_bytes, s.kdiv, s.ti0};
+  const OzOut& o = p.out;
+  const OzCrt r{p.res, p.res_bytes, s.tri, ntj, o.exr, o.exc, o.C, o.ldc, o.rows, o.cols, o.lower128, o.alpha, s.ti0, o.acc};
+  hipError_t e;
+  if (e0 && (e = hipEventRecord(e0, st)) != hipSuccess) return e;
+  hipLaunchKernelGGL(k_oz_gemm, dim3((unsigned)(k.nmod * g.list_len)), dim3(256), OZ_LDS, st, g, k);
+  if (e1 && (e = hipEventRecord(e1, st)) != hipSuccess) return e;
+  hipLaunchKernelGGL(k_oz_crt, dim3((unsigned)(s.tiles() * 16)), dim3(256), 0, st, r, k);
+  return hipGetLastError();
+}
+
 // The block pairs (t0, h, t1) of the TRTRI level of span s tiles (s = 2, 4, ... while
 // s / 2 < NB; tile units of 128): X(t0:h, t0:h) and X(h:t1, h:t1) are inverted, the level fills
 // X(h:t1, t0:h).  The last pair of a level is ragged (t1 = NB) and a block without a lower
@@ -749,15 +870,22 @@ inline std::vector<std::array<int, 3>> trtri_level_pairs(int NB, int s) {
 //   T   = L21 X11      (rows of L21 against columns of X11, k >= the column: kbeg = 256 tj)
 //   X21 = -X22 T       (rows of X22, k <= the row: kend = 256 (ti + 1), against columns of T)
 // T goes to a scratch block (column-major, ld Pb, so its columns are the second product's
-// rows).  Plan (host): the rows of each block (Ra, Rb), padded to 256 (Pa, Pb), the two tile
-// lists' offsets in a list array, and the products' int8 operations (every modulus).
+// rows).  Plan (host): the rows of each block (Ra, Rb), padded to 256 (Pa, Pb), the two
+// products' shapes, their tile lists' offsets in a list array, and their int8 operations
+// (every modulus).
 struct OzTriPair {
   int t0, h, t1, Ra, Rb, Pa, Pb;
   long long la_off, lb_off;
   int la_len, lb_len;
   double ops_a, ops_b;
+  OzShape shape_a() const { return OzShape::rect(Pb / OZ_T, Pa / OZ_T, Pa, 2, 0); }
+  OzShape shape_b() const { return OzShape::rect(Pb / OZ_T, Pa / OZ_T, Pb, 0, 1); }
+  // the split Cholesky's S = A22 - L21 L21^T on the pair (0, h, NB): the lower tiles, every sum K = Pa
+  OzShape shape_schur() const { return OzShape::lower(Pb / OZ_T, 0, Pa, 0); }
   size_t planes_bytes(int N) const { return (size_t)N * Pa * (Pa + Pb); }
-  size_t resid_bytes(int N) const { return (size_t)N * Pa * Pb; }
+  size_t resid_bytes(int N) const { return (size_t)N * shape_a().res_bytes(); }   // (shape_b's too)
+  // the first product's L21 side
+  OzSrc l21(const double* L21, long long ld) const { return {L21, ld, Rb, Ra, 0, true}; }
 };
 inline OzTriPair oz_tri_pair_plan(int t0, int h, int t1, int N, std::vector<unsigned>& lists) {
   OzTriPair q;
@@ -766,12 +894,9 @@ inline OzTriPair oz_tri_pair_plan(int t0, int h, int t1, int N, std::vector<unsi
   q.Rb = (t1 - h) * TILE;
   q.Pa = (q.Ra + OZ_T - 1) / OZ_T * OZ_T;
   q.Pb = (q.Rb + OZ_T - 1) / OZ_T * OZ_T;
-  const int nti = q.Pb / OZ_T, ntj = q.Pa / OZ_T;
-  const std::vector<unsigned> la = oz_list(nti, ntj, false, [&](int, int tj) { return (double)(q.Pa - OZ_T * tj); });
-  const std::vector<unsigned> lb = oz_list(nti, ntj, false, [&](int ti, int) { return (double)(OZ_T * (ti + 1)); });
-  q.ops_a = q.ops_b = 0.0;
-  for (int tj = 0; tj < ntj; ++tj) q.ops_a += 2.0 * OZ_T * OZ_T * nti * (double)(q.Pa - OZ_T * tj) * N;
-  for (int ti = 0; ti < nti; ++ti) q.ops_b += 2.0 * OZ_T * OZ_T * ntj * (double)(OZ_T * (ti + 1)) * N;
+  const std::vector<unsigned> la = q.shape_a().list(), lb = q.shape_b().list();
+  q.ops_a = q.shape_a().ops(N);
+  q.ops_b = q.shape_b().ops(N);
   q.la_off = (long long)lists.size();
   q.la_len = (int)la.size();
   lists.insert(lists.end(), la.begin(), la.end());
@@ -781,82 +906,39 @@ inline OzTriPair oz_tri_pair_plan(int t0, int h, int t1, int N, std::vector<unsi
   return q;
 }
 
-// the first product's L21 side: row exponents (into ex[0, Pb)) and planes of L21's rows
-inline void oz_l21_launch(hipStream_t st, const OzConst& k, const OzTriPair& q, const double* L21, long long ld,
-                          int8_t* planes, int* ex) {
-  const long long pA = (long long)q.Pb * q.Pa;
-  (void)hipMemsetAsync(ex, 0, q.Pb * sizeof(int), st);
-  hipLaunchKernelGGL(k_oz_rowexp<true>, dim3(q.Pb / 64, (q.Ra + 255) / 256), dim3(256), 0, st, L21, ld, q.Rb, q.Pb,
-                     q.Ra, 0, k.beta, ex);
-  hipLaunchKernelGGL(k_oz_il_to_ex, dim3((q.Pb + 255) / 256), dim3(256), 0, st, ex, q.Pb, k.beta);
-  hipLaunchKernelGGL(k_oz_split_rect<true>, dim3(q.Pb / 64, q.Pa / 64), dim3(256), 0, st, L21, ld, q.Rb, q.Ra, 0,
-                     ex, planes, pA, (long long)q.Pa, q.Pa, k);
-}
-
 // both products of the pair on stream st (X blocks and L21 with leading dimension ld; T:
 // Pb x Pa doubles; planes: q.planes_bytes(N); res: q.resid_bytes(N); ex: Pa + Pb ints;
-// lists: the list array of oz_tri_pair_plan, on the device).  l21_done: oz_l21_launch already
-// ran (ordered before st's work by the caller).  gc(g, r, nti, ops, flops64) launches one
-// k_oz_gemm + k_oz_crt pair.
+// lists: the list array of oz_tri_pair_plan, on the device).  l21_done: L21's operand
+// (q.l21: planes at planes, exponents at ex) is already there (ordered before st's work by the
+// caller).  gc(p, ops, flops64) launches one product (oz_product_launch).
 template <class GC>
 void oz_tri_pair_launches(hipStream_t st, const OzConst& k, const OzTriPair& q, const unsigned* lists, const double* L21,
                           const double* X11, const double* X22, double* X21, long long ld, double* T, int8_t* planes,
                           int8_t* res, int* ex, bool l21_done, GC gc) {
   int* exA = ex;
   int* exB = ex + q.Pb;
-  const int nti = q.Pb / OZ_T, ntj = q.Pa / OZ_T;
-  const long long rb = (long long)nti * ntj * OZ_T * OZ_T;
+  int8_t* PA = planes;
+  const long long rb = q.shape_a().res_bytes();
   {   // T = L21 X11
     const long long pA = (long long)q.Pb * q.Pa, pB = (long long)q.Pa * q.Pa;
-    int8_t* PA = planes;
     int8_t* PB = planes + (size_t)k.nmod * pA;
-    if (!l21_done) oz_l21_launch(st, k, q, L21, ld, PA, exA);
-    hipLaunchKernelGGL(k_oz_rowexp<false>, dim3(q.Pa / 4), dim3(256), 0, st, X11, ld, q.Ra, q.Pa, q.Ra, 1, k.beta, exB);
-    hipLaunchKernelGGL(k_oz_split_rect<false>, dim3(q.Pa, (q.Pa + 2047) / 2048), dim3(256), 0, st, X11, ld, q.Ra, q.Ra,
-                       1, exB, PB, pB, (long long)q.Pa, q.Pa, k);
-    OzGemm g;
-    g.a = OzOpnd{PA, pA, q.Pa, 0};
-    g.b = OzOpnd{PB, pB, q.Pa, 0};
-    g.list = lists + q.la_off;
-    g.list_len = q.la_len;
-    g.K = q.Pa;
-    g.kbeg = 2;
-    g.kend = 0;
-    g.tri = 0;
-    g.ntj = ntj;
-    g.res = res;
-    g.res_bytes = rb;
-    OzCrt r{res, rb, 0, ntj, exA, exB, T, (long long)q.Pb, q.Rb, q.Ra, 0, 1.0};
-    gc(g, r, nti, q.ops_a, (double)q.Ra * q.Ra * q.Rb);
+    if (!l21_done) oz_operand(st, k, q.l21(L21, ld), q.Pb, q.Pa, exA, PA);
+    oz_operand(st, k, OzSrc{X11, ld, q.Ra, q.Ra, 1, false}, q.Pa, q.Pa, exB, PB);
+    gc(OzProduct{q.shape_a(), OzOpnd{PA, pA, q.Pa, 0}, OzOpnd{PB, pB, q.Pa, 0}, lists + q.la_off, q.la_len, res, rb,
+                 OzOut{exA, exB, T, (long long)q.Pb, q.Rb, q.Ra, 0, 1.0}},
+       q.ops_a, (double)q.Ra * q.Ra * q.Rb);
   }
-  {   // X21 = -X22 T
+  {   // X21 = -X22 T (both operands' exponents, then both operands' planes)
     const long long pA = (long long)q.Pb * q.Pb, pB = (long long)q.Pa * q.Pb;
-    int8_t* PA = planes;
     int8_t* PB = planes + (size_t)k.nmod * pA;
-    (void)hipMemsetAsync(exA, 0, q.Pb * sizeof(int), st);
-    hipLaunchKernelGGL(k_oz_rowexp<true>, dim3(q.Pb / 64, (q.Rb + 255) / 256), dim3(256), 0, st, X22, ld, q.Rb, q.Pb,
-                       q.Rb, 2, k.beta, exA);
-    hipLaunchKernelGGL(k_oz_il_to_ex, dim3((q.Pb + 255) / 256), dim3(256), 0, st, exA, q.Pb, k.beta);
-    hipLaunchKernelGGL(k_oz_rowexp<false>, dim3(q.Pa / 4), dim3(256), 0, st, T, (long long)q.Pb, q.Ra, q.Pa, q.Rb, 0,
-                       k.beta, exB);
-    hipLaunchKernelGGL(k_oz_split_rect<true>, dim3(q.Pb / 64, q.Pb / 64), dim3(256), 0, st, X22, ld, q.Rb, q.Rb, 2,
-                       exA, PA, pA, (long long)q.Pb, q.Pb, k);
-    hipLaunchKernelGGL(k_oz_split_rect<false>, dim3(q.Pa, (q.Pb + 2047) / 2048), dim3(256), 0, st, T, (long long)q.Pb,
-                       q.Ra, q.Rb, 0, exB, PB, pB, (long long)q.Pb, q.Pb, k);
-    OzGemm g;
-    g.a = OzOpnd{PA, pA, q.Pb, 0};
-    g.b = OzOpnd{PB, pB, q.Pb, 0};
-    g.list = lists + q.lb_off;
-    g.list_len = q.lb_len;
-    g.K = q.Pb;
-    g.kbeg = 0;
-    g.kend = 1;
-    g.tri = 0;
-    g.ntj = ntj;
-    g.res = res;
-    g.res_bytes = rb;
-    OzCrt r{res, rb, 0, ntj, exA, exB, X21, ld, q.Rb, q.Ra, 0, -1.0};
-    gc(g, r, nti, q.ops_b, (double)q.Rb * q.Rb * q.Ra);
+    const OzSrc x22{X22, ld, q.Rb, q.Rb, 2, true}, t{T, (long long)q.Pb, q.Ra, q.Rb, 0, false};
+    oz_operand_exp(st, k, x22, q.Pb, exA);
+    oz_operand_exp(st, k, t, q.Pa, exB);
+    oz_operand_split(st, k, x22, q.Pb, q.Pb, exA, PA);
+    oz_operand_split(st, k, t, q.Pa, q.Pb, exB, PB);
+    gc(OzProduct{q.shape_b(), OzOpnd{PA, pA, q.Pb, 0}, OzOpnd{PB, pB, q.Pb, 0}, lists + q.lb_off, q.lb_len, res, rb,
+                 OzOut{exA, exB, X21, ld, q.Rb, q.Ra, 0, -1.0}},
+       q.ops_b, (double)q.Rb * q.Rb * q.Ra);
   }
 }
 

@@ -327,8 +327,9 @@ int gpe_test_gemm(gpe_ctx* ctx, int32_t trans_a, int32_t trans_b, int64_t M, int
  * reference has no counterpart.  C = alpha op(A) op(B)^T (+ C with acc) through the
  * production sequence -- exponents, split into int8 planes, k_oz_gemm, k_oz_crt -- on device
  * buffers of its own, freed on exit; the context's resident factor and cached plans are not
- * touched.  The tile list comes from oz_list, the constants from oz_consts(nmod, K), the
- * launches from the routine every single-GPU product goes through.
+ * touched.  The constants come from oz_consts(nmod, K); the operand conversion, the tile list
+ * with its k ranges and the two product launches are calls of the launch layer every
+ * production product goes through (oz_operand / oz_operand_packed, OzShape, oz_product_launch).
  *
  * An operand is a window of a host fp64 array `src` of `len` doubles, copied to the device
  * as it is: op(r, k) = src[offset + k + r ld] (trans 0) or src[offset + r + k ld] (trans 1)

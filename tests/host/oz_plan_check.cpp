@@ -1,5 +1,5 @@
 // oz_plan_check.cpp -- host-only check of the int8 products' constants and plans
-// (gpemu_ozaki.hpp: oz_consts, oz_list, trtri_level_pairs, oz_tri_pair_plan).  No HIP runtime
+// (gpemu_ozaki.hpp: oz_consts, oz_list, OzShape, trtri_level_pairs, oz_tri_pair_plan).  No HIP runtime
 // call: it runs without a GPU.  Built and run by tests/test_ozaki_host.py:
 //   hipcc --offload-arch=gfx950 -std=c++17 -I gp_emu_uqsa_amd/csrc tests/host/oz_plan_check.cpp
 // Prints one line per failed check and "beta12_4096=<beta>"; exit status 0 and a last line
@@ -175,10 +175,96 @@ static void check_pairs() {
   }
 }
 
+// One product description against the closed forms its call site used to write out by hand,
+// restated here (never taken from OzShape): over every tile the k-range length, the list entry
+// for entry against oz_list with the closed form (nti, ntj, lower, ti0 as the site passed
+// them), the operation count against the site's loop, the residue-tile count.  All integers
+// far below 2^53: equality is exact.
+template <class W>
+static void check_shape(const OzShape& s, int nti, int ntj, bool lower, int ti0, W klen, double ops, long long tiles,
+                        const char* what, int id) {
+  for (int ti = ti0; ti < ti0 + nti; ++ti)
+    for (int tj = 0; tj < (lower ? ti + 1 : ntj); ++tj)
+      CHECK(s.klen(ti, tj) == klen(ti, tj), "%s %d: tile (%d, %d) k range %d, closed form %d", what, id, ti, tj,
+            s.klen(ti, tj), klen(ti, tj));
+  const std::vector<unsigned> got = s.list();
+  const std::vector<unsigned> want = oz_list(nti, ntj, lower, [&](int ti, int tj) { return (double)klen(ti, tj); }, ti0);
+  CHECK(got == want, "%s %d: list of %zu entries differs from oz_list with the closed form (%zu)", what, id, got.size(),
+        want.size());
+  check_list(got, 0, got.size(), nti, ntj, lower, ti0, what);
+  CHECK(s.ops(OZ_MAXMOD) == ops, "%s %d: ops %.17g, the site's loop %.17g", what, id, s.ops(OZ_MAXMOD), ops);
+  CHECK(s.tiles() == tiles, "%s %d: %lld residue tiles, %lld expected", what, id, s.tiles(), tiles);
+  CHECK(s.res_bytes() == tiles * OZ_T * OZ_T, "%s %d: residue bytes", what, id);
+}
+
+// a TRTRI pair's two products, and its lists in the plan's array
+static void check_pair_shapes(int t0, int h, int t1) {
+  const int N = OZ_MAXMOD;
+  std::vector<unsigned> lists(3, 0u);
+  const OzTriPair q = oz_tri_pair_plan(t0, h, t1, N, lists);
+  const int nti = q.Pb / OZ_T, ntj = q.Pa / OZ_T, id = 10000 * t0 + 100 * h + t1;
+  double ops_a = 0.0, ops_b = 0.0;
+  for (int tj = 0; tj < ntj; ++tj) ops_a += 2.0 * OZ_T * OZ_T * nti * (double)(q.Pa - OZ_T * tj) * N;
+  for (int ti = 0; ti < nti; ++ti) ops_b += 2.0 * OZ_T * OZ_T * ntj * (double)(OZ_T * (ti + 1)) * N;
+  const auto ka = [&](int, int tj) { return q.Pa - OZ_T * tj; };
+  const auto kb = [&](int ti, int) { return OZ_T * (ti + 1); };
+  check_shape(q.shape_a(), nti, ntj, false, 0, ka, ops_a, (long long)nti * ntj, "pair T = L21 X11", id);
+  check_shape(q.shape_b(), nti, ntj, false, 0, kb, ops_b, (long long)nti * ntj, "pair X21 = -X22 T", id);
+  const std::vector<unsigned> la = oz_list(nti, ntj, false, [&](int ti, int tj) { return (double)ka(ti, tj); });
+  const std::vector<unsigned> lb = oz_list(nti, ntj, false, [&](int ti, int tj) { return (double)kb(ti, tj); });
+  CHECK(std::vector<unsigned>(lists.begin() + q.la_off, lists.begin() + q.la_off + q.la_len) == la, "pair %d: list a", id);
+  CHECK(std::vector<unsigned>(lists.begin() + q.lb_off, lists.begin() + q.lb_off + q.lb_len) == lb, "pair %d: list b", id);
+  CHECK(q.ops_a == ops_a && q.ops_b == ops_b, "pair %d: the plan's ops %.17g, %.17g", id, q.ops_a, q.ops_b);
+  CHECK(q.resid_bytes(N) == (size_t)N * nti * ntj * OZ_T * OZ_T, "pair %d: residues", id);
+  // the split Cholesky's Schur complement on the same pair: every sum Pa long
+  const int nts = q.Pb / OZ_T;
+  check_shape(q.shape_schur(), nts, nts, true, 0, [&](int, int) { return q.Pa; },
+              2.0 * OZ_T * OZ_T * (double)q.Pa * N * (nts * (nts + 1) / 2), (long long)nts * (nts + 1) / 2, "Schur", id);
+}
+
+static void check_shapes() {
+  const int N = OZ_MAXMOD;
+  // n_pad 1152 and 1280 share np2 = 1280, 8320 and 8448 share 8448; 2944 is NB = 23
+  for (int n_pad : {1152, 1280, 2944, 8320, 8448}) {
+    const int NB = n_pad / TILE, np2 = (n_pad + OZ_T - 1) / OZ_T * OZ_T, NT2 = np2 / OZ_T;
+    {   // the LAUUM
+      double ops = 0.0;
+      for (int ti = 0; ti < NT2; ++ti) ops += 2.0 * OZ_T * OZ_T * (ti + 1) * (double)(np2 - OZ_T * ti) * N;
+      check_shape(oz_lauum_shape(np2), NT2, NT2, true, 0, [&](int ti, int) { return np2 - OZ_T * ti; }, ops,
+                  (long long)NT2 * (NT2 + 1) / 2, "LAUUM", n_pad);
+    }
+    for (int s = 2; s / 2 < NB; s *= 2)
+      for (const auto& pr : trtri_level_pairs(NB, s)) check_pair_shapes(pr[0], pr[1], pr[2]);
+    // the posterior's V = L^-1 K* for chunks of one and of three tile columns: the rows of
+    // L^-1, k up to the row's tile end
+    for (int ntj : {1, 3}) {
+      double ops = 0.0;
+      for (int ti = 0; ti < NT2; ++ti) ops += 2.0 * OZ_T * OZ_T * ntj * (double)(OZ_T * (ti + 1)) * N;
+      check_shape(OzShape::rect(NT2, ntj, np2, 0, 1), NT2, ntj, false, 0, [&](int ti, int) { return OZ_T * (ti + 1); }, ops,
+                  (long long)NT2 * ntj, "posterior", n_pad);
+    }
+    // the row-block partial: slabs of 6 and of 10 tile rows (all but the first with ti0 > 0)
+    for (int P : {1, 2, 3, 8})
+      for (int rows : {6, 10}) {
+        const int Kp = ((NB - 1) / P + 1) * TILE;
+        for (int a0 = 0; a0 < NB; a0 += rows) {
+          const int a1 = std::min(NB, a0 + rows), ti0 = a0 / 2, ti1 = (a1 + 1) / 2;
+          const auto kl = [&](int ti, int) { return std::max(0, Kp - 128 * ((2 * ti) / P)); };
+          double ops = 0.0;
+          for (int ti = ti0; ti < ti1; ++ti) ops += 2.0 * OZ_T * OZ_T * (ti + 1) * (double)kl(ti, 0) * N;
+          check_shape(oz_slab_shape(a0, a1, Kp, P), ti1 - ti0, ti1, true, ti0, kl, ops,
+                      (long long)ti1 * (ti1 + 1) / 2 - (long long)ti0 * (ti0 + 1) / 2, "slab", 100 * n_pad + P);
+        }
+      }
+  }
+  check_pair_shapes(0, 3, 4);   // Ra = 384, Rb = 128: Rb < Ra and Pb = 256 > Rb
+}
+
 int main() {
   check_consts();
   check_lists();
   check_pairs();
+  check_shapes();
   if (g_fail) {
     std::printf("oz_plan_check: %d checks failed\n", g_fail);
     return 1;

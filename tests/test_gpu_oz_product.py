@@ -1,7 +1,11 @@
 """The int8 products (gpemu_ozaki.hpp) kernel by kernel against exact integers: one product at
 a time through gpe_test_oz_product -- the production sequence k_oz_colexp / k_oz_rowexp<T>
 (+ k_oz_il_to_ex), k_oz_split / k_oz_split_rect<T>, k_oz_gemm, k_oz_crt on buffers of the
-hook's own -- compared entry by entry with tests/oz_product_ref.py: the row exponents
+hook's own.  The hook does not repeat that sequence: it calls the launch layer every
+production product calls (gpemu_ozaki.hpp: oz_operand / oz_operand_packed for the operands,
+OzShape for the tile list and its k ranges, oz_product_launch for the two kernels), so the
+launch lines, grids and the k-range rule checked here are the ones production runs.  The
+results are compared entry by entry with tests/oz_product_ref.py: the row exponents
 exactly, the residues of two moduli (congruent to the exact C', within the epilogue's stated
 range), and C within the bound derived there from k_oz_crt's arithmetic.
 A failure names the operand form, the entry (so the tile, row and column) and, for the
@@ -299,7 +303,7 @@ def test_form_lauum_packed(ctx, integer):
 
 @pytest.mark.parametrize("integer", [0, 1])
 def test_form_trtri_pair(ctx, integer):
-    """oz_tri_pair_launches at Ra = 384, Rb = 128 (Pa = 512, Pb = 256 > Rb).
+    """The two products of oz_tri_pair_launches at Ra = 384, Rb = 128 (Pa = 512, Pb = 256 > Rb).
     T = L21 X11: A = L21's rows (transposed split), B = X11's columns with mask 1, kbeg 2.
     X21 = -X22 T: A = X22's rows with mask 2 (transposed), B = T's columns (ld Pb: the rows of
     the scratch block past Rb are never read), kend 1, alpha -1."""

@@ -153,6 +153,45 @@ def test_split_objective(split, fp64, n, case):
     _against(n, case, res, _grad(fp64, n, case), "split")
 
 
+def test_int8_ops_are_the_closed_forms(split):
+    """gpe_ozaki_stats' int8 operations of one gradient objective at n = 2900 (n_pad 2944,
+    NB = 23, np2 = 3072, 16 moduli) are the sum, over the products it launched, of
+    2 * 256^2 * (the tile's sum length) * 16 with the sum lengths written out per product: the
+    LAUUM's np2 - 256 ti over the lower tiles, each TRTRI pair's Pa - 256 tj and 256 (ti + 1)
+    over its Pb / 256 x Pa / 256 tiles, the Schur complement's Pa over the lower tiles of S.
+    Integers far below 2^53: the equality is exact."""
+    n, N, T = 2900, 16, 256
+    NB = (n + 127) // 128
+    np2 = -(-NB * 128 // T) * T
+    pad = lambda rows: -(-rows // T) * T
+    ksum = sum((ti + 1) * (np2 - T * ti) for ti in range(np2 // T))              # the LAUUM
+    s = 8
+    while s // 2 < NB:                                                             # blocks of >= 512 rows
+        for t0 in range(0, NB, s):
+            h, t1 = t0 + s // 2, min(t0 + s, NB)
+            if h >= NB:
+                continue
+            Pa, Pb = pad((h - t0) * 128), pad((t1 - h) * 128)
+            ksum += sum((Pb // T) * (Pa - T * tj) for tj in range(Pa // T))      # T = L21 X11
+            ksum += sum((Pa // T) * T * (ti + 1) for ti in range(Pb // T))       # X21 = -X22 T
+        s *= 2
+    Pa, nts = pad(16 * 128), pad((NB - 16) * 128) // T                             # S: the pair (0, 16, 23)
+    ksum += Pa * nts * (nts + 1) // 2
+    want = 2 * T * T * ksum * N
+    variant, kind, _, _ = CASES["gp4ml_fit"]
+    X, f, H, r, hp, nu_fixed, _ = _problem(n, "gp4ml_fit")
+    split.set_data(X, f, H, r)
+    split.set_profiling(True)
+    try:
+        split.objective(variant, kind, hp, nu_fixed=nu_fixed)
+        stats = split.ozaki_stats()
+    finally:
+        split.set_profiling(False)
+    print(f"int8 ops {stats['int8_ops']:.0f}, closed forms {want}, launches {stats['launches']}")
+    assert stats["launches"] == 1 + 2 * _pairs(NB, 4) + 1
+    assert stats["int8_ops"] == float(want), (stats["int8_ops"], want)
+
+
 @pytest.mark.parametrize("n,case", [(1024, "gp4ml_fit"), (1400, "gp4ml_fit"), (2900, "gp4ml_fit"), (2900, "mucm_fix")])
 def test_split_reuses_l21_planes(top, fp64, n, case):
     """GPEMU_OZAKI_TRI_MIN=2048: at n = 2900 only the top TRTRI pair (0, 16, 23) runs on the
