@@ -84,6 +84,11 @@ struct Plan {
   // the augmented row's tiles [h, NB) by the first h columns
   int split_h = 0, aug_mid = -1;
   std::vector<int> sfused, sfused_aug, sgrp, sgrp_aug;
+  // the TRTRI by sides of the split column (tri_ahead; sides: these are built): per level below
+  // the top one its launch pairs {T^T, X21} of the block pairs inside [0, h), then of those
+  // inside [h, NB) (-1: none)
+  bool sides = false;
+  std::vector<std::array<int, 4>> trtri_side;
   std::vector<GemmLaunch> launches;
   std::vector<GemmProb> probs;
   std::vector<unsigned> tiles;   // concatenated tile lists
@@ -121,8 +126,15 @@ struct Fact {
   // SPLIT_SLOTS partial tiles and one counter per tile of a launch
   double* part = nullptr;
   int* tcnt = nullptr;
-  // B's diagonal tiles hold the full X_tt = L_tt^-1 (k_xasm ran after the last sweep)
-  bool xdone = false;
+  // B's diagonal tiles hold the full X_tt = L_tt^-1 (k_xasm ran after the last sweep), by side
+  // of the last sweep's column xh: tiles [0, xh) and [xh, NB) (xh = 0: every tile on side 1)
+  bool xdone[2] = {false, false};
+  int xh = 0;
+  // B(0:x11, 0:x11) holds X11 = L11^-1 of the last sweep (tri_ahead; tile units, 0: not), and
+  // the int8 scratch block the top pair's T = L21 X11
+  int x11 = 0;
+  bool t_ahead = false;
+  void xclear(int h = 0) { xdone[0] = xdone[1] = t_ahead = false; x11 = 0; xh = h; }
   int desc_base = 0;         // first slot of its descriptors in the device array
   Plan plan;
 };
@@ -203,6 +215,11 @@ struct gpe_ctx {
   // gpe_factor's sweep (tests: the only way to read a split sweep's L out again); from
   // oz_chol_min rows of S (GPEMU_OZAKI_CHOL_MIN)
   int oz_chol = 1, oz_chol_min = OZ_CHOL_MIN;
+  // gradient evaluations with the split sweep: X11 = L11^-1 (the TRTRI's pairs inside [0, h))
+  // and the top pair's T = L21 X11 on the context stream beside the sweep's second phase
+  // (tri_ahead; GPEMU_TRTRI_AHEAD=0: after the sweep, as every other caller)
+  int tri_ahead_on = 1;
+  hipEvent_t ev_l11 = nullptr, ev_schur = nullptr;   // L11 is final / chol_schur is through (the sweep's stream)
   OzTriPair oz_chol_q{};          // the pair (0, h, NB): L21's planes and exponents as the TRTRI's
   long long oz_chol_loff = 0;     // the lower tile list of S in dozl
   int oz_chol_llen = 0;
@@ -1008,23 +1025,26 @@ int build_plan(gpe_ctx* c, Fact& F) {
   };
   CHK(sweep(0, NB, NB, {&pl.fused, &pl.fused_aug, &pl.grp, &pl.grp_aug}));
   // --- triangular inverse X = L^-1 in B (diagonal tiles already hold Dinv)
+  // the two problems of block pair pr = {t0, h, t1}, appended to a level's two launches
+  auto tri_pair = [&](const std::array<int, 3>& pr, std::vector<GemmProb>& pa, std::vector<GemmProb>& pb, double& fa,
+                      double& fb) {
+    const int t0 = pr[0], h = pr[1], t1 = pr[2];
+    const int a = h - t0, b = t1 - h;
+    // T^T (a x b tiles, stored in the upper block rows t0:h, cols h:t1 of B)
+    //   = X11^T L21^T ;  opA(m,k) = X11(k,m): K-contiguous, upper -> kbeg = ti*128
+    pa.push_back(mkprob(tile(B, t0, t0), ld, tile(A, h, t0), ld, tile(B, t0, h), ld, a, b,
+                        a * TILE, G_KBEG_TI, 1.0, 0.0));
+    fa += (double)a * T * a * T * b * T;   // triangular a x a times a x b
+    // X21 = -X22 T ;  opA = X22 lower -> kend = (ti+1)*128 ; opB(k,n) = T^T(n,k)
+    pb.push_back(mkprob(tile(B, h, h), ld, tile(B, t0, h), ld, tile(B, h, t0), ld, b, a,
+                        b * TILE, G_KEND_TI, -1.0, 0.0));
+    fb += (double)b * T * b * T * a * T;
+  };
   for (int s = 2; s / 2 < NB; s *= 2) {
     std::vector<GemmProb> pa, pb;
     const std::vector<std::array<int, 3>> prs = trtri_level_pairs(NB, s);
     double fa = 0.0, fb = 0.0;
-    for (const auto& pr : prs) {
-      const int t0 = pr[0], h = pr[1], t1 = pr[2];
-      const int a = h - t0, b = t1 - h;
-      // T^T (a x b tiles, stored in the upper block rows t0:h, cols h:t1 of B)
-      //   = X11^T L21^T ;  opA(m,k) = X11(k,m): K-contiguous, upper -> kbeg = ti*128
-      pa.push_back(mkprob(tile(B, t0, t0), ld, tile(A, h, t0), ld, tile(B, t0, h), ld, a, b,
-                          a * TILE, G_KBEG_TI, 1.0, 0.0));
-      fa += (double)a * T * a * T * b * T;   // triangular a x a times a x b
-      // X21 = -X22 T ;  opA = X22 lower -> kend = (ti+1)*128 ; opB(k,n) = T^T(n,k)
-      pb.push_back(mkprob(tile(B, h, h), ld, tile(B, t0, h), ld, tile(B, h, t0), ld, b, a,
-                          b * TILE, G_KEND_TI, -1.0, 0.0));
-      fb += (double)b * T * b * T * a * T;
-    }
+    for (const auto& pr : prs) tri_pair(pr, pa, pb, fa, fb);
     if (pa.empty()) continue;
     pl.tri_pairs.push_back(prs);
     split_k(pa, F.part, F.tcnt);
@@ -1070,6 +1090,42 @@ int build_plan(gpe_ctx* c, Fact& F) {
       pl.tiles.resize(nt);
       pl.split_h = 0;
       pl.aug_mid = -1;
+    }
+    // --- the TRTRI levels below the top one by side of h (a power of two: no pair of theirs
+    // straddles it), so X11 can be formed while the sweep's second phase runs (tri_ahead).  Each
+    // side's launch splits K as the level's one launch does: the same sums, bit for bit.  Left
+    // out the same way
+    if (pl.split_h) {
+      const size_t nl1 = pl.launches.size(), np1 = pl.probs.size(), nt1 = pl.tiles.size();
+      for (size_t lv = 0; lv < pl.tri_pairs.size(); ++lv) {
+        std::array<int, 4> side = {-1, -1, -1, -1};
+        std::vector<GemmProb> wa, wb;
+        double f0 = 0.0, f1 = 0.0;
+        for (const auto& pr : pl.tri_pairs[lv]) tri_pair(pr, wa, wb, f0, f1);
+        int ta = 0, tb = 0, ka = 0, kb = 0;
+        for (const GemmProb& q : wa) { ta += prob_tiles(q); ka = std::max(ka, q.K); }
+        for (const GemmProb& q : wb) { tb += prob_tiles(q); kb = std::max(kb, q.K); }
+        for (int sd = 0; sd < 2; ++sd) {
+          std::vector<GemmProb> pa, pb;
+          double fa = 0.0, fb = 0.0;
+          for (const auto& pr : trtri_side_pairs(pl.tri_pairs[lv], h, sd)) tri_pair(pr, pa, pb, fa, fb);
+          if (pa.empty()) continue;
+          split_k(pa, F.part, F.tcnt, ta, ka);
+          split_k(pb, F.part, F.tcnt, tb, kb);
+          side[2 * sd] = (int)pl.launches.size();
+          add_launch(pl, GEMM_AK, pa, fa);
+          side[2 * sd + 1] = (int)pl.launches.size();
+          add_launch(pl, GEMM_PLAIN, pb, fb);
+        }
+        pl.trtri_side.push_back(side);
+      }
+      pl.sides = true;
+      if ((int)pl.probs.size() > limit) {
+        pl.launches.resize(nl1);
+        pl.probs.resize(np1);
+        pl.tiles.resize(nt1);
+        pl.sides = false;
+      }
     }
   }
   if ((int)pl.probs.size() > limit) return fail(c, GPE_ERR_UNSUPPORTED, "GEMM schedule too large");
@@ -1188,10 +1244,13 @@ int kbuild(gpe_ctx* c, int kernel, double nu, double s2, double rscale) {
 // aux plan of gpe_noise_sample between gpe_factor and a later on-demand TRTRI / LAUUM.
 int oz_prepare(gpe_ctx* c, Fact& F);
 int chol_schur(gpe_ctx* c, Fact& F, hipStream_t st, bool with_aug);
+int trtri(gpe_ctx* c, Fact& F, bool ozaki = false, bool ahead = false);
 
 // split: the objective's sweep of the training matrix, in two phases around the int8 Schur
-// complement where the plan has them (Plan::split_h, chol_schur)
-int potrf(gpe_ctx* c, Fact& F, bool with_aug = false, bool split = false) {
+// complement where the plan has them (Plan::split_h, chol_schur); ahead: the caller inverts
+// next, so X11 and the top pair's T start on the context stream while the second phase runs
+// on the high-priority one (trtri's ahead)
+int potrf(gpe_ctx* c, Fact& F, bool with_aug = false, bool split = false, bool ahead = false) {
   CHK(build_plan(c, F));
   const int hs = split ? F.plan.split_h : 0;
   if (hs) CHK(oz_prepare(c, F));   // (may rebuild the plan: before pl is taken)
@@ -1200,8 +1259,9 @@ int potrf(gpe_ctx* c, Fact& F, bool with_aug = false, bool split = false) {
   const int NB = F.NB;
   // flags, the group schedule's counters and the launches' list tickets start at zero
   HIPCHK(c, hipMemsetAsync(F.flags, 0, FACT_FLAG_INTS * (size_t)NB * sizeof(int), c->stream));
-  F.xdone = false;   // the sweep leaves only X's diagonal 16 x 16 blocks (ensure_xdiag)
   const bool wa = with_aug && pl.aug;
+  const bool tri_ahead = hs && ahead && pl.sides && c->tri_ahead_on && c->chol_prio;
+  F.xclear(tri_ahead ? hs : 0);   // the sweep leaves only X's diagonal 16 x 16 blocks (ensure_xdiag)
   const bool grp = c->potrf_group &&
                    (c->potrf_mode == 1 || (c->potrf_mode == 0 && g_inflight[c->device & 63].load() <= 1));
   const std::vector<int>& fidx = hs ? (grp ? (wa ? pl.sgrp_aug : pl.sgrp) : (wa ? pl.sfused_aug : pl.sfused))
@@ -1212,7 +1272,14 @@ int potrf(gpe_ctx* c, Fact& F, bool with_aug = false, bool split = false) {
     HIPCHK(c, hipEventRecord(c->ev_fork, c->stream));
     HIPCHK(c, hipStreamWaitEvent(c->stream2, c->ev_fork, 0));
     for (int t = 0; t < NB; ++t) {
-      if (hs && t == hs) CHK(chol_schur(c, F, c->stream2, wa));
+      if (hs && t == hs) {
+        if (tri_ahead) HIPCHK(c, hipEventRecord(c->ev_l11, c->stream2));
+        CHK(chol_schur(c, F, c->stream2, wa));
+        if (tri_ahead) {
+          HIPCHK(c, hipEventRecord(c->ev_schur, c->stream2));
+          CHK(trtri(c, F, true, true));
+        }
+      }
       if (fidx[t] >= 0) CHK(launch_gemm_range(c, pl.launches[fidx[t]], c->stream2));
     }
     HIPCHK(c, hipEventRecord(c->ev_join, c->stream2));
@@ -1245,49 +1312,94 @@ int lauum(gpe_ctx* c, Fact& F) {
 }
 
 // the full diagonal-tile inverses X_tt in B (k_xasm) after a sweep: the TRTRI's leaves and
-// the forward substitution's D_t
-int ensure_xdiag(gpe_ctx* c, Fact& F) {
-  if (F.xdone) return GPE_OK;
-  hipLaunchKernelGGL(k_xasm, dim3(F.NB), dim3(256), DB_LDS_DOUBLES * sizeof(double), c->stream, F.A, F.B,
-                     (long long)F.n_pad);
-  HIPCHK(c, hipGetLastError());
-  F.xdone = true;
+// the forward substitution's D_t.  side: -1 every tile, else the tiles on that side of the
+// sweep's column F.xh (0: [0, xh), 1: [xh, NB))
+int ensure_xdiag(gpe_ctx* c, Fact& F, int side = -1) {
+  const bool want0 = side != 1 && !F.xdone[0], want1 = side != 0 && !F.xdone[1];
+  const int a = want0 ? 0 : F.xh, b = want1 ? F.NB : F.xh;   // (the tiles still due are one range)
+  if (b > a) {
+    const long long off = (long long)a * TILE * (F.n_pad + 1);
+    hipLaunchKernelGGL(k_xasm, dim3(b - a), dim3(256), DB_LDS_DOUBLES * sizeof(double), c->stream, F.A + off, F.B + off,
+                       (long long)F.n_pad);
+    HIPCHK(c, hipGetLastError());
+  }
+  F.xdone[0] = F.xdone[0] || want0;
+  F.xdone[1] = F.xdone[1] || want1;
   return GPE_OK;
 }
 
-int trtri_pair_ozaki(gpe_ctx* c, Fact& F, int t0, int h, int t1, int l21);
+int trtri_pair_ozaki(gpe_ctx* c, Fact& F, int t0, int h, int t1, int l21, int part = 0);
 int oz_l21_ahead(gpe_ctx* c, Fact& F, int t0, int h, int t1);
 bool oz_tri_level(const gpe_ctx* c, const std::vector<std::array<int, 3>>& prs);
 
 // X = L^-1 by levels; with ozaki (the objective's gradient) the levels whose blocks are at
-// least oz_tri_min rows run their two products on the int8 matrix cores (trtri_pair_ozaki)
-int trtri(gpe_ctx* c, Fact& F, bool ozaki = false) {
+// least oz_tri_min rows run their two products on the int8 matrix cores (trtri_pair_ozaki).
+// ahead (potrf, between the phases of the split sweep at column hs, which goes on on the
+// high-priority stream): on the context stream, from L11 final on (ev_l11), X11 -- the levels
+// below the top one over the pairs inside [0, hs) -- and, once chol_schur is through (ev_schur:
+// the int8 buffers are free, L21's planes there), the top pair's T = L21 X11, unless a pair
+// inside [hs, NB) runs on the int8 cores too and would write over T's scratch block.
+// After such a sweep (F.x11) the call that follows does what is left: the pairs inside
+// [hs, NB), then the top pair or its second product.  The operations and their operands are
+// those of the whole TRTRI after the sweep: the same X, bit for bit.
+int trtri(gpe_ctx* c, Fact& F, bool ozaki, bool ahead) {
   CHK(build_plan(c, F));
-  CHK(ensure_xdiag(c, F));
   const Plan& pl = F.plan;
+  const int hs = pl.split_h;
+  const bool rest = !ahead && F.x11 > 0 && pl.sides && F.x11 == hs && F.xh == hs;
+  if (ahead && !(pl.sides && F.xh == hs)) return fail(c, GPE_ERR_STATE, "internal error: TRTRI by side without its plan");
+  const int side = ahead ? 0 : (rest ? 1 : -1);   // of the levels below the top one (-1: whole levels)
+  const auto is_top = [&](size_t lv) { return side >= 0 && pl.tri_pairs[lv][0][0] < hs && pl.tri_pairs[lv][0][2] > hs; };
+  const auto pairs_of = [&](size_t lv, int sd) {
+    return (sd < 0 || is_top(lv)) ? pl.tri_pairs[lv] : trtri_side_pairs(pl.tri_pairs[lv], hs, sd);
+  };
+  const auto int8_level = [&](size_t lv) { return ozaki && oz_tri_level(c, pl.tri_pairs[lv]); };
+  // int8 pairs inside [0, hs) / [hs, NB), and the top level there
+  bool int8_side[2] = {false, false}, int8_top = false;
+  for (size_t lv = 0; lv < pl.tri_pairs.size() && side >= 0; ++lv) {
+    if (!int8_level(lv)) continue;
+    if (is_top(lv)) int8_top = true;
+    else for (int sd = 0; sd < 2; ++sd) int8_side[sd] = int8_side[sd] || !pairs_of(lv, sd).empty();
+  }
+  if (ahead) HIPCHK(c, hipStreamWaitEvent(c->stream, int8_side[0] ? c->ev_schur : c->ev_l11, 0));
+  CHK(ensure_xdiag(c, F, side));
   // the first int8 pair's L21 (final since the Cholesky) is converted on the second stream
-  // while the fp64 levels below it run
+  // while the fp64 levels below it run (not ahead: the sweep is on that stream)
   int first = -1;
-  for (size_t lv = 0; lv < pl.tri_pairs.size() && ozaki && first < 0; ++lv)
-    if (oz_tri_level(c, pl.tri_pairs[lv])) first = (int)lv;
+  for (size_t lv = 0; lv < pl.tri_pairs.size() && !ahead && first < 0; ++lv)
+    if (int8_level(lv) && !pairs_of(lv, side).empty() && !(is_top(lv) && F.t_ahead)) first = (int)lv;
   // ... unless the split sweep left them (chol_schur) and no int8 level below wrote over them
   bool have = false;
   if (first >= 0) {
-    const auto& pr = pl.tri_pairs[first][0];
-    have = c->oz_l21_valid && &F == &c->tr && pl.split_h > 0 && pr[0] == 0 && pr[1] == pl.split_h && pr[2] == F.NB;
+    const auto pr = pairs_of((size_t)first, side)[0];
+    have = c->oz_l21_valid && &F == &c->tr && hs > 0 && pr[0] == 0 && pr[1] == hs && pr[2] == F.NB;
     if (!have) CHK(oz_l21_ahead(c, F, pr[0], pr[1], pr[2]));
   }
   for (size_t lv = 0; lv < pl.tri_pairs.size(); ++lv) {
-    if (ozaki && oz_tri_level(c, pl.tri_pairs[lv])) {
-      for (size_t i = 0; i < pl.tri_pairs[lv].size(); ++i) {
-        const auto& pr = pl.tri_pairs[lv][i];
-        CHK(trtri_pair_ozaki(c, F, pr[0], pr[1], pr[2], ((int)lv == first && i == 0) ? (have ? 2 : 1) : 0));
+    const bool top = is_top(lv);
+    if (top && ahead) {
+      if (!int8_top || int8_side[1]) break;
+      HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_schur, 0));
+      const auto& pr = pl.tri_pairs[lv][0];
+      CHK(trtri_pair_ozaki(c, F, pr[0], pr[1], pr[2], c->oz_l21_valid ? 2 : 0, 1));
+      F.t_ahead = true;
+      break;
+    }
+    const std::vector<std::array<int, 3>> prs = pairs_of(lv, side);
+    if (prs.empty()) continue;
+    if (int8_level(lv)) {
+      for (size_t i = 0; i < prs.size(); ++i) {
+        const auto& pr = prs[i];
+        const int l21 = ((int)lv == first && i == 0) ? (have ? 2 : 1) : 0;
+        CHK(trtri_pair_ozaki(c, F, pr[0], pr[1], pr[2], l21, (top && F.t_ahead) ? 2 : 0));
       }
       continue;
     }
-    CHK(launch_gemm_range(c, pl.launches[pl.trtri[2 * lv]]));
-    CHK(launch_gemm_range(c, pl.launches[pl.trtri[2 * lv + 1]]));
+    const bool whole = side < 0 || top;
+    CHK(launch_gemm_range(c, pl.launches[whole ? pl.trtri[2 * lv] : pl.trtri_side[lv][2 * side]]));
+    CHK(launch_gemm_range(c, pl.launches[whole ? pl.trtri[2 * lv + 1] : pl.trtri_side[lv][2 * side + 1]]));
   }
+  if (ahead) F.x11 = hs;
   return GPE_OK;
 }
 
@@ -1479,7 +1591,7 @@ int factor_and_invert(gpe_ctx* c, int kernel, const double* delta, double nu, do
   ev_rec(c, 1);
   CHK(build_plan(c, c->tr));
   // the objective's sweep may split (its gradient evaluations; the value-only ones when asked)
-  CHK(potrf(c, c->tr, c->zaug_valid, objective && (invert || c->oz_chol >= 2)));
+  CHK(potrf(c, c->tr, c->zaug_valid, objective && (invert || c->oz_chol >= 2), objective && invert));
   if (kernel_fam(kernel) != FAM_GAUSS) {
     // Matern families: a pivot within the factorisation's backward error of zero is not
     // positive definite (k_pivot_floor).  The Gaussian kernels keep the reference's LAPACK
@@ -1732,21 +1844,22 @@ int oz_l21_ahead(gpe_ctx* c, Fact& F, int t0, int h, int t1) {
 
 // One pair (t0, h, t1) of a TRTRI level on the int8 cores (oz_tri_pair_launches): L21 from
 // A, X11 / X22 / X21 in B, T in the scratch block.  l21: 1 oz_l21_ahead ran, 2 the planes
-// are the split sweep's (chol_schur, earlier on this stream), 0 neither.
-int trtri_pair_ozaki(gpe_ctx* c, Fact& F, int t0, int h, int t1, int l21) {
+// are the split sweep's (chol_schur, earlier on this stream), 0 neither.  part: 0 both products,
+// 1 the first alone, 2 the second alone (oz_tri_pair_launches).
+int trtri_pair_ozaki(gpe_ctx* c, Fact& F, int t0, int h, int t1, int l21, int part) {
   CHK(oz_prepare(c, F));
   const OzTriPair* qp = oz_pair(c, t0, h, t1);
   if (!qp) return fail(c, GPE_ERR_STATE, "internal error: TRTRI pair without an int8 plan");
   const long long ld = F.n_pad;
   auto tile = [&](double* M, int i, int j) { return M + (long long)i * TILE + (long long)j * TILE * ld; };
   if (l21 == 1) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_oz, 0));
-  c->oz_l21_valid = false;   // the second product's planes go over them
+  if (part != 1) c->oz_l21_valid = false;   // the second product's planes go over them
   int rc = GPE_OK;
   oz_tri_pair_launches(c->stream, c->oz_c, *qp, c->dozl, tile(F.A, h, t0), tile(F.B, t0, t0), tile(F.B, h, h),
                        tile(F.B, h, t0), ld, c->dozt, c->dozp, c->dozr, c->dozx, l21 != 0,
                        [&](const OzProduct& p, double ops, double fl) {
                          if (rc == GPE_OK) rc = oz_gemm_crt(c, c->oz_c, p, ops, fl);
-                       });
+                       }, part);
   CHK(rc);
   HIPCHK(c, hipGetLastError());
   return GPE_OK;
@@ -1853,6 +1966,7 @@ gpe_ctx* gpe_create(int32_t device) {
     if (const char* et = std::getenv("GPEMU_OZAKI_TRI_MIN")) c->oz_tri_min = std::max(512, std::atoi(et));
     if (const char* ec = std::getenv("GPEMU_OZAKI_CHOL")) c->oz_chol = std::max(0, std::min(3, std::atoi(ec)));
     if (const char* ec = std::getenv("GPEMU_OZAKI_CHOL_MIN")) c->oz_chol_min = std::max(256, std::atoi(ec));
+    if (const char* ea = std::getenv("GPEMU_TRTRI_AHEAD")) c->tri_ahead_on = std::atoi(ea) != 0;
     if (const char* es = std::getenv("GPEMU_POTRF_SB")) {
       c->potrf_sb = std::max(1, std::min(8, std::atoi(es)));
       if (const char* colon = std::strchr(es, ':')) c->potrf_sb_min = std::max(0, std::atoi(colon + 1));
@@ -1877,6 +1991,8 @@ gpe_ctx* gpe_create(int32_t device) {
       !create_priority_stream(&c->stream2) ||
       hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming) != hipSuccess ||
       hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming) != hipSuccess ||
+      hipEventCreateWithFlags(&c->ev_l11, hipEventDisableTiming) != hipSuccess ||
+      hipEventCreateWithFlags(&c->ev_schur, hipEventDisableTiming) != hipSuccess ||
       hipEventCreateWithFlags(&c->ev_host, hipEventDisableTiming) != hipSuccess) {
     g_create_error = "failed to initialise device/stream";
     delete c;
@@ -1955,6 +2071,8 @@ void gpe_destroy(gpe_ctx* c) {
   for (hipEvent_t e : c->ev_pipe)
     if (e) (void)hipEventDestroy(e);
   if (c->ev_join) (void)hipEventDestroy(c->ev_join);
+  if (c->ev_l11) (void)hipEventDestroy(c->ev_l11);
+  if (c->ev_schur) (void)hipEventDestroy(c->ev_schur);
   if (c->ev_host) (void)hipEventDestroy(c->ev_host);
   if (c->stream2) {
     (void)hipStreamSynchronize(c->stream2);
@@ -2069,7 +2187,7 @@ int tiny_objective(gpe_ctx* c, bool gp4ml, int kernel, const double* hp, int n_h
   for (int k = d; k < TINY_DM; ++k) a.invd[k] = 0.0;
   c->linv_valid = false;
   c->zaug_valid = false;
-  c->tr.xdone = false;
+  c->tr.xclear();
   HIPCHK(c, hipStreamSynchronize(c->stream2));   // (a failed sweep's leftovers, as factor_and_invert)
   constexpr size_t tiny_doubles = 36 * DB_BS + TILE * 32;
   if (!c->dtiny) CHK(dalloc(c, &c->dtiny, tiny_doubles));
@@ -2186,7 +2304,7 @@ int snb_objective(gpe_ctx* c, bool gp4ml, int kernel, const double* hp, int n_hp
   for (int k = d; k < TINY_DM; ++k) a.invd[k] = 0.0;
   c->linv_valid = false;
   c->zaug_valid = false;
-  c->tr.xdone = false;
+  c->tr.xclear();
   HIPCHK(c, hipStreamSynchronize(c->stream2));
   if (c->snb_np != np) {
     c->snb_np = 0;

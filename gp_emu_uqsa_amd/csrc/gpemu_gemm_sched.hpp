@@ -92,9 +92,11 @@ inline void set_list(GemmLaunch& L, std::vector<unsigned>& tiles, const std::vec
 // Split K over workgroups for a launch with few tiles (small n, the TRTRI's first levels):
 // there each tile's K loop on one CU is the launch's latency, and the chip has 512
 // workgroup slots.  ks shares of at least 64 K each, at most SPLIT_SLOTS partials; beta = 0
-// problems only.  The launch then takes the implicit tile order (no list).
+// problems only.  The launch then takes the implicit tile order (no list).  t_all, k_all: decide
+// as for a launch of that many tiles and that longest K (a TRTRI level's launch dealt over two:
+// every tile then sums in the shares it has in the whole level's launch, bit for bit).
 constexpr int SPLIT_SLOTS = 512;
-inline void split_k(std::vector<GemmProb>& probs, double* part, int* tcnt) {
+inline void split_k(std::vector<GemmProb>& probs, double* part, int* tcnt, int t_all = 0, int k_all = 0) {
 #ifdef GPE_NO_SPLITK   // dev A/B build (tools/ab_libs.sh)
   return;
 #endif
@@ -104,6 +106,7 @@ inline void split_k(std::vector<GemmProb>& probs, double* part, int* tcnt) {
     T += prob_tiles(p);
     kmax = std::max(kmax, p.K);
   }
+  if (t_all > 0) { T = t_all; kmax = k_all; }
   if (T <= 0 || T >= 256) return;
   // shares of at least 64 of K (4 stages): one 128 x 128 x 128 tile is ~16 us of fp64
   // MFMA on one CU, the first TRTRI level's whole launch

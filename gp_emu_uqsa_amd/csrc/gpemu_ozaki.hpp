@@ -864,6 +864,16 @@ inline std::vector<std::array<int, 3>> trtri_level_pairs(int NB, int s) {
   return prs;
 }
 
+// A level's pairs on one side of tile column hs (the split Cholesky's, a power of two): side 0
+// those inside [0, hs), side 1 those inside [hs, NB).  A pair that straddles hs, the top one
+// (0, hs, NB), is on neither side.
+inline std::vector<std::array<int, 3>> trtri_side_pairs(const std::vector<std::array<int, 3>>& prs, int hs, int side) {
+  std::vector<std::array<int, 3>> out;
+  for (const auto& pr : prs)
+    if (!(pr[0] < hs && pr[2] > hs) && (pr[0] >= hs) == (side == 1)) out.push_back(pr);
+  return out;
+}
+
 // ---- one block pair (t0, h, t1) of a TRTRI level (tile units of 128) on the int8 cores:
 // the blocks X11 = X(t0:h, t0:h) and X22 = X(h:t1, h:t1) already inverted, L21 = L(h:t1,
 // t0:h):
@@ -910,16 +920,17 @@ inline OzTriPair oz_tri_pair_plan(int t0, int h, int t1, int N, std::vector<unsi
 // Pb x Pa doubles; planes: q.planes_bytes(N); res: q.resid_bytes(N); ex: Pa + Pb ints;
 // lists: the list array of oz_tri_pair_plan, on the device).  l21_done: L21's operand
 // (q.l21: planes at planes, exponents at ex) is already there (ordered before st's work by the
-// caller).  gc(p, ops, flops64) launches one product (oz_product_launch).
+// caller).  gc(p, ops, flops64) launches one product (oz_product_launch).  part: 0 both
+// products, 1 the first alone (T, which needs X11 and not X22), 2 the second alone (T is there).
 template <class GC>
 void oz_tri_pair_launches(hipStream_t st, const OzConst& k, const OzTriPair& q, const unsigned* lists, const double* L21,
                           const double* X11, const double* X22, double* X21, long long ld, double* T, int8_t* planes,
-                          int8_t* res, int* ex, bool l21_done, GC gc) {
+                          int8_t* res, int* ex, bool l21_done, GC gc, int part = 0) {
   int* exA = ex;
   int* exB = ex + q.Pb;
   int8_t* PA = planes;
   const long long rb = q.shape_a().res_bytes();
-  {   // T = L21 X11
+  if (part != 2) {   // T = L21 X11
     const long long pA = (long long)q.Pb * q.Pa, pB = (long long)q.Pa * q.Pa;
     int8_t* PB = planes + (size_t)k.nmod * pA;
     if (!l21_done) oz_operand(st, k, q.l21(L21, ld), q.Pb, q.Pa, exA, PA);
@@ -928,7 +939,7 @@ void oz_tri_pair_launches(hipStream_t st, const OzConst& k, const OzTriPair& q, 
                  OzOut{exA, exB, T, (long long)q.Pb, q.Rb, q.Ra, 0, 1.0}},
        q.ops_a, (double)q.Ra * q.Ra * q.Rb);
   }
-  {   // X21 = -X22 T (both operands' exponents, then both operands' planes)
+  if (part != 1) {   // X21 = -X22 T (both operands' exponents, then both operands' planes)
     const long long pA = (long long)q.Pb * q.Pb, pB = (long long)q.Pa * q.Pb;
     int8_t* PB = planes + (size_t)k.nmod * pA;
     const OzSrc x22{X22, ld, q.Rb, q.Rb, 2, true}, t{T, (long long)q.Pb, q.Ra, q.Rb, 0, false};
