@@ -30,6 +30,7 @@
 #include "gpemu_snb.hpp"
 #include "gpemu_ozaki.hpp"
 #include "gpemu_pivchol.hpp"
+#include "gpemu_imse.hpp"
 #include "gpemu_postgrad.hpp"
 #include "gpemu_postmean.hpp"
 #include "gpemu_postgroup.hpp"
@@ -48,7 +49,8 @@ constexpr int ADHOC_DESC_BASE = MAX_PROBS - 64;
 // Descriptor slots of the GEMMs outside the cached plans (adhoc_gemm), each named for its
 // owner.  Live within one call: gpe_noise_sample and gpe_posterior_pivchol run the posterior
 // first (ADHOC_POST_V, then the ADHOC_COV pair, re-uploaded per chunk and per block) and then
-// their own slot; ADHOC_PIVCHOL is uploaded once and launched after every panel of that call;
+// their own slot; ADHOC_PIVCHOL is uploaded once and launched after every panel of that call,
+// as is ADHOC_IMSE by gpe_posterior_imse;
 // gpe_posterior_grad re-uploads the ADHOC_POST_U pair per chunk, behind that chunk's ADHOC_POST_V.
 // The test and bench GEMMs stand alone.
 enum AdhocSlot {
@@ -57,6 +59,7 @@ enum AdhocSlot {
   ADHOC_NOISE = ADHOC_DESC_BASE + 3,      // gpe_noise_sample: the draws L U^T
   ADHOC_PIVCHOL = ADHOC_DESC_BASE + 4,    // gpe_posterior_pivchol: the trailing update S -= W W^T
   ADHOC_POST_U = ADHOC_DESC_BASE + 5,     // gpe_posterior_grad: U = L^-T V, then U += G tau^T (two slots)
+  ADHOC_IMSE = ADHOC_DESC_BASE + 7,       // gpe_posterior_imse: the trailing update over the candidates
   ADHOC_TEST = ADHOC_DESC_BASE + 8,       // gpe_test_gemm
   ADHOC_BENCH = ADHOC_DESC_BASE + 16,     // gpe_bench_gemm
 };
@@ -283,6 +286,11 @@ struct gpe_ctx {
   double* dPc = nullptr;
   double* dPcL = nullptr;
   size_t pc_cap = 0, pcl_cap = 0;
+  // integrated-variance design (gpe_posterior_imse): the state, outputs, d, lambda, w, flags and
+  // partials in one buffer; C (the reference x candidate cross-covariance); the panel W is dPcL
+  double* dIm = nullptr;
+  double* dImC = nullptr;
+  size_t im_cap = 0, imc_cap = 0;
   // gradient of the posterior (gpe_posterior_grad): the chunk's basis and its derivative, tau,
   // Q^-1, beta, hdim, the results, k_post_grad's partial sums and G padded to the GEMM's K step
   double* dPg = nullptr;
@@ -2037,7 +2045,7 @@ void gpe_destroy(gpe_ctx* c) {
                     c->aux.logdet, c->dinvdelta, c->dZ,
                     c->dR2, c->dWa, c->dskp, c->dgpart, c->dgram, c->dT2, c->dcpart, c->dcsum,
                     c->dW1, c->dW2, c->dW3, c->dXs, c->dXsw, c->dsmall, c->dtiny, c->dsnb, c->dRn, c->dNU,
-                    c->dVall, c->dXall, c->dTall, c->dPc, c->dPcL, c->dPg, c->dPm, c->dPgc};
+                    c->dVall, c->dXall, c->dTall, c->dPc, c->dPcL, c->dIm, c->dImC, c->dPg, c->dPm, c->dPgc};
   for (double* b : bufs)
     if (b) hipFree(b);
   if (c->dinfo) hipFree(c->dinfo);
@@ -3788,6 +3796,132 @@ int gpe_posterior_pivchol(gpe_ctx* c, int64_t m, const double* Xs, const double*
   *rank_out = rank;
   // the device copy is row-major m x k like L_out, columns >= rank written as zeros
   if (L_out) HIPCHK(c, hipMemcpy(L_out, Ld, (size_t)m * (size_t)k * sizeof(double), hipMemcpyDeviceToHost));
+  return GPE_OK;
+}
+
+// Greedy integrated-variance (IMSE) batch among the first mc of the m points (include/gpemu.h;
+// DESIGN.md).  The covariance is formed in c->dW3 as for gpe_posterior_pivchol; C, the
+// reference rows of the candidate columns, is copied out of it, and then two launches per pick
+// (gpemu_imse.hpp: k_im_col, k_im_sweep) work in panels of PC_PANEL picks: after a full panel
+// with steps left, S -= W W^T over the candidate tiles, so k_im_col reads at most PC_PANEL
+// earlier columns.  All k steps are queued without a synchronisation; the stop rule is the
+// device's, and the state, picks, gains and variances are read once at the end.
+int gpe_posterior_imse(gpe_ctx* c, int64_t m, int64_t mc, const double* Xs, const double* Hs, const double* beta,
+                       double sigma, const double* r_new, double r_scale, const double* w, int64_t k, double tol,
+                       double* mean_out, int64_t* piv_out, double* gain_out, double* pivvar_out,
+                       double* imse0_out, int64_t* rank_out) {
+  CHK(check_ready(c));
+  if (!c->factor_valid) return fail(c, GPE_ERR_STATE, "no resident factor (call gpe_factor)");
+  if (m <= 0 || !Xs || !Hs || !beta || !mean_out || !piv_out || !gain_out || !pivvar_out || !imse0_out || !rank_out)
+    return fail(c, GPE_ERR_ARG, "bad imse args");
+  if (m > 16384)
+    return fail(c, GPE_ERR_UNSUPPORTED, "the integrated-variance design takes at most 16384 points (one posterior chunk)");
+  if (mc < 1 || m - mc < 1 || k < 1 || k > mc || !(tol >= 0.0))
+    return fail(c, GPE_ERR_ARG, "bad imse args (1 <= mc < m, 1 <= k <= mc, tol >= 0)");
+  const long long mr = m - mc;
+  if (w)
+    for (long long r = 0; r < mr; ++r)
+      if (!(w[r] >= 0.0)) return fail(c, GPE_ERR_ARG, "bad imse args (a weight is negative or NaN)");
+  const long long mp = ((m + TILE - 1) / TILE) * TILE;
+  const int mct = (int)((mc + TILE - 1) / TILE);
+  const int Gc = mct * (TILE / PC_ROWS);
+  const int Gs = (int)((mc + IM_NC - 1) / IM_NC);
+  const long long mcp = (long long)Gc * PC_ROWS;
+  const long long ldc = (mr + 1) / 2 * 2;
+  if (c->prof) {
+    for (int i = 0; i < 8; ++i) c->phase_ms[i] = 0.0;
+    HIPCHK(c, hipEventRecord(c->ev[0], c->stream));
+  }
+  PostReq r{m, Xs, Hs, beta, sigma, 64, mean_out, PostVar::FULL_DW3, nullptr, nullptr, r_new, r_scale};
+  CHK(posterior_impl(c, r));
+  // workspace: [state | pivvar (k) | gain (k) | piv (k ints)] (read back in one copy, padded to
+  // an even number of doubles: lambda and w are read 16 bytes at a time), d (mcp), lambda (ldc),
+  // w (ldc), the partial scores (2 Gs), then the ints: flags (mcp) and partial indices (2 Gs)
+  static_assert(sizeof(ImState) == 3 * sizeof(double), "ImState");
+  const size_t kh = (size_t)(k + 1) / 2;
+  const size_t head = (3 + 2 * (size_t)k + kh + 1) / 2 * 2;
+  CHK(grow_buf(c, &c->dIm, &c->im_cap,
+               head + (size_t)mcp + 2 * (size_t)ldc + 2 * (size_t)Gs + ((size_t)mcp + 2 * (size_t)Gs + 1) / 2));
+  CHK(grow_buf(c, &c->dImC, &c->imc_cap, (size_t)ldc * (size_t)Gs * IM_NC));
+  CHK(grow_buf(c, &c->dPcL, &c->pcl_cap, (size_t)mp * PC_PANEL));
+  CHK(ensure_pinned(c, std::max<size_t>(head + 8, (size_t)ldc)));
+  double* W = c->dPcL;
+  ImArgs a;
+  a.S = c->dW3; a.ld = mp; a.mc = (int)mc; a.mr = (int)mr; a.Gc = Gc; a.Gs = Gs;
+  a.C = c->dImC; a.ldc = ldc;
+  a.st = reinterpret_cast<ImState*>(c->dIm);
+  a.pivvar = c->dIm + 3;
+  a.gain = c->dIm + 3 + k;
+  a.piv = reinterpret_cast<int*>(c->dIm + 3 + 2 * k);
+  a.d = c->dIm + head;
+  a.lam = a.d + mcp;
+  double* dw = a.lam + ldc;
+  a.w = dw;
+  a.psc = dw + ldc;
+  a.chosen = reinterpret_cast<int*>(a.psc + 2 * (size_t)Gs);
+  a.pidx = a.chosen + mcp;
+  a.tol = tol;
+  // the weights (NULL: 1 / m_r each), zero in the padding
+  for (long long i = 0; i < ldc; ++i) c->hpin[i] = i < mr ? (w ? w[i] : 1.0 / (double)mr) : 0.0;
+  HIPCHK(c, hipMemcpyAsync(dw, c->hpin, (size_t)ldc * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  // the trailing update's descriptor: S -= W W^T over the candidates' tiles, K = PC_PANEL
+  GemmLaunch Lt{};
+  if (k > PC_PANEL) {
+    CHK(adhoc_gemm(c, ADHOC_IMSE, {{GEMM_PLAIN, mkprob(W, mp, W, mp, c->dW3, mp, mct, mct, PC_PANEL, 0, -1.0, 1.0)}}, &Lt));
+    Lt.flops = 2.0 * (double)mct * TILE * (double)mct * TILE * PC_PANEL;
+  }
+  hipLaunchKernelGGL(k_im_init, dim3(1), dim3(256), 0, c->stream, a, (int)k);
+  HIPCHK(c, hipGetLastError());
+  hipLaunchKernelGGL(k_im_copy, dim3((unsigned)((ldc + 255) / 256), (unsigned)(Gs * IM_NC)), dim3(256), 0, c->stream, a);
+  HIPCHK(c, hipGetLastError());
+  float ms = 0.f;
+  if (c->prof) {
+    HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
+    HIPCHK(c, hipEventSynchronize(c->ev[1]));
+    (void)hipEventElapsedTime(&ms, c->ev[0], c->ev[1]);
+    c->phase_ms[0] = ms;
+  }
+  // step 0's scores: the sweep without a downdate
+  hipLaunchKernelGGL(k_im_sweep<false>, dim3(Gs), dim3(256), 0, c->stream, a, (const double*)W, -1);
+  HIPCHK(c, hipGetLastError());
+  for (long long t0 = 0; t0 < k; t0 += PC_PANEL) {
+    const int cols = (int)std::min<long long>(PC_PANEL, k - t0);
+    for (int j = 0; j < cols; ++j) {
+      hipLaunchKernelGGL(k_im_col, dim3(Gc), dim3(256), 0, c->stream, a, W, (int)(t0 + j), j);
+      HIPCHK(c, hipGetLastError());
+      if (t0 + j + 1 < k) {   // (the last pick's downdate would feed a step that is not taken)
+        hipLaunchKernelGGL(k_im_sweep<true>, dim3(Gs), dim3(256), 0, c->stream, a,
+                           (const double*)(W + (size_t)j * mp), (int)(t0 + j));
+        HIPCHK(c, hipGetLastError());
+      }
+    }
+    if (c->prof) HIPCHK(c, hipEventRecord(c->ev[2], c->stream));
+    if (t0 + cols < k) CHK(launch_gemm_range(c, Lt));
+    if (c->prof) {   // (profiling only: one synchronisation per panel)
+      HIPCHK(c, hipEventRecord(c->ev[3], c->stream));
+      HIPCHK(c, hipEventSynchronize(c->ev[3]));
+      (void)hipEventElapsedTime(&ms, c->ev[1], c->ev[2]);
+      c->phase_ms[1] += ms;
+      (void)hipEventElapsedTime(&ms, c->ev[2], c->ev[3]);
+      c->phase_ms[2] += ms;
+      HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
+    }
+  }
+  HIPCHK(c, hipMemcpyAsync(c->hpin, c->dIm, head * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (c->prof) c->phase_ms[6] = c->phase_ms[0] + c->phase_ms[1] + c->phase_ms[2];
+  ImState st;
+  std::memcpy(&st, c->hpin, sizeof(st));
+  const long long rank = st.rank;
+  if (rank < 0 || rank > k) return fail(c, GPE_ERR_HIP, "internal error: integrated-variance design rank out of range");
+  const int* pv32 = reinterpret_cast<const int*>(c->hpin + 3 + 2 * k);
+  for (long long t = 0; t < k; ++t) {
+    piv_out[t] = t < rank ? pv32[t] : -1;
+    pivvar_out[t] = t < rank ? c->hpin[3 + t] : 0.0;
+    gain_out[t] = t < rank ? c->hpin[3 + k + t] : 0.0;
+  }
+  *imse0_out = st.imse0;
+  *rank_out = rank;
   return GPE_OK;
 }
 

@@ -18,7 +18,9 @@ reference's RNG order, in batches of at most _BATCH doubles.
 ``max_variance_design`` (no counterpart in the reference) asks a trained emulator where the
 next simulator runs would teach it most: the greedy maximum-variance batch among candidate
 points, the first pivots of a pivoted Cholesky of their posterior covariance on the GPU
-(gpe_posterior_pivchol).
+(gpe_posterior_pivchol).  ``imse_design`` answers the same question with the integrated-variance
+rule: the batch that most reduces the posterior variance averaged over a reference sample of
+the inputs the emulator will be used on (gpe_posterior_imse).
 """
 from __future__ import annotations
 
@@ -106,3 +108,53 @@ def max_variance_design(E, candidates, k, tol=0.0):
     _, piv, pivvar, _, _ = ctx.posterior_pivchol(xs.inputs, xs.H, E.par.beta, float(E.par.sigma), k=int(k),
                                                  tol=tol, want_L=False)
     return piv, pivvar
+
+
+def _scaled_points(E, points):
+    x = _np.asarray(points, dtype=float)
+    if x[0].size == 1:
+        x = _np.array([x]).T
+    if x[0, :].size != E.training.inputs[0, :].size:
+        print("ERROR: test points have different number of columns to data in emulator. Exiting.")
+        raise SystemExit(1)
+    return x
+
+
+def imse_design(E, candidates, reference, k, weights=None, tol=1e-8):
+    """The greedy integrated-variance (IMSE, Cohn's ALC) batch of k points among `candidates`.
+
+    Each pick is the candidate whose run most reduces the posterior variance of emulator E
+    averaged over `reference`, a sample of the input distribution the emulator will be used on
+    (`weights`: one value >= 0 per reference point, default equal), given E.training and the
+    candidates picked before it, with E's current hyperparameters (the outputs at the picks are
+    not needed).  Where ``max_variance_design`` goes to the boundary of the input box, this rule
+    goes where the reference sample is.  Both arrays are points in the emulator's scaled input
+    space, one row each, with as many columns as E's training inputs.
+    Returns (indices into candidates, the reduction of the averaged variance each pick bought,
+    the averaged variance before any pick): after t picks imse0 - sum(gains[:t]) is left.
+    Fewer than k picks if no candidate is eligible any more: a candidate whose remaining
+    variance has fallen to tol * the largest initial one is dropped.  The default 1e-8 is the
+    accuracy of the posterior covariance itself: such a variance carries fewer than three
+    correct digits, and the score, a ratio with it as the denominator, is noise.
+    At most 16384 candidates and reference points together (one chunk of the posterior), and
+    k at most the number of candidates: ValueError beyond."""
+    x = _scaled_points(E, candidates)
+    xr = _scaled_points(E, reference)
+    if x.shape[0] + xr.shape[0] > MAX_CANDIDATES:
+        raise ValueError(f"imse_design takes at most {MAX_CANDIDATES} candidates and reference points together, "
+                         f"got {x.shape[0]} + {xr.shape[0]}")
+    k = int(k)
+    if not 1 <= k <= x.shape[0]:
+        raise ValueError(f"imse_design picks 1 <= k <= {x.shape[0]} (the candidates), got k = {k}")
+    w = None
+    if weights is not None:
+        w = _np.asarray(weights, dtype=float).ravel()
+        if w.size != xr.shape[0] or not _np.all(w >= 0.0):
+            raise ValueError("imse_design takes one weight >= 0 per reference point")
+    from . import model as _model
+    xs = _model.Data(_np.vstack([x, xr]), None, E.basis, E.par, E.beliefs, E.K)
+    ctx = _model.upload_training(E.training)
+    ctx.ensure_factor(E.K.kind, E.K.d, float(E.K.n), 1.0, E.training.r_scale())
+    _, piv, gain, _, imse0, _ = ctx.posterior_imse(xs.inputs, xs.H, E.par.beta, float(E.par.sigma), x.shape[0], k,
+                                                   w=w, tol=tol)
+    return piv, gain, imse0

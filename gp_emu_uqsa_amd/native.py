@@ -91,6 +91,9 @@ SIGNATURES = {
     "gpe_posterior_pivchol": (_ct.c_int, [_VP, _ct.c_int64, _D, _D, _D, _ct.c_double, _D, _ct.c_double,
                                           _ct.c_int64, _ct.c_double, _D, _ct.POINTER(_ct.c_int64), _D, _D,
                                           _ct.POINTER(_ct.c_int64)]),
+    "gpe_posterior_imse": (_ct.c_int, [_VP, _ct.c_int64, _ct.c_int64, _D, _D, _D, _ct.c_double, _D, _ct.c_double,
+                                       _D, _ct.c_int64, _ct.c_double, _D, _ct.POINTER(_ct.c_int64), _D, _D, _D,
+                                       _ct.POINTER(_ct.c_int64)]),
     "gpe_solve": (_ct.c_int, [_VP, _ct.c_int32, _D, _D]),
     "gpe_sense_pairs": (_ct.c_int, [_VP, _ct.c_int32, _D, _D, _ct.c_int32, _D, _D, _D]),
     "gpe_gauss_transform": (_ct.c_int, [_VP, _ct.c_int64, _ct.c_int32, _ct.POINTER(_ct.c_int32), _D, _D, _D,
@@ -437,6 +440,39 @@ class Context:
                                                    _ptr(L), _ct.byref(rank)), "gpe_posterior_pivchol")
         r = int(rank.value)
         return mean, piv[:r].copy(), pivvar[:r].copy(), (L[:, :r].copy() if L is not None else None), r
+
+    def posterior_imse(self, Xs, Hs, beta, sigma, mc, k, w=None, tol=1e-8, r_new=None, r_scale=0.0):
+        """Greedy integrated-variance (IMSE) batch for the resident factor: the first mc rows of
+        Xs are candidates, the rest a reference sample with weights w (None: equal).  Up to k
+        picks, each the candidate whose run most reduces the w-weighted posterior variance of
+        the reference points given the picks before it; a candidate whose remaining variance
+        is <= tol * the largest initial one is no longer eligible.  Returns
+        (mean, piv, gain, pivvar, imse0, rank) trimmed to rank: piv (rank,) the candidates in the
+        order chosen, gain the reduction each bought, pivvar their conditional variances, imse0
+        the weighted variance before any pick.  At most 16384 points in all."""
+        Xs = _f64(Xs)
+        if Xs.ndim == 1:
+            Xs = Xs.reshape(-1, 1)
+        m = Xs.shape[0]
+        mc, k = int(mc), int(k)
+        Hs = _f64(Hs, (m, self.q))
+        beta = _f64(beta).ravel()
+        rn = None if r_new is None else _f64(r_new, (m,))
+        wv = None if w is None else _f64(w, (max(m - mc, 0),))
+        kk = max(k, 1)
+        mean = _np.zeros(m)
+        piv = _np.zeros(kk, dtype=_np.int64)
+        gain = _np.zeros(kk)
+        pivvar = _np.zeros(kk)
+        imse0 = _ct.c_double(0.0)
+        rank = _ct.c_int64(0)
+        self._check(self.lib.gpe_posterior_imse(self._h, m, mc, _ptr(Xs), _ptr(Hs), _ptr(beta), float(sigma),
+                                                _ptr(rn), float(r_scale), _ptr(wv), k, float(tol), _ptr(mean),
+                                                piv.ctypes.data_as(_ct.POINTER(_ct.c_int64)), _ptr(gain),
+                                                _ptr(pivvar), _ct.byref(imse0), _ct.byref(rank)),
+                    "gpe_posterior_imse")
+        r = int(rank.value)
+        return mean, piv[:r].copy(), gain[:r].copy(), pivvar[:r].copy(), float(imse0.value), r
 
     # -- sensitivity building blocks (resident factor)
     def solve(self, B):

@@ -36,7 +36,7 @@ extern "C" {
                                 gpe_device_synchronize, gpe_build_id;
                                 9: gpe_dist_local_rows takes the basis width q;
                                 10: gpe_ozaki_stats (gpe_loo, gpe_posterior_pivchol,
-                                gpe_posterior_grad, gpe_posterior_mean, gpe_posterior_groups and the test
+                                gpe_posterior_imse, gpe_posterior_grad, gpe_posterior_mean, gpe_posterior_groups and the test
                                 hooks gpe_test_oz_product and gpe_test_gemm_group were added within 10:
                                 additions, nothing existing changed) */
 
@@ -475,11 +475,50 @@ int gpe_posterior_pivchol(gpe_ctx* ctx, int64_t m, const double* Xs, const doubl
                           int64_t k, double tol, double* mean_out, int64_t* piv_out,
                           double* pivvar_out, double* L_out, int64_t* rank_out);
 
+/* Greedy integrated-variance (IMSE, Cohn's ALC) batch design (an addition within ABI 10; the
+ * reference has no counterpart).  Xs holds m = mc + mr points: the first mc rows are the
+ * candidates, the last mr = m - mc rows a reference sample of the input distribution.  S is
+ * exactly the matrix gpe_posterior_pivchol works on: gpe_posterior(full_var = 1,
+ * precision = 64)'s covariance plus sigma^2 r_scale r_new on its diagonal (r_new m values or
+ * NULL; "diagonal" by index); mean_out (m) is its mean.  w holds mr weights >= 0, NULL
+ * meaning 1 / mr each.  Each step picks the candidate whose run most reduces the posterior
+ * variance averaged (with w) over the reference points.
+ * State, for candidates c and reference rows r: d_c = S_cc, C_rc = S[mc + r, c],
+ * thr = tol max_c d^0_c (over the candidates only), *imse0_out = sum_r w_r S[mc + r, mc + r].
+ * Step t = 0, 1, ...:
+ *   q_c = sum_r w_r C_rc^2 and score_c = q_c / d_c; candidate c is eligible if it is unchosen,
+ *   d_c > thr and its score is not NaN; stop before the step if t = k or nobody is eligible;
+ *   p = the eligible candidate with the largest score (lowest index on ties; a NaN never wins);
+ *   piv_out[t] = p, gain_out[t] = score_p, pivvar_out[t] = d_p;
+ *   l_c = (S_cp - sum_{s<t} L_cs L_ps) / sqrt(d_p) for unchosen c (exactly 0 for candidates
+ *   chosen earlier, sqrt(d_p) at c = p), lambda_r = C_rp / sqrt(d_p);
+ *   C_rc -= lambda_r l_c and d_c -= l_c^2 for unchosen c.
+ * gain_out[t] is the reduction of sum_r w_r Var(reference r) bought by observing candidate p
+ * with the variance on S's diagonal: the integrated variance left after t picks is
+ * imse0 - sum_{s<t} gain[s].  *rank_out = picks taken; piv_out / gain_out / pivvar_out (k
+ * values) are -1 / 0 / 0 from rank on.
+ * 1 <= mc < m <= 16384 (one chunk of gpe_posterior): beyond, GPE_ERR_UNSUPPORTED; mc < 1,
+ * m - mc < 1, k outside [1, mc], tol < 0, a negative or NaN weight or a NULL among the
+ * required pointers (all but r_new and w): GPE_ERR_ARG, before any device work;
+ * GPE_ERR_STATE without a resident factor.  Repeated calls on one factor return the same
+ * bits; the resident factor stays usable.
+ * Two launches per pick (gpemu_imse.hpp: the column of L over the candidates, then one
+ * streaming pass over C that downdates it and forms the next scores) in panels of 128 picks,
+ * a grouped MFMA GEMM S -= W W^T over the candidates after each full panel; no
+ * synchronisation before the end. */
+int gpe_posterior_imse(gpe_ctx* ctx, int64_t m, int64_t mc, const double* Xs, const double* Hs,
+                       const double* beta, double sigma, const double* r_new, double r_scale,
+                       const double* w, int64_t k, double tol, double* mean_out,
+                       int64_t* piv_out, double* gain_out, double* pivvar_out,
+                       double* imse0_out, int64_t* rank_out);
+
 /* Per-phase device time of the most recent gpe_objective call, in ms:
  * [0] K-build, [1] Cholesky, [2] triangular inverse, [3] A^-1 (L^-T L^-1),
  * [4] skinny solves / small algebra, [5] gradient contraction, [6] total.
  * After gpe_posterior_pivchol: [0] forming the covariance, [1] the pivot steps, [2] the
  * trailing updates and panel copies, [6] their sum (one synchronisation per panel is added).
+ * After gpe_posterior_imse: [0] forming the covariance and copying C, [1] the column and
+ * sweep kernels, [2] the trailing updates, [6] their sum (one synchronisation per panel is added).
  * After gpe_posterior_grad: [0] k_post_grad's device time summed over the chunks, [1] the
  * number of chunks (one synchronisation per chunk is added).
  * After gpe_posterior_mean: [0] k_post_mean's device time summed over the chunks, [1] the
