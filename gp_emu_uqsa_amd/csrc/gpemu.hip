@@ -87,6 +87,11 @@ struct Plan {
   // the augmented row's tiles [h, NB) by the first h columns
   int split_h = 0, aug_mid = -1;
   std::vector<int> sfused, sfused_aug, sgrp, sgrp_aug;
+  // the nested split (build_plan): tile column q = h / 2 > 0 where phase A is split once more,
+  // its three sweeps' launches per step ([0, q) over all rows, [q, h) over the rows from q,
+  // [h, NB)) and the launch that updates the augmented row's tiles [q, h) by the first q columns
+  int split_q = 0, aug_q = -1;
+  std::vector<int> nfused, nfused_aug, ngrp, ngrp_aug;
   // the TRTRI by sides of the split column (tri_ahead; sides: these are built): per level below
   // the top one its launch pairs {T^T, X21} of the block pairs inside [0, h), then of those
   // inside [h, NB) (-1: none)
@@ -106,6 +111,9 @@ constexpr int FACT_FLAG_INTS = 6;
 // rows of the Schur complement from which the objective's Cholesky is split and S runs on the
 // int8 cores (GPEMU_OZAKI_CHOL_MIN)
 constexpr int OZ_CHOL_MIN = 8192;
+// rows of the trapezoid (those from the inner split column q on) from which the split sweep's
+// first phase is split once more (GPEMU_OZAKI_CHOL_NEST_MIN)
+constexpr int OZ_CHOL_NEST_MIN = 12288;
 
 // one TRTRI block pair on the int8 cores (trtri_pair_ozaki): rows of X11 / X22 (Ra / Rb),
 // padded to 256 (Pa / Pb), and its two products' tile lists in dozl
@@ -228,6 +236,17 @@ struct gpe_ctx {
   int oz_chol_llen = 0;
   double oz_chol_ops = 0.0;
   bool oz_chol_ready = false;     // oz_chol_q and the list are planned for this n_pad
+  // the split sweep's first phase split once more at q = h / 2, the trapezoid's update by the
+  // columns [0, q) a second int8 product (OzCholNest, chol_schur at q).  oz_nest: 0 off
+  // (GPEMU_OZAKI_CHOL_NEST=0: the two-phase sweep); on only with the split itself, for the
+  // gradient evaluations (and gpe_factor's sweep under oz_chol 3), from oz_nest_min rows of the
+  // trapezoid (GPEMU_OZAKI_CHOL_NEST_MIN)
+  int oz_nest = 1, oz_nest_min = OZ_CHOL_NEST_MIN;
+  OzCholNest oz_nest_q{};         // its plan, the list in dozl and its int8 operations
+  long long oz_nest_loff = 0;
+  int oz_nest_llen = 0;
+  double oz_nest_ops = 0.0;
+  bool oz_nest_ready = false;
   // dozp / dozx[0, Pb) hold L21's planes and exponents of the resident factor (written by
   // chol_schur; cleared by everything else that writes them and by gpe_set_data)
   bool oz_l21_valid = false;
@@ -573,6 +592,7 @@ void add_launch(Plan& pl, GemmKind kind, const std::vector<GemmProb>& probs, dou
 
 bool oz_use(const gpe_ctx* c);
 int oz_chol_split(const gpe_ctx* c, const Fact& F);
+int oz_chol_nest_split(const gpe_ctx* c, const Fact& F, int h);
 
 // objective evaluations in flight per device (gpe_objective), for the auto Cholesky schedule
 std::atomic<int> g_inflight[64];
@@ -1135,6 +1155,38 @@ int build_plan(gpe_ctx* c, Fact& F) {
         pl.sides = false;
       }
     }
+    // --- the nested split: phase A once more at q = h / 2, the trapezoid's update by the columns
+    // [0, q) a second int8 product (chol_schur at q): columns [0, q) over all rows, then [q, h)
+    // over the rows from q on, then the Schur complement's sweep as above; before the middle sweep
+    // the augmented row's tiles [q, h) take the first q columns' update in one launch (its tiles
+    // [h, NB) still take all h columns' at h: aug_mid).  Left out the same way
+    if (const int q = pl.split_h ? oz_chol_nest_split(c, F, h) : 0) {
+      const size_t nl2 = pl.launches.size(), np2 = pl.probs.size(), nt2 = pl.tiles.size();
+      pl.nfused.assign(NB, -1);
+      pl.nfused_aug.assign(NB, -1);
+      if (c->potrf_group) {
+        pl.ngrp.assign(NB, -1);
+        if (pl.aug) pl.ngrp_aug.assign(NB, -1);
+      }
+      const std::array<std::vector<int>*, 4> nx = {&pl.nfused, &pl.nfused_aug, &pl.ngrp, &pl.ngrp_aug};
+      CHK(sweep(0, q, NB, nx));
+      CHK(sweep(q, h - q, NB - q, nx));
+      for (int v = 0; v < 4; ++v)   // (h, NB - h, NB - h): the split sweep's own launches
+        for (int t = h; t < NB && !nx[v]->empty(); ++t) (*nx[v])[t] = (*ix[v])[t];
+      if (pl.aug) {
+        pl.aug_q = (int)pl.launches.size();
+        add_launch(pl, GEMM_PLAIN, {mkprob(F.Faug, TILE, tile(A, q, 0), ld, F.Faug + (long long)q * TILE * TILE, TILE, 1, h - q,
+                                  q * TILE, 0, -1.0, 1.0)}, 0.0);
+      }
+      pl.split_q = q;
+      if ((int)pl.probs.size() > limit) {
+        pl.launches.resize(nl2);
+        pl.probs.resize(np2);
+        pl.tiles.resize(nt2);
+        pl.split_q = 0;
+        pl.aug_q = -1;
+      }
+    }
   }
   if ((int)pl.probs.size() > limit) return fail(c, GPE_ERR_UNSUPPORTED, "GEMM schedule too large");
   for (auto& L : pl.launches) L.first += F.desc_base;
@@ -1251,19 +1303,22 @@ int kbuild(gpe_ctx* c, int kernel, double nu, double s2, double rscale) {
 // tile-list array for one workspace's plan resets the other's (build_plan), e.g. the
 // aux plan of gpe_noise_sample between gpe_factor and a later on-demand TRTRI / LAUUM.
 int oz_prepare(gpe_ctx* c, Fact& F);
-int chol_schur(gpe_ctx* c, Fact& F, hipStream_t st, bool with_aug);
+int chol_schur(gpe_ctx* c, Fact& F, hipStream_t st, bool with_aug, int at);
 int trtri(gpe_ctx* c, Fact& F, bool ozaki = false, bool ahead = false);
 
 // split: the objective's sweep of the training matrix, in two phases around the int8 Schur
 // complement where the plan has them (Plan::split_h, chol_schur); ahead: the caller inverts
 // next, so X11 and the top pair's T start on the context stream while the second phase runs
 // on the high-priority one (trtri's ahead)
-int potrf(gpe_ctx* c, Fact& F, bool with_aug = false, bool split = false, bool ahead = false) {
+// nest: with the split, its first phase split once more where the plan has that (Plan::split_q,
+// chol_schur at q)
+int potrf(gpe_ctx* c, Fact& F, bool with_aug = false, bool split = false, bool ahead = false, bool nest = false) {
   CHK(build_plan(c, F));
   const int hs = split ? F.plan.split_h : 0;
   if (hs) CHK(oz_prepare(c, F));   // (may rebuild the plan: before pl is taken)
   const Plan& pl = F.plan;
   if (hs != (split ? pl.split_h : 0)) return fail(c, GPE_ERR_STATE, "internal error: split plan changed");
+  const int qs = (hs && nest) ? pl.split_q : 0;
   const int NB = F.NB;
   // flags, the group schedule's counters and the launches' list tickets start at zero
   HIPCHK(c, hipMemsetAsync(F.flags, 0, FACT_FLAG_INTS * (size_t)NB * sizeof(int), c->stream));
@@ -1272,17 +1327,19 @@ int potrf(gpe_ctx* c, Fact& F, bool with_aug = false, bool split = false, bool a
   F.xclear(tri_ahead ? hs : 0);   // the sweep leaves only X's diagonal 16 x 16 blocks (ensure_xdiag)
   const bool grp = c->potrf_group &&
                    (c->potrf_mode == 1 || (c->potrf_mode == 0 && g_inflight[c->device & 63].load() <= 1));
-  const std::vector<int>& fidx = hs ? (grp ? (wa ? pl.sgrp_aug : pl.sgrp) : (wa ? pl.sfused_aug : pl.sfused))
-                                    : (grp ? (wa ? pl.grp_aug : pl.grp) : (wa ? pl.fused_aug : pl.fused));
+  const std::vector<int>& fidx = qs ? (grp ? (wa ? pl.ngrp_aug : pl.ngrp) : (wa ? pl.nfused_aug : pl.nfused))
+                                 : hs ? (grp ? (wa ? pl.sgrp_aug : pl.sgrp) : (wa ? pl.sfused_aug : pl.sfused))
+                                      : (grp ? (wa ? pl.grp_aug : pl.grp) : (wa ? pl.fused_aug : pl.fused));
   if (c->chol_prio) {
     // the whole sweep on the context's high-priority stream: with two tries in flight
     // its chain workgroups are dispatched ahead of the other try's inverse tiles
     HIPCHK(c, hipEventRecord(c->ev_fork, c->stream));
     HIPCHK(c, hipStreamWaitEvent(c->stream2, c->ev_fork, 0));
     for (int t = 0; t < NB; ++t) {
+      if (qs && t == qs) CHK(chol_schur(c, F, c->stream2, wa, qs));
       if (hs && t == hs) {
         if (tri_ahead) HIPCHK(c, hipEventRecord(c->ev_l11, c->stream2));
-        CHK(chol_schur(c, F, c->stream2, wa));
+        CHK(chol_schur(c, F, c->stream2, wa, hs));
         if (tri_ahead) {
           HIPCHK(c, hipEventRecord(c->ev_schur, c->stream2));
           CHK(trtri(c, F, true, true));
@@ -1305,7 +1362,8 @@ int potrf(gpe_ctx* c, Fact& F, bool with_aug = false, bool split = false, bool a
   }
 #endif
   for (int t = 0; t < NB; ++t) {
-    if (hs && t == hs) CHK(chol_schur(c, F, c->stream, wa));
+    if (qs && t == qs) CHK(chol_schur(c, F, c->stream, wa, qs));
+    if (hs && t == hs) CHK(chol_schur(c, F, c->stream, wa, hs));
     if (fidx[t] >= 0) CHK(launch_gemm_range(c, pl.launches[fidx[t]]));
   }
   return GPE_OK;
@@ -1599,7 +1657,9 @@ int factor_and_invert(gpe_ctx* c, int kernel, const double* delta, double nu, do
   ev_rec(c, 1);
   CHK(build_plan(c, c->tr));
   // the objective's sweep may split (its gradient evaluations; the value-only ones when asked)
-  CHK(potrf(c, c->tr, c->zaug_valid, objective && (invert || c->oz_chol >= 2), objective && invert));
+  // ... and nest with its gradient evaluations (and gpe_factor's sweep under the test switch 3)
+  CHK(potrf(c, c->tr, c->zaug_valid, objective && (invert || c->oz_chol >= 2), objective && invert,
+            objective && (invert || c->oz_chol == 3)));
   if (kernel_fam(kernel) != FAM_GAUSS) {
     // Matern families: a pivot within the factorisation's backward error of zero is not
     // positive definite (k_pivot_floor).  The Gaussian kernels keep the reference's LAPACK
@@ -1690,6 +1750,14 @@ int oz_chol_split(const gpe_ctx* c, const Fact& F) {
   return (F.NB - h) * TILE >= c->oz_chol_min ? h : 0;
 }
 
+// The tile column q = h / 2 at which the split sweep's first phase is split once more (0: not):
+// q even, so the product's sums and the trapezoid's columns are whole 256-tiles, and the
+// trapezoid's rows [q, NB) at least oz_nest_min
+int oz_chol_nest_split(const gpe_ctx* c, const Fact& F, int h) {
+  if (!c->oz_nest || h < 4 || (h / 2) % 2) return 0;
+  return (F.NB - h / 2) * TILE >= c->oz_nest_min ? h / 2 : 0;
+}
+
 // the TRTRI levels on the int8 cores: every pair of a level whose blocks have at least
 // oz_tri_min rows (GPEMU_OZAKI_TRI_MIN; the levels below stay fp64: their products are a
 // few short tiles)
@@ -1707,6 +1775,7 @@ int oz_prepare(gpe_ctx* c, Fact& F) {
   c->oz_np2 = 0;
   c->oz_npad = 0;
   c->oz_chol_ready = false;
+  c->oz_nest_ready = false;
   c->oz_l21_valid = false;
   CHK(build_plan(c, F));
   const int N = c->oz_nmod;
@@ -1745,6 +1814,20 @@ int oz_prepare(gpe_ctx* c, Fact& F) {
     resid = std::max(resid, (size_t)q.shape_schur().res_bytes() * N);
     nex = std::max(nex, (size_t)q.Pb);
     c->oz_chol_ready = true;
+    // the nested split's product (OzCholNest): its list after S's
+    if (const int qs = F.plan.split_q) {
+      const OzCholNest nq = oz_chol_nest_plan(qs, hs, F.NB);
+      const std::vector<unsigned> ln = nq.shape().list();
+      c->oz_nest_q = nq;
+      c->oz_nest_loff = (long long)all.size();
+      c->oz_nest_llen = (int)ln.size();
+      all.insert(all.end(), ln.begin(), ln.end());
+      c->oz_nest_ops = nq.shape().ops(N);
+      planes = std::max(planes, nq.planes_bytes(N));
+      resid = std::max(resid, nq.resid_bytes(N));
+      nex = std::max(nex, (size_t)nq.Pb);
+      c->oz_nest_ready = true;
+    }
   }
   CHK(dalloc(c, &c->dozp, planes));
   CHK(dalloc(c, &c->dozr, resid));
@@ -1789,8 +1872,29 @@ int oz_gemm_crt(gpe_ctx* c, const OzConst& k, const OzProduct& p, double ops, do
 // planes (as for the top TRTRI pair's first product, which then reuses them: oz_l21_valid);
 // S = A22 - L21 L21^T: one product over the lower 256-tiles, K = Pa, and its reconstruction
 // subtracted from A22's lower 128-tiles in place.
-int chol_schur(gpe_ctx* c, Fact& F, hipStream_t st, bool with_aug) {
+// at: the split column h, or the nested split's q (Plan::split_q) -- there L's columns [0, q) are
+// final over all rows and the same steps update the trapezoid {rows [q, NB), columns [q, h)}: the
+// augmented row's tiles [q, h) by the first q columns, the rows [q, NB) of those columns to
+// planes, serving as both operands (OzCholNest), the product over the triangle capped at
+// column h subtracted in place.  The product at h then converts L21 over those planes.
+int chol_schur(gpe_ctx* c, Fact& F, hipStream_t st, bool with_aug, int at) {
   const Plan& pl = F.plan;
+  if (at != pl.split_h) {
+    const OzCholNest& n = c->oz_nest_q;
+    if (!c->oz_nest_ready || at != pl.split_q || n.q != at || n.h != pl.split_h)
+      return fail(c, GPE_ERR_STATE, "internal error: nested split Cholesky without an int8 plan");
+    if (with_aug) CHK(launch_gemm_range(c, pl.launches[pl.aug_q], st));
+    const long long ld = F.n_pad;
+    c->oz_l21_valid = false;
+    oz_operand(st, c->oz_c, n.src(F.A + (long long)n.q * TILE, ld), n.Pb, n.K, c->dozx, c->dozp);
+    HIPCHK(c, hipGetLastError());
+    const OzShape s = n.shape();
+    const OzOpnd l{c->dozp, (long long)n.Pb * n.K, n.K, 0};
+    return oz_gemm_crt(c, c->oz_c,
+                       OzProduct{s, l, l, c->dozl + c->oz_nest_loff, c->oz_nest_llen, c->dozr, s.res_bytes(),
+                                 OzOut{c->dozx, c->dozx, F.A + (long long)n.q * TILE * (ld + 1), ld, n.Rb, n.cols, 1, -1.0, 1}},
+                       c->oz_nest_ops, (double)n.cols * (2.0 * n.Rb - n.cols) * n.K, st);
+  }
   const OzTriPair& q = c->oz_chol_q;
   if (!c->oz_chol_ready || q.h != pl.split_h) return fail(c, GPE_ERR_STATE, "internal error: split Cholesky without an int8 plan");
   if (with_aug) CHK(launch_gemm_range(c, pl.launches[pl.aug_mid], st));
@@ -1974,6 +2078,8 @@ gpe_ctx* gpe_create(int32_t device) {
     if (const char* et = std::getenv("GPEMU_OZAKI_TRI_MIN")) c->oz_tri_min = std::max(512, std::atoi(et));
     if (const char* ec = std::getenv("GPEMU_OZAKI_CHOL")) c->oz_chol = std::max(0, std::min(3, std::atoi(ec)));
     if (const char* ec = std::getenv("GPEMU_OZAKI_CHOL_MIN")) c->oz_chol_min = std::max(256, std::atoi(ec));
+    if (const char* ec = std::getenv("GPEMU_OZAKI_CHOL_NEST")) c->oz_nest = std::atoi(ec) != 0;
+    if (const char* ec = std::getenv("GPEMU_OZAKI_CHOL_NEST_MIN")) c->oz_nest_min = std::max(256, std::atoi(ec));
     if (const char* ea = std::getenv("GPEMU_TRTRI_AHEAD")) c->tri_ahead_on = std::atoi(ea) != 0;
     if (const char* es = std::getenv("GPEMU_POTRF_SB")) {
       c->potrf_sb = std::max(1, std::min(8, std::atoi(es)));
@@ -4330,14 +4436,15 @@ static int oz_test_product(gpe_ctx* c, const gpe_oz_operand& a, const gpe_oz_ope
     }
     if (p.kbeg < 0 || p.kbeg > 3 || p.kend < 0 || p.kend > 1 || p.kdiv < 1) return bad("bad kbeg / kend / kdiv");
     if (p.ti0 < 0 || p.ti0 >= Pa / OZ_T) return bad("ti0 past the last tile row");
-    if (p.tri && Pb < Pa) return bad("tri: B has fewer tile rows than A");
+    // tri with fewer tile rows in B than in A: the triangle capped at B's (OzShape::lower_capped)
+    if (p.tri && Pb < Pa && p.ti0 != 0) return bad("tri: B has fewer tile rows than A and ti0 > 0");
   }
   if (p.rows <= OZ_T * p.ti0 || p.rows > Pa || p.cols < 1 || p.cols > Pb) return bad("rows / cols outside the product");
   if (!C || p.ldc < 1 || p.c_len < 1 || (long long)(p.rows - 1 - OZ_T * p.ti0) + (long long)(p.cols - 1) * p.ldc >= p.c_len)
     return bad("C too small for rows x cols at ldc");
   const int K = p.K, ti0 = p.ti0, nti = Pa / OZ_T - ti0, ntj = Pb / OZ_T;
   const OzConst k = oz_consts(p.nmod, K);
-  const OzShape s{nti, p.tri ? 0 : ntj, ti0, p.tri ? 1 : 0, K, p.kbeg, p.kend, p.kdiv};
+  const OzShape s{nti, p.tri ? (Pb < Pa ? ntj : 0) : ntj, ti0, p.tri ? 1 : 0, K, p.kbeg, p.kend, p.kdiv};
   OzTestBufs d;
   hipStream_t st = c->stream;
   OzOpnd oa, ob;
@@ -4376,11 +4483,10 @@ static int oz_test_product(gpe_ctx* c, const gpe_oz_operand& a, const gpe_oz_ope
     std::vector<int8_t> h((size_t)rb);
     HIPCHK(c, hipMemcpy(h.data(), d.res + (long long)p.res_mod * rb, (size_t)rb, hipMemcpyDeviceToHost));
     std::memset(res_out, 0, (size_t)nti * OZ_T * Pb);
-    const auto tile_of = [&](long long ti, long long tj) { return p.tri ? ti * (ti + 1) / 2 + tj : ti * ntj + tj; };
     for (const unsigned ent : list) {
       if (ent == 0xffffffffu) continue;
       const int ti = (int)(ent >> 16), tj = (int)(ent & 0xffffu);
-      const int8_t* t = h.data() + (tile_of(ti, tj) - tile_of(ti0, 0)) * (OZ_T * OZ_T);
+      const int8_t* t = h.data() + s.res_tile(ti, tj) * (OZ_T * OZ_T);
       for (int u = 0; u < OZ_T * OZ_T / 16; ++u) {
         const int wave = u >> 10, blk = (u >> 6) & 15, lane = u & 63;
         const long long gm = OZ_T * (ti - ti0) + (wave >> 1) * 128 + 32 * (blk >> 2) + (lane & 31);

@@ -186,14 +186,19 @@ struct OzGemm {
   const unsigned* list;
   int list_len;
   int K, kbeg, kend;
-  int tri, ntj;    // residue tile of (ti, tj): ti (ti + 1) / 2 + tj (tri) or ti ntj + tj
+  int tri, ntj;    // residue tile of (ti, tj): oz_res_tile
   int8_t* res;
   long long res_bytes;
   int kdiv = 1;
   int ti0 = 0;
 };
-__device__ __forceinline__ long long oz_res_tile(int tri, int ntj, int ti, int tj) {
-  return tri ? (long long)ti * (ti + 1) / 2 + tj : (long long)ti * ntj + tj;
+// residue tile of (ti, tj): ti ntj + tj, or (tri) ti (ti + 1) / 2 + tj over the lower triangle;
+// tri with ntj > 0: the lower triangle capped at ntj tile columns (tj <= min(ti, ntj - 1)), the
+// rows from ntj on ntj tiles each
+__host__ __device__ __forceinline__ long long oz_res_tile(int tri, int ntj, int ti, int tj) {
+  if (!tri) return (long long)ti * ntj + tj;
+  if (ntj > 0 && ti >= ntj) return (long long)ntj * (ntj + 1) / 2 + (long long)(ti - ntj) * ntj + tj;
+  return (long long)ti * (ti + 1) / 2 + tj;
 }
 // the k range [kb, ke) of tile (ti, tj) (above): the one statement of the rule, for k_oz_gemm
 // and for the host's tile weights and operation counts (OzShape::klen)
@@ -446,10 +451,15 @@ static __global__ void __launch_bounds__(256) k_oz_crt(OzCrt g, OzConst cst) {
   const int u = ((int)blockIdx.x & 15) * 256 + (int)threadIdx.x;
   int ti, tj;
   if (g.tri) {
-    const int ta = t + g.ti0 * (g.ti0 + 1) / 2;
-    ti = g.ti0;
-    while ((ti + 1) * (ti + 2) / 2 <= ta) ++ti;
-    tj = ta - ti * (ti + 1) / 2;
+    const int ta = t + (int)oz_res_tile(1, g.ntj, g.ti0, 0), cap = g.ntj * (g.ntj + 1) / 2;
+    if (g.ntj > 0 && ta >= cap) {   // the capped triangle's full rows (oz_res_tile)
+      ti = g.ntj + (ta - cap) / g.ntj;
+      tj = (ta - cap) % g.ntj;
+    } else {
+      ti = g.ti0;
+      while ((ti + 1) * (ti + 2) / 2 <= ta) ++ti;
+      tj = ta - ti * (ti + 1) / 2;
+    }
   } else {
     ti = g.ti0 + t / g.ntj;
     tj = t % g.ntj;
@@ -707,7 +717,7 @@ std::vector<unsigned> oz_list(int nti, int ntj, bool lower, W work, int ti0 = 0)
     for (int c0 = 0; c0 < ntj && (!lower || c0 <= r0 + OZ_BR - 1); c0 += OZ_BC) {
       Blk b{0.0, {}};
       for (int ti = r0; ti < std::min(ti0 + nti, r0 + OZ_BR); ++ti)
-        for (int tj = c0; tj < std::min(lower ? ti + 1 : ntj, c0 + OZ_BC); ++tj) {
+        for (int tj = c0; tj < std::min(std::min(lower ? ti + 1 : ntj, ntj), c0 + OZ_BC); ++tj) {
           b.t.push_back(((unsigned)ti << 16) | (unsigned)tj);
           b.w += work(ti, tj);
         }
@@ -773,11 +783,15 @@ inline void oz_operand_packed(hipStream_t st, const OzConst& k, const double* X,
 }
 
 // A product's shape, stated once: tile rows [ti0, ti0 + nti) against ntj tile columns, or (tri)
-// against the lower triangle's tj <= ti; K, kbeg, kend, kdiv as OzGemm's
+// against the lower triangle's tj <= ti, whole (ntj 0) or capped at ntj tile columns (a
+// trapezoid: tj <= min(ti, ntj - 1)); K, kbeg, kend, kdiv as OzGemm's
 struct OzShape {
   int nti, ntj, ti0, tri, K, kbeg, kend, kdiv;
   static OzShape lower(int nti, int ti0, int K, int kbeg, int kdiv = 1) { return {nti, 0, ti0, 1, K, kbeg, 0, kdiv}; }
+  static OzShape lower_capped(int nti, int cap, int K) { return {nti, cap < nti ? cap : 0, 0, 1, K, 0, 0, 1}; }
   static OzShape rect(int nti, int ntj, int K, int kbeg, int kend) { return {nti, ntj, 0, 0, K, kbeg, kend, 1}; }
+  // tile columns of tile row ti
+  int row_tiles(int ti) const { return tri ? (ntj > 0 ? std::min(ti + 1, ntj) : ti + 1) : ntj; }
   // length of tile (ti, tj)'s k range: its weight in the list, its share of the operations
   int klen(int ti, int tj) const {
     int kb, ke;
@@ -785,19 +799,18 @@ struct OzShape {
     return std::max(0, ke - kb);
   }
   std::vector<unsigned> list() const {
-    return oz_list(nti, tri ? ti0 + nti : ntj, tri != 0, [&](int ti, int tj) { return (double)klen(ti, tj); }, ti0);
+    return oz_list(nti, tri && ntj == 0 ? ti0 + nti : ntj, tri != 0, [&](int ti, int tj) { return (double)klen(ti, tj); }, ti0);
   }
+  // residue tile of (ti, tj) less that of the shape's first (k_oz_gemm's and k_oz_crt's index)
+  long long res_tile(int ti, int tj) const { return oz_res_tile(tri, ntj, ti, tj) - oz_res_tile(tri, ntj, ti0, 0); }
   // residue tiles (tri: the lower tiles of the rows up to ti0 + nti less those above ti0)
-  long long tiles() const {
-    const long long t1 = ti0 + nti;
-    return tri ? t1 * (t1 + 1) / 2 - (long long)ti0 * (ti0 + 1) / 2 : (long long)nti * ntj;
-  }
+  long long tiles() const { return tri ? oz_res_tile(1, ntj, ti0 + nti, 0) - oz_res_tile(1, ntj, ti0, 0) : (long long)nti * ntj; }
   long long res_bytes() const { return tiles() * OZ_T * OZ_T; }   // per modulus
   // int8 operations with N moduli
   double ops(int N) const {
     double s = 0.0;
     for (int ti = ti0; ti < ti0 + nti; ++ti)
-      for (int tj = 0; tj < (tri ? ti + 1 : ntj); ++tj) s += klen(ti, tj);
+      for (int tj = 0; tj < row_tiles(ti); ++tj) s += klen(ti, tj);
     return 2.0 * OZ_T * OZ_T * s * N;
   }
 };
@@ -838,7 +851,7 @@ struct OzProduct {
 inline hipError_t oz_product_launch(hipStream_t st, const OzConst& k, const OzProduct& p, hipEvent_t e0 = nullptr,
                                     hipEvent_t e1 = nullptr) {
   const OzShape& s = p.s;
-  const int ntj = s.tri ? 0 : s.ntj;
+  const int ntj = s.ntj;   // (tri: 0, or the cap)
   const OzGemm g{p.a, p.b, p.list, p.list_len, s.K, s.kbeg, s.kend, s.tri, ntj, p.res, p.res_bytes, s.kdiv, s.ti0};
   const OzOut& o = p.out;
   const OzCrt r{p.res, p.res_bytes, s.tri, ntj, o.exr, o.exc, o.C, o.ldc, o.rows, o.cols, o.lower128, o.alpha, s.ti0, o.acc};
@@ -914,6 +927,28 @@ inline OzTriPair oz_tri_pair_plan(int t0, int h, int t1, int N, std::vector<unsi
   q.lb_len = (int)lb.size();
   lists.insert(lists.end(), lb.begin(), lb.end());
   return q;
+}
+
+// ---- the split Cholesky's first phase split once more at tile column q = h / 2 (q even): the
+// trapezoid {rows [q, NB), columns [q, h), column <= row} of A takes the update by columns
+// [0, q) as one product.  The one operand, used on both sides, is the rows [q, NB) of L's
+// columns [0, q) (Rb rows padded to Pb, every sum K = 128 q long; b's rows are a's first
+// 128 (h - q)); the shape is the lower triangle capped at (h - q) / 2 tile columns.
+struct OzCholNest {
+  int q, h, NB, Rb, Pb, K, cols;
+  OzShape shape() const { return OzShape::lower_capped(Pb / OZ_T, (h - q) / 2, K); }
+  OzSrc src(const double* Lq0, long long ld) const { return {Lq0, ld, Rb, K, 0, true}; }
+  size_t planes_bytes(int N) const { return (size_t)N * Pb * K; }
+  size_t resid_bytes(int N) const { return (size_t)N * shape().res_bytes(); }
+};
+inline OzCholNest oz_chol_nest_plan(int q, int h, int NB) {
+  OzCholNest n;
+  n.q = q; n.h = h; n.NB = NB;
+  n.Rb = (NB - q) * TILE;
+  n.Pb = (n.Rb + OZ_T - 1) / OZ_T * OZ_T;
+  n.K = q * TILE;
+  n.cols = (h - q) * TILE;
+  return n;
 }
 
 // both products of the pair on stream st (X blocks and L21 with leading dimension ld; T:

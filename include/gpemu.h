@@ -339,8 +339,9 @@ int gpe_test_gemm(gpe_ctx* ctx, int32_t trans_a, int32_t trans_b, int64_t M, int
  * Rectangular form (packed 0): a and b (b NULL: B is A, one set of planes and one exponent
  * array) and the product's parameters, passed on as they are to OzGemm / OzCrt: K (a
  * multiple of 64 in [64, 2^17 - 128], >= both Kv), kbeg 0 to 3, kend 0 / 1, kdiv >= 1,
- * ti0 (first tile row: the product covers tile rows [ti0, Pa / 256)), tri (then Pb >= Pa and
- * only tiles tj <= ti), lower128, alpha, acc, nmod in [6, 16].  C is column-major, c_len
+ * ti0 (first tile row: the product covers tile rows [ti0, Pa / 256)), tri (only tiles tj <= ti; with
+ * Pb < Pa, which needs ti0 = 0, the triangle capped at B's Pb / 256 tile columns: the nested
+ * split Cholesky's trapezoid), lower128, alpha, acc, nmod in [6, 16].  C is column-major, c_len
  * doubles, read first and written back whole: entry (i, j) of the product, i < rows <= Pa,
  * j < cols <= Pb, goes to C[i - 256 ti0 + j ldc]; nothing else changes.
  * Packed form (packed 1; the A^-1 = X^T X of the objective's gradient): a describes X, R x R
