@@ -4510,6 +4510,66 @@ int gpe_test_oz_product(gpe_ctx* c, const gpe_oz_operand* a, const gpe_oz_operan
   return rc;
 }
 
+// ---- gpe_test_oz_planes: one operand's exponents and int8 planes, on buffers of its own
+static int oz_test_planes(gpe_ctx* c, const gpe_oz_operand& a, int packed, int K, int nmod, int32_t* ex_out, int8_t* planes_out) {
+  const auto bad = [&](const char* what) { return fail(c, GPE_ERR_ARG, std::string("gpe_test_oz_planes: ") + what); };
+  if (nmod < 6 || nmod > OZ_MAXMOD) return bad("nmod outside [6, 16]");
+  if (a.R < 1 || a.R > (1 << 20)) return bad("bad operand rows");
+  if (!ex_out || !planes_out) return bad("NULL output");
+  const int P = (a.R + OZ_T - 1) / OZ_T * OZ_T;
+  if (packed) {
+    if (a.R % TILE || (a.offset & 1) || (a.ld & 1) || a.ld < a.R || !oz_test_extent(a, 1, 1) ||
+        (long long)(a.R - 1) * a.ld + a.R > a.len - a.offset)
+      return bad("packed: X is R x R, R a multiple of 128, ld >= R and offset even, inside src");
+    K = P;
+  } else {
+    if (K < OZ_SK || K % OZ_SK || K > OZ_MAX_K) return bad("K is not a multiple of 64 in [64, 2^17 - 128]");
+    if (a.mask < 0 || a.mask > 2 || a.Kv > K || !oz_test_extent(a, a.R, a.Kv)) return bad("operand outside its source");
+  }
+  const OzConst k = oz_consts(nmod, K);
+  OzTestBufs d;
+  if (packed) {
+    const long long pb = oz_plane_bytes(P);
+    CHK(dalloc(c, &d.sa, (size_t)a.len));
+    CHK(dalloc(c, &d.exa, (size_t)P));
+    CHK(dalloc(c, &d.pa, (size_t)nmod * pb));
+    HIPCHK(c, hipMemcpy(d.sa, a.src, (size_t)a.len * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemsetAsync(d.pa, 0x55, (size_t)nmod * pb, c->stream));   // (every byte is to be written)
+    oz_operand_packed(c->stream, k, d.sa + a.offset, (long long)a.ld, a.R, P, d.exa, d.pa);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    std::vector<int8_t> h((size_t)nmod * pb);
+    HIPCHK(c, hipMemcpy(h.data(), d.pa, h.size(), hipMemcpyDeviceToHost));
+    std::memset(planes_out, 0, (size_t)nmod * P * P);
+    for (int l = 0; l < nmod; ++l)
+      for (int j = 0; j < P; ++j) {   // column j of X: rows 256 (j / 256) .. P of its panel
+        const int r0 = j / OZ_T * OZ_T;
+        std::memcpy(planes_out + ((size_t)l * P + j) * P + r0,
+                    h.data() + (size_t)l * pb + oz_panel_off(j / OZ_T, P) + (long long)(j - r0) * (P - r0), (size_t)(P - r0));
+      }
+  } else {
+    CHK(dalloc(c, &d.sa, (size_t)a.len));
+    CHK(dalloc(c, &d.exa, (size_t)P));
+    CHK(dalloc(c, &d.pa, (size_t)nmod * P * K));
+    HIPCHK(c, hipMemcpy(d.sa, a.src, (size_t)a.len * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemsetAsync(d.pa, 0x55, (size_t)nmod * P * K, c->stream));
+    oz_operand(c->stream, k, OzSrc{d.sa + a.offset, (long long)a.ld, a.R, a.Kv, a.mask, a.trans != 0}, P, K, d.exa, d.pa);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(planes_out, d.pa, (size_t)nmod * P * K, hipMemcpyDeviceToHost));
+  }
+  HIPCHK(c, hipMemcpy(ex_out, d.exa, (size_t)P * sizeof(int), hipMemcpyDeviceToHost));
+  return GPE_OK;
+}
+
+int gpe_test_oz_planes(gpe_ctx* c, const gpe_oz_operand* a, int32_t packed, int32_t K, int32_t nmod, int32_t* ex_out,
+                       int8_t* planes_out) {
+  if (!c) return GPE_ERR_ARG;
+  if (!a) return fail(c, GPE_ERR_ARG, "gpe_test_oz_planes: NULL operand");
+  HIPCHK(c, hipSetDevice(c->device));
+  return oz_test_planes(c, *a, packed, K, nmod, ex_out, planes_out);
+}
+
 // ---- gpe_test_gemm_group: one k_gemm launch on a group of problems, on buffers of its own
 struct GemmGroupBufs {   // (freed, and the context's descriptor / list arrays put back, on every way out)
   gpe_ctx* c;

@@ -50,6 +50,8 @@ struct OzConst {
   int m[OZ_MAXMOD];        // modulus
   int c16[OZ_MAXMOD];      // 2^16 mod m
   float inv[OZ_MAXMOD];    // 1 / m
+  int wlo[OZ_MAXMOD];      // centred 256^i mod m as int8, i = 0 .. 3 from the low byte (oz_residues)
+  int whi[OZ_MAXMOD];      // i = 4 .. 6, the top byte 0
   double rhi[OZ_MAXMOD];   // y / m rounded to a multiple of 2^-41 (y = (M / m)^-1 mod m)
   double rlo[OZ_MAXMOD];   // y / m - rhi
   double Md;               // M = prod m (rounded)
@@ -77,6 +79,90 @@ __host__ __device__ __forceinline__ long long oz_panel_off(int cb, int np2) {
 }
 __host__ __device__ __forceinline__ long long oz_plane_bytes(int np2) { return oz_panel_off(np2 / OZ_T, np2); }
 
+// ---- an operand entry -> its residue bytes (k_oz_split, k_oz_split_rect; compiled for the
+// host too: tests/host/oz_residue_check.cpp holds it against 128-bit integers).
+// x = rint(ldexp(., e)) is an integer-valued double, |x| <= 2^53.  Once per entry:
+//   X = (long long)x = sum_i d_i 256^i, seven balanced digits d_i in [-128, 127]: byte i of
+//       (X + c) ^ c, c = 0x0080808080808080 (one addition puts 128 on every digit and carries;
+//       the eighth digit would be 0 for -c <= X < 2^56 - c).
+// Per modulus:
+//   t = sum_i d_i w_i, w_i the centred 256^i mod m (OzConst::wlo, whi; (1, 0, ..) for 256):
+//       t = X (mod m), |t| <= 7 128 128 < 2^17, two 4 x int8 dot products;
+//   r = t - m rint(t / m), the tile end's reduction (oz_store_residues: q from fl(t (1 / m)) +
+//       1.5 2^23, two roundings, then a 24-bit multiply-add; only the low byte is kept).
+//       |fl(t (1 / m)) - t / m| <= 2^-23 |t| / m < 1e-4, and for odd m t / m is at least
+//       1 / (2 m) > 1.9e-3 from a tie: q is exact and r the one centred residue,
+//       |r| <= (m - 1) / 2.  For m = 256 (1 / m exact) q may go either way at a tie, and
+//       r = t (mod 256) regardless: the low byte of t.
+struct OzDigits {
+  int lo, hi;   // d_0 .. d_3 and d_4 .. d_6 (top byte 0), as packed int8
+};
+__host__ __device__ __forceinline__ OzDigits oz_digits(double x) {
+  const unsigned long long c = 0x0080808080808080ull;
+  const unsigned long long b = ((unsigned long long)(long long)x + c) ^ c;
+  return OzDigits{(int)(unsigned)b, (int)(unsigned)(b >> 32)};
+}
+// c + sum of the four int8 products of a's and b's bytes
+__host__ __device__ __forceinline__ int oz_dot4(int a, int b, int c) {
+#if __HIP_DEVICE_COMPILE__
+  return __builtin_amdgcn_sdot4(a, b, c, false);
+#else
+  for (int i = 0; i < 4; ++i) c += (int)(int8_t)((unsigned)a >> (8 * i)) * (int)(int8_t)((unsigned)b >> (8 * i));
+  return c;
+#endif
+}
+// the product of the low 24 bits (signed) of a and b, its low 32 bits
+__host__ __device__ __forceinline__ int oz_mul24(int a, int b) {
+#if __HIP_DEVICE_COMPILE__
+  return __mul24(a, b);
+#else
+  const int a24 = (int)((unsigned)a << 8) >> 8, b24 = (int)((unsigned)b << 8) >> 8;
+  return (int)((unsigned)a24 * (unsigned)b24);
+#endif
+}
+__host__ __device__ __forceinline__ int oz_float_bits(float f) {
+#if __HIP_DEVICE_COMPILE__
+  return __float_as_int(f);
+#else
+  int i;
+  std::memcpy(&i, &f, sizeof i);
+  return i;
+#endif
+}
+__host__ __device__ __forceinline__ int oz_digit_sum(OzDigits d, int wlo, int whi) {   // t
+  return oz_dot4(d.lo, wlo, oz_dot4(d.hi, whi, 0));
+}
+// the centred residue of t modulo m = -nm in the low byte (the rest is not the residue's)
+__host__ __device__ __forceinline__ unsigned oz_reduce(int t, float inv, int nm) {
+#pragma clang fp contract(off)
+  const float qf = (float)t * inv + 12582912.0f;
+  return (unsigned)(oz_mul24(oz_float_bits(qf), nm) + t);
+}
+// the low bytes of v0 .. v3, lowest first
+__host__ __device__ __forceinline__ unsigned oz_pack4(unsigned v0, unsigned v1, unsigned v2, unsigned v3) {
+#if __HIP_DEVICE_COMPILE__
+  return __builtin_amdgcn_perm(__builtin_amdgcn_perm(v3, v2, 0x0c0c0400u), __builtin_amdgcn_perm(v1, v0, 0x0c0c0400u),
+                               0x05040100u);
+#else
+  return (v0 & 0xffu) | (v1 & 0xffu) << 8 | (v2 & 0xffu) << 16 | v3 << 24;
+#endif
+}
+// the residues of x modulo cst's moduli, one int8 each
+__host__ __device__ inline void oz_residues(double x, const OzConst& cst, int8_t* out) {
+  const OzDigits d = oz_digits(x);
+  for (int l = 0; l < cst.nmod; ++l)
+    out[l] = (int8_t)(oz_reduce(oz_digit_sum(d, cst.wlo[l], cst.whi[l]), cst.inv[l], -cst.m[l]) & 0xffu);
+}
+// the same for 8 entries (their digits) and modulus number l: two words, entry 0 in the lowest byte
+__host__ __device__ __forceinline__ uint2 oz_residues8(const OzDigits (&d)[8], const OzConst& cst, int l) {
+  const int wlo = cst.wlo[l], whi = cst.whi[l], nm = -cst.m[l];
+  const float inv = cst.inv[l];
+  unsigned v[8];
+#pragma unroll
+  for (int u = 0; u < 8; ++u) v[u] = oz_reduce(oz_digit_sum(d[u], wlo, whi), inv, nm);
+  return make_uint2(oz_pack4(v[0], v[1], v[2], v[3]), oz_pack4(v[4], v[5], v[6], v[7]));
+}
+
 // e_j for every column j < np2 (one wave per column, rows k >= j; columns past np: 0)
 static __global__ void __launch_bounds__(256) k_oz_colexp(const double* __restrict__ X, long long ldx, int np,
                                                           int np2, int beta, int* __restrict__ ex) {
@@ -91,7 +177,8 @@ static __global__ void __launch_bounds__(256) k_oz_colexp(const double* __restri
 
 // X -> the N int8 planes: thread = 8 consecutive rows of one column (a wave reads 4 KB of
 // the column and writes 512 contiguous bytes per plane); entries above the diagonal (and past
-// np) are zero.  Precondition: X is 16-byte aligned and ldx even (every column starts on a
+// np) are zero, and a thread whose 8 rows are all such writes its zeros and nothing else; the
+// residues by oz_residues8.  Precondition: X is 16-byte aligned and ldx even (every column starts on a
 // 16-byte boundary: the double2 loads below; the callers' ldx is n_pad, a multiple of 128).
 // Entries above the diagonal are never read.
 constexpr int OZ_SPLIT_ROWS = 8;
@@ -103,8 +190,14 @@ static __global__ void __launch_bounds__(256) k_oz_split(const double* __restric
   const int k0 = r0 + OZ_SPLIT_ROWS * ((int)blockIdx.y * 256 + (int)threadIdx.x);
   if (k0 >= np2) return;
   const int e = ex[j];
+  const long long ld = np2 - r0;
+  int8_t* dst = planes + oz_panel_off(cb, np2) + (long long)(j - r0) * ld + (k0 - r0);
+  if (j >= np || k0 >= np || k0 + OZ_SPLIT_ROWS <= j || e == OZ_EX_NAN) {   // all 8 zero: the stores alone
+    for (int l = 0; l < cst.nmod; ++l) *reinterpret_cast<uint2*>(dst + (long long)l * plane_bytes) = make_uint2(0u, 0u);
+    return;
+  }
   double xs[OZ_SPLIT_ROWS];
-  if (j < np && k0 + OZ_SPLIT_ROWS <= np && k0 >= j) {   // (16-byte loads: k0 is a multiple of 8)
+  if (k0 + OZ_SPLIT_ROWS <= np && k0 >= j) {   // (16-byte loads: k0 is a multiple of 8)
 #pragma unroll
     for (int u = 0; u < OZ_SPLIT_ROWS; u += 2) {
       const double2 v = *reinterpret_cast<const double2*>(X + k0 + u + (long long)j * ldx);
@@ -115,27 +208,13 @@ static __global__ void __launch_bounds__(256) k_oz_split(const double* __restric
 #pragma unroll
     for (int u = 0; u < OZ_SPLIT_ROWS; ++u) {
       const int k = k0 + u;
-      xs[u] = (k >= j && k < np && j < np) ? X[k + (long long)j * ldx] : 0.0;
+      xs[u] = (k >= j && k < np) ? X[k + (long long)j * ldx] : 0.0;
     }
   }
+  OzDigits d[OZ_SPLIT_ROWS];
 #pragma unroll
-  for (int u = 0; u < OZ_SPLIT_ROWS; ++u) xs[u] = e == OZ_EX_NAN ? 0.0 : rint(ldexp(xs[u], e));   // |.| <= 2^beta
-  const long long ld = np2 - r0;
-  int8_t* dst = planes + oz_panel_off(cb, np2) + (long long)(j - r0) * ld + (k0 - r0);
-  for (int l = 0; l < cst.nmod; ++l) {
-    const double m = (double)cst.m[l], im = 1.0 / m;
-    unsigned w[2] = {0u, 0u};
-#pragma unroll
-    for (int u = 0; u < OZ_SPLIT_ROWS; ++u) {
-      // centred residue: x - m rint(x / m) is exact (|x| <= 2^53, the product q m an integer
-      // below 2^53), |.| <= m / 2 + 1; the m = 256 one wraps into int8 congruently
-      const double q = rint(xs[u] * im);
-      int r = (int)fma(-q, m, xs[u]);
-      r = r > 127 ? r - cst.m[l] : (r < -128 ? r + cst.m[l] : r);
-      w[u >> 2] |= ((unsigned)r & 0xffu) << (8 * (u & 3));
-    }
-    *reinterpret_cast<uint2*>(dst + (long long)l * plane_bytes) = make_uint2(w[0], w[1]);
-  }
+  for (int u = 0; u < OZ_SPLIT_ROWS; ++u) d[u] = oz_digits(rint(ldexp(xs[u], e)));   // |.| <= 2^beta
+  for (int l = 0; l < cst.nmod; ++l) *reinterpret_cast<uint2*>(dst + (long long)l * plane_bytes) = oz_residues8(d, cst, l);
 }
 
 __device__ __forceinline__ void oz_glds16(const int8_t* src, int8_t* dst) {
@@ -446,7 +525,15 @@ struct OzCrt {
   int ti0 = 0;
   int acc = 0;
 };
+// A thread's loads -- its 16 residue bytes of every modulus (16 bytes each), its row exponent and
+// its 16 column exponents (columns gn0 + 8 q + {0 .. 3}: four 16-byte loads) -- are all issued
+// before the first is used, so a wave has nmod + 5 loads (nmod KB of residues) in flight, not
+// one: the sums wait for memory once.  NM: the number of moduli at compile time (16, the default's), or 0: cst.nmod
+// (6 .. 15), the same code with the moduli past nmod skipped.  The sums themselves run over
+// l = 0 .. nmod - 1 in that order for every entry.
+template <int NM>
 static __global__ void __launch_bounds__(256) k_oz_crt(OzCrt g, OzConst cst) {
+  const int nmod = NM ? NM : cst.nmod;
   const int t = (int)blockIdx.x >> 4;
   const int u = ((int)blockIdx.x & 15) * 256 + (int)threadIdx.x;
   int ti, tj;
@@ -469,28 +556,45 @@ static __global__ void __launch_bounds__(256) k_oz_crt(OzCrt g, OzConst cst) {
   const int gm = OZ_T * ti + (wave >> 1) * 128 + 32 * i + (lane & 31);
   const int gn0 = OZ_T * tj + (wave & 1) * 128 + 32 * j + 4 * (lane >> 5);
   if (gm >= g.rows || gn0 >= g.cols) return;
+  const int8_t* src = g.res + (long long)t * (OZ_T * OZ_T) + (long long)u * 16;
+  oz_v4i w[OZ_MAXMOD];
+#pragma unroll
+  for (int l = 0; l < OZ_MAXMOD; ++l)
+    if (l < nmod) w[l] = *reinterpret_cast<const oz_v4i*>(src + (long long)l * g.res_bytes);
+  const int em = g.exr[gm];
+  oz_v4i ec[4];   // (gn0 is a multiple of 4; the 16-byte load only where all four columns exist and exc allows it)
+  const bool ec16 = (reinterpret_cast<uintptr_t>(g.exc) & 15) == 0;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int gn = gn0 + 8 * q;
+    if (ec16 && gn + 3 < g.cols) {
+      ec[q] = *reinterpret_cast<const oz_v4i*>(g.exc + gn);
+    } else {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) ec[q][i] = gn + i < g.cols ? g.exc[gn + i] : 0;
+    }
+  }
   double shi[16], slo[16];
 #pragma unroll
   for (int r = 0; r < 16; ++r) shi[r] = slo[r] = 0.0;
-  const int8_t* src = g.res + (long long)t * (OZ_T * OZ_T) + (long long)u * 16;
-  for (int l = 0; l < cst.nmod; ++l) {
-    const oz_v4i w = *reinterpret_cast<const oz_v4i*>(src + (long long)l * g.res_bytes);
-    const double rh = cst.rhi[l], rl = cst.rlo[l];
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const double cv = (double)(int)(int8_t)((unsigned)w[r >> 2] >> (8 * (r & 3)));
-      shi[r] = fma(cv, rh, shi[r]);   // exact: multiples of 2^-41 below 2^11
-      slo[r] = fma(cv, rl, slo[r]);
+  for (int l = 0; l < OZ_MAXMOD; ++l)
+    if (l < nmod) {
+      const double rh = cst.rhi[l], rl = cst.rlo[l];
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const double cv = (double)(int)(int8_t)((unsigned)w[l][r >> 2] >> (8 * (r & 3)));
+        shi[r] = fma(cv, rh, shi[r]);   // exact: multiples of 2^-41 below 2^11
+        slo[r] = fma(cv, rl, slo[r]);
+      }
     }
-  }
-  const int em = g.exr[gm];
   const double sc = g.alpha * cst.Md;
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
     const int gn = gn0 + (r & 3) + 8 * (r >> 2);
     if (gn >= g.cols || (g.lower128 && (gm >> 7) < (gn >> 7))) continue;
     const double v = (shi[r] - rint(shi[r])) + slo[r];   // C' / M, centred
-    const int en = g.exc[gn];
+    const int en = ec[r >> 2][r & 3];
     double* dst = g.C + (gm - OZ_T * g.ti0 + (long long)gn * g.ldc);
     const double s = ldexp(sc, -(em + en));
     if (em == OZ_EX_NAN || en == OZ_EX_NAN) *dst = __builtin_nan("");
@@ -547,22 +651,15 @@ static __global__ void __launch_bounds__(256) k_oz_il_to_ex(int* __restrict__ ex
   if (r < Rp) ex[r] = ex[r] >= OZ_IL_BAD ? OZ_EX_NAN : (ex[r] > 0 ? (beta - 1) - (ex[r] - 2048) : 0);
 }
 
-// x (an integer-valued double, |x| <= 2^53) -> its centred residue mod m as one byte
-__device__ __forceinline__ unsigned oz_res8(double x, double m, double im, int mi) {
-  // x - m rint(x / m) is exact (the product q m an integer below 2^53), |.| <= m / 2 + 1;
-  // the m = 256 one wraps into int8 congruently
-  const double q = rint(x * im);
-  int r = (int)fma(-q, m, x);
-  r = r > 127 ? r - mi : (r < -128 ? r + mi : r);
-  return (unsigned)r & 0xffu;
-}
-
 // op -> the N int8 planes, rectangular (row r at r ldp + k, k < Kp; zero past R / Kv and
-// masked).  TRANS false: thread = 8 consecutive k of one row (contiguous in src: four 16-byte
-// loads when the 8 are in range and on one side of the mask's diagonal).  TRANS true:
-// workgroup = 64 rows x 64 k, thread = 2 adjacent rows x 8 consecutive k (each load 16 bytes,
-// the lanes along r); each plane's 64 x 64 bytes go through LDS so the stores run along k
-// (4 threads per row, 16 bytes each).
+// masked), the residues by oz_residues8.  TRANS false: thread = 8 consecutive k of one row
+// (contiguous in src: four 16-byte loads when the 8 are in range and on one side of the
+// mask's diagonal); a thread whose 8 are all dropped writes its zeros and nothing else.
+// TRANS true: workgroup = 64 rows x 64 k, thread = 2 adjacent rows x 8 consecutive k (each
+// load 16 bytes, the lanes along r); the planes' 64 x 64 bytes go through LDS four planes a
+// round (two barriers per round) so the stores run along k (4 threads per row, 16 bytes
+// each); a block wholly dropped writes zeros without the LDS rounds.  The zeros are stored
+// because a product's k range may cover them.
 template <bool TRANS>
 static __global__ void __launch_bounds__(256) k_oz_split_rect(const double* __restrict__ src, long long ld, int R,
                                                               int Kv, int mask, const int* __restrict__ ex,
@@ -573,12 +670,17 @@ static __global__ void __launch_bounds__(256) k_oz_split_rect(const double* __re
     const int k0 = ((int)blockIdx.y * 256 + (int)threadIdx.x) * 8;
     if (k0 >= Kp) return;
     const int e = ex[r];
-    double xs[8];
     const double* p = src + k0 + (long long)r * ld;
     // the mask's diagonal k = r: all 8 kept (1), all dropped (0), or mixed (2)
     const int side = mask == 1 ? (k0 >= r ? 1 : (k0 + 7 < r ? 0 : 2))
                    : (mask == 2 ? (k0 + 7 <= r ? 1 : (k0 > r ? 0 : 2)) : 1);
-    if (r < R && k0 + 8 <= Kv && side == 1 && ((reinterpret_cast<uintptr_t>(p) & 15) == 0)) {
+    int8_t* dst = planes + (long long)r * ldp + k0;
+    if (side == 0 || r >= R || k0 >= Kv || e == OZ_EX_NAN) {   // all 8 zero: the stores alone
+      for (int l = 0; l < cst.nmod; ++l) *reinterpret_cast<uint2*>(dst + (long long)l * plane_bytes) = make_uint2(0u, 0u);
+      return;
+    }
+    double xs[8];
+    if (k0 + 8 <= Kv && side == 1 && ((reinterpret_cast<uintptr_t>(p) & 15) == 0)) {
 #pragma unroll
       for (int u = 0; u < 8; u += 2) {
         const double2 v = *reinterpret_cast<const double2*>(p + u);
@@ -589,25 +691,26 @@ static __global__ void __launch_bounds__(256) k_oz_split_rect(const double* __re
 #pragma unroll
       for (int u = 0; u < 8; ++u) {
         const int k = k0 + u;
-        xs[u] = (side != 0 && r < R && k < Kv && oz_keep(mask, r, k)) ? p[u] : 0.0;
+        xs[u] = (k < Kv && oz_keep(mask, r, k)) ? p[u] : 0.0;
       }
     }
+    OzDigits d[8];
 #pragma unroll
-    for (int u = 0; u < 8; ++u) xs[u] = e == OZ_EX_NAN ? 0.0 : rint(ldexp(xs[u], e));
-    int8_t* dst = planes + (long long)r * ldp + k0;
-    for (int l = 0; l < cst.nmod; ++l) {
-      const double m = (double)cst.m[l], im = 1.0 / m;
-      unsigned w0 = 0u, w1 = 0u;
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        w0 |= oz_res8(xs[u], m, im, cst.m[l]) << (8 * u);
-        w1 |= oz_res8(xs[u + 4], m, im, cst.m[l]) << (8 * u);
-      }
-      *reinterpret_cast<uint2*>(dst + (long long)l * plane_bytes) = make_uint2(w0, w1);
-    }
+    for (int u = 0; u < 8; ++u) d[u] = oz_digits(rint(ldexp(xs[u], e)));
+    for (int l = 0; l < cst.nmod; ++l) *reinterpret_cast<uint2*>(dst + (long long)l * plane_bytes) = oz_residues8(d, cst, l);
   } else {
-    __shared__ __attribute__((aligned(16))) unsigned tr[64 * 20];   // [row][16 words + 4 pad]
+    constexpr int PL = 4;   // planes per LDS round
+    __shared__ __attribute__((aligned(16))) unsigned tr[PL][64 * 20];   // [plane][row][16 words + 4 pad]
     const int lane = threadIdx.x & 63, rp = lane & 31, kg = (int)threadIdx.x >> 5;
+    const int wr = (int)threadIdx.x >> 2, wp = (int)threadIdx.x & 3;   // row wr, piece wp of the block
+    int8_t* dst = planes + ((long long)blockIdx.x * 64 + wr) * ldp + (long long)blockIdx.y * 64 + 16 * wp;
+    {   // a block wholly past R / Kv or on the mask's dropped side (the same for the whole workgroup): zeros alone
+      const int rb = (int)blockIdx.x * 64, kb = (int)blockIdx.y * 64;
+      if (rb >= R || kb >= Kv || (mask == 1 && kb + 63 < rb) || (mask == 2 && kb > rb + 63)) {
+        for (int l = 0; l < cst.nmod; ++l) *reinterpret_cast<uint4*>(dst + (long long)l * plane_bytes) = make_uint4(0u, 0u, 0u, 0u);
+        return;
+      }
+    }
     const int r = (int)blockIdx.x * 64 + 2 * rp;          // rows r, r + 1
     const int k0 = (int)blockIdx.y * 64 + 8 * kg;         // k0 .. k0 + 7
     const int e0 = ex[r], e1 = ex[r + 1];
@@ -631,28 +734,26 @@ static __global__ void __launch_bounds__(256) k_oz_split_rect(const double* __re
       x0[u] = oz_keep(mask, r, k) ? a : 0.0;
       x1[u] = oz_keep(mask, r + 1, k) ? b : 0.0;
     }
+    OzDigits d0[8], d1[8];
 #pragma unroll
     for (int u = 0; u < 8; ++u) {
-      x0[u] = e0 == OZ_EX_NAN ? 0.0 : rint(ldexp(x0[u], e0));
-      x1[u] = e1 == OZ_EX_NAN ? 0.0 : rint(ldexp(x1[u], e1));
+      d0[u] = oz_digits(e0 == OZ_EX_NAN ? 0.0 : rint(ldexp(x0[u], e0)));
+      d1[u] = oz_digits(e1 == OZ_EX_NAN ? 0.0 : rint(ldexp(x1[u], e1)));
     }
-    const int wr = (int)threadIdx.x >> 2, wp = (int)threadIdx.x & 3;   // row wr, piece wp of the block
-    int8_t* dst = planes + ((long long)blockIdx.x * 64 + wr) * ldp + (long long)blockIdx.y * 64 + 16 * wp;
-    for (int l = 0; l < cst.nmod; ++l) {
-      const double m = (double)cst.m[l], im = 1.0 / m;
-      unsigned a0 = 0u, a1 = 0u, b0 = 0u, b1 = 0u;
+    for (int l0 = 0; l0 < cst.nmod; l0 += PL) {
+      if (l0 > 0) __syncthreads();   // (the previous round's reads done)
 #pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        a0 |= oz_res8(x0[u], m, im, cst.m[l]) << (8 * u);
-        a1 |= oz_res8(x0[u + 4], m, im, cst.m[l]) << (8 * u);
-        b0 |= oz_res8(x1[u], m, im, cst.m[l]) << (8 * u);
-        b1 |= oz_res8(x1[u + 4], m, im, cst.m[l]) << (8 * u);
-      }
-      if (l > 0) __syncthreads();   // (the previous plane's reads done)
-      *reinterpret_cast<uint2*>(tr + (2 * rp) * 20 + 2 * kg) = make_uint2(a0, a1);
-      *reinterpret_cast<uint2*>(tr + (2 * rp + 1) * 20 + 2 * kg) = make_uint2(b0, b1);
+      for (int q = 0; q < PL; ++q)
+        if (l0 + q < cst.nmod) {
+          *reinterpret_cast<uint2*>(tr[q] + (2 * rp) * 20 + 2 * kg) = oz_residues8(d0, cst, l0 + q);
+          *reinterpret_cast<uint2*>(tr[q] + (2 * rp + 1) * 20 + 2 * kg) = oz_residues8(d1, cst, l0 + q);
+        }
       __syncthreads();
-      *reinterpret_cast<uint4*>(dst + (long long)l * plane_bytes) = *reinterpret_cast<const uint4*>(tr + wr * 20 + 4 * wp);
+#pragma unroll
+      for (int q = 0; q < PL; ++q)
+        if (l0 + q < cst.nmod)
+          *reinterpret_cast<uint4*>(dst + (long long)(l0 + q) * plane_bytes) =
+              *reinterpret_cast<const uint4*>(tr[q] + wr * 20 + 4 * wp);
     }
   }
 }
@@ -677,6 +778,13 @@ inline OzConst oz_consts(int nmod, int np2) {
     k.m[l] = m;
     k.c16[l] = 65536 % m;
     k.inv[l] = 1.0f / (float)m;
+    unsigned w[2] = {0u, 0u};   // centred 256^i mod m, i = 0 .. 6, one int8 each
+    for (int i = 0, p = 1; i < 7; ++i, p = (p * 256) % m) {
+      const int wc = p > m / 2 ? p - m : p;   // (m = 256: 1, 0, ..; odd m: |wc| <= 126)
+      w[i >> 2] |= ((unsigned)wc & 0xffu) << (8 * (i & 3));
+    }
+    k.wlo[l] = (int)w[0];
+    k.whi[l] = (int)w[1];
     long long Mm = 1;   // (M / m) mod m
     for (int j = 0; j < nmod; ++j)
       if (j != l) Mm = (Mm * (mods[j] % m)) % m;
@@ -859,7 +967,8 @@ inline hipError_t oz_product_launch(hipStream_t st, const OzConst& k, const OzPr
   if (e0 && (e = hipEventRecord(e0, st)) != hipSuccess) return e;
   hipLaunchKernelGGL(k_oz_gemm, dim3((unsigned)(k.nmod * g.list_len)), dim3(256), OZ_LDS, st, g, k);
   if (e1 && (e = hipEventRecord(e1, st)) != hipSuccess) return e;
-  hipLaunchKernelGGL(k_oz_crt, dim3((unsigned)(s.tiles() * 16)), dim3(256), 0, st, r, k);
+  if (k.nmod == OZ_MAXMOD) hipLaunchKernelGGL(k_oz_crt<OZ_MAXMOD>, dim3((unsigned)(s.tiles() * 16)), dim3(256), 0, st, r, k);
+  else hipLaunchKernelGGL(k_oz_crt<0>, dim3((unsigned)(s.tiles() * 16)), dim3(256), 0, st, r, k);
   return hipGetLastError();
 }
 

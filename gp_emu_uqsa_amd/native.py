@@ -67,6 +67,8 @@ SIGNATURES = {
     "gpe_test_oz_product": (_ct.c_int, [_VP, _ct.POINTER(OzOperand), _ct.POINTER(OzOperand),
                                         _ct.POINTER(OzParams), _D, _ct.POINTER(_ct.c_int32),
                                         _ct.POINTER(_ct.c_int32), _ct.POINTER(_ct.c_int8)]),
+    "gpe_test_oz_planes": (_ct.c_int, [_VP, _ct.POINTER(OzOperand), _ct.c_int32, _ct.c_int32, _ct.c_int32,
+                                       _ct.POINTER(_ct.c_int32), _ct.POINTER(_ct.c_int8)]),
     "gpe_abi_version": (_ct.c_int, []),
     "gpe_build_id": (_ct.c_char_p, []),
     "gpe_device_count": (_ct.c_int, []),
@@ -641,6 +643,22 @@ class Context:
             exa.ctypes.data_as(i32), exb.ctypes.data_as(i32),
             None if res is None else res.ctypes.data_as(_ct.POINTER(_ct.c_int8))), "gpe_test_oz_product")
         return {"C": Cc, "exa": exa, "exb": exb, "res": res}
+
+    def test_oz_planes(self, a, *, packed=False, K=0, nmod=16):
+        """One operand through the production conversion (gpe_test_oz_planes, a test hook).
+        a: as test_oz_product's.  Returns dict(ex, planes): the exponents of the rows padded to
+        P = 256 ceil(R / 256) and the int8 planes, nmod x P x K (packed: nmod x P x P, row j the
+        column j of X, zero above its 256-row panel)."""
+        src = _np.ascontiguousarray(a["src"], dtype=_np.float64).ravel()
+        oa = OzOperand(_ptr(src), src.size, int(a.get("offset", 0)), int(a["ld"]), int(a.get("trans", 0)),
+                       int(a.get("R", 0)), int(a.get("Kv", 0)), int(a.get("mask", 0)))
+        P = (oa.R + 255) // 256 * 256
+        ex = _np.zeros(max(P, 1), dtype=_np.int32)
+        planes = _np.zeros((int(nmod), max(P, 1), max(P if packed else int(K), 1)), dtype=_np.int8)
+        self._check(self.lib.gpe_test_oz_planes(
+            self._h, _ct.byref(oa), int(bool(packed)), int(K), int(nmod), ex.ctypes.data_as(_ct.POINTER(_ct.c_int32)),
+            planes.ctypes.data_as(_ct.POINTER(_ct.c_int8))), "gpe_test_oz_planes")
+        return {"ex": ex, "planes": planes}
 
     def test_gemm_group(self, bufs, probs, *, kind, split=False, listed=False, reps=1):
         """One launch of the grouped fp64 GEMM on a group of problems through the production

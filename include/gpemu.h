@@ -37,8 +37,8 @@ extern "C" {
                                 9: gpe_dist_local_rows takes the basis width q;
                                 10: gpe_ozaki_stats (gpe_loo, gpe_posterior_pivchol,
                                 gpe_posterior_imse, gpe_posterior_grad, gpe_posterior_mean, gpe_posterior_groups and the test
-                                hooks gpe_test_oz_product and gpe_test_gemm_group were added within 10:
-                                additions, nothing existing changed) */
+                                hooks gpe_test_oz_product, gpe_test_oz_planes and gpe_test_gemm_group were
+                                added within 10: additions, nothing existing changed) */
 
 enum gpe_status {
     GPE_OK = 0,
@@ -369,6 +369,21 @@ typedef struct gpe_oz_params {
 int gpe_test_oz_product(gpe_ctx* ctx, const gpe_oz_operand* a, const gpe_oz_operand* b,
                         const gpe_oz_params* p, double* C, int32_t* exa_out, int32_t* exb_out,
                         int8_t* res_out);
+
+/* Test hook for one operand's conversion (gpemu_ozaki.hpp), an addition within ABI 10; the
+ * reference has no counterpart.  The operand a (as gpe_test_oz_product's: a window of a host
+ * array, R rows padded to P, a multiple of 256) goes through the production oz_operand
+ * (packed 0: k_oz_rowexp<trans> and k_oz_split_rect<trans>, k padded to K, a multiple of 64 in
+ * [64, 2^17 - 128], >= Kv) or oz_operand_packed (packed 1: X is R x R lower-triangular, R a
+ * multiple of 128, ld and offset even, K ignored and taken as P; k_oz_colexp and k_oz_split)
+ * on device buffers of its own, freed on exit, with the constants of oz_consts(nmod, K).
+ * Outputs: ex_out, the P row (packed: column) exponents, and planes_out, the int8 planes of
+ * all nmod moduli, [modulus][row][k]: nmod x P x K bytes; packed: nmod x P x P bytes, row j the
+ * column j of X over k = the rows of X, the bytes with k < 256 (j / 256) -- above column j's
+ * panel, which the planes do not hold -- 0.  The planes are filled with 0x55 before the
+ * conversion: a byte the kernels fail to write shows. */
+int gpe_test_oz_planes(gpe_ctx* ctx, const gpe_oz_operand* a, int32_t packed, int32_t K,
+                       int32_t nmod, int32_t* ex_out, int8_t* planes_out);
 
 /* Test hook for one launch of the plain (non-fused) grouped fp64 GEMM k_gemm on a group of
  * problems, an addition within ABI 10; the reference has no counterpart.  Descriptors come
