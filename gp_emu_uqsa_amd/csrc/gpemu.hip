@@ -25,6 +25,7 @@
 #include "../../include/gpemu.h"
 #include "gpemu_kernels.hpp"
 #include "gpemu_gemm_sched.hpp"
+#include "gpemu_chol_sched.hpp"
 #include "gpemu_small.hpp"
 #include "gpemu_tiny.hpp"
 #include "gpemu_snb.hpp"
@@ -63,50 +64,6 @@ enum AdhocSlot {
   ADHOC_TEST = ADHOC_DESC_BASE + 8,       // gpe_test_gemm
   ADHOC_BENCH = ADHOC_DESC_BASE + 16,     // gpe_bench_gemm
 };
-
-struct Plan {
-  long long n_pad = 0;
-  const double* a_ptr = nullptr;   // buffers the descriptors point into
-  const double* b_ptr = nullptr;
-  // fused schedule: one launch per column block (see build_plan); fused_aug: the same
-  // launches also carrying the augmented row (when the workspace has one)
-  std::vector<int> fused, fused_aug;
-  std::vector<int> trtri;   // launches in order
-  // per TRTRI level (launches trtri[2 l], trtri[2 l + 1]): its block pairs {t0, h, t1}
-  std::vector<std::vector<std::array<int, 3>>> tri_pairs;
-  int lauum = -1;
-  bool aug = false;         // fused_aug is built
-  // group schedule (the default for a lone evaluation): ONE launch per column group of width >= 2 holding
-  // its whole chain (diagonal and panel tiles of every step, handed on by counters in
-  // F.flags) beside the previous group's trailing update; width-1 groups as fused.  Per
-  // step: the launch to issue, -1 for the later steps of a group
-  std::vector<int> grp, grp_aug;
-  // the split sweep (build_plan): tile column h > 0 where the factorisation of the training
-  // matrix is split, its launches per step as fused / fused_aug / grp / grp_aug (columns
-  // [0, h): phase A, [h, NB): the Schur complement's own sweep) and the launch that updates
-  // the augmented row's tiles [h, NB) by the first h columns
-  int split_h = 0, aug_mid = -1;
-  std::vector<int> sfused, sfused_aug, sgrp, sgrp_aug;
-  // the nested split (build_plan): tile column q = h / 2 > 0 where phase A is split once more,
-  // its three sweeps' launches per step ([0, q) over all rows, [q, h) over the rows from q,
-  // [h, NB)) and the launch that updates the augmented row's tiles [q, h) by the first q columns
-  int split_q = 0, aug_q = -1;
-  std::vector<int> nfused, nfused_aug, ngrp, ngrp_aug;
-  // the TRTRI by sides of the split column (tri_ahead; sides: these are built): per level below
-  // the top one its launch pairs {T^T, X21} of the block pairs inside [0, h), then of those
-  // inside [h, NB) (-1: none)
-  bool sides = false;
-  std::vector<std::array<int, 4>> trtri_side;
-  std::vector<GemmLaunch> launches;
-  std::vector<GemmProb> probs;
-  std::vector<unsigned> tiles;   // concatenated tile lists
-};
-
-// F.flags: NB ints each of the diagonal-inverse flags, the group schedule's column and
-// panel counters, the list tickets of the Cholesky launches (one per column step), the
-// diagonal tiles' quadrant counters (G_DQUAD) and the panel tiles' stored-update counters
-// (G_PHALF0)
-constexpr int FACT_FLAG_INTS = 6;
 
 // rows of the Schur complement from which the objective's Cholesky is split and S runs on the
 // int8 cores (GPEMU_OZAKI_CHOL_MIN)
@@ -333,27 +290,15 @@ struct gpe_ctx {
   double f_nu = 0.0;
   double f_rscale = 0.0;     // coefficient of diag(r) in the resident A (gpe_loo takes it out again)
 
-  // GPEMU_POTRF=group: one launch per column group (Plan::grp); list positions of the
-  // chain steps (GPEMU_GROUP_P0, GPEMU_GROUP_STRIDE)
-  bool potrf_group = true;    // the group launches are built (Plan::grp)
+  // how the fused Cholesky is cut into launches: per step and by column groups, the group
+  // widths, the super-blocks (GPEMU_POTRF, GPEMU_GROUP_P0, GPEMU_GROUP_STRIDE, GPEMU_POTRF_W,
+  // GPEMU_POTRF_SB; gpemu_chol_sched.hpp)
+  CholSchedParams sched;
   // 0 auto: group launches while this is the only objective evaluation in flight on the
   // device, one launch per step when others run beside it (their tiles fill the per-step
   // drains, and the group launches' waiting chain tiles would hold slots they could use);
   // 1 always group (GPEMU_POTRF=group), 2 always per step (GPEMU_POTRF=fused)
   int potrf_mode = 0;
-  int grp_p0 = 512, grp_stride = 896;
-  // column-group widths of the fused Cholesky: {width, min remaining columns}, first
-  // match wins, else 1 (GPEMU_POTRF_W="4:64,2:32" style).  Round 4 (a shorter chain per
-  // step): 4 while more than 48 columns remain, then 2 while more than 24 -- at n = 16384
-  // the two-try bench 14.70 / 14.72 -> 14.78 / 14.81 evals/s and the Cholesky 28.4 -> 28.1 ms
-  // against round 3's {4, 80}, {2, 40} (profiles/group_width_ab_r04.log)
-  std::vector<std::pair<int, int>> potrf_groups = {{4, 48}, {2, 24}};
-  // super-blocks of the fused Cholesky (lazy far updates): up to potrf_sb consecutive column
-  // groups of one width >= 2 form a super-block; the columns beyond it receive its update
-  // as ONE trailing update of K = 128 x its width, spread over the next super-block's
-  // launches (1: every group updates the whole trailing matrix, K = 128 x its width), while
-  // more than potrf_sb_min tile columns remain (GPEMU_POTRF_SB="groups:min_remaining")
-  int potrf_sb = 2, potrf_sb_min = 80;
   // the fused Cholesky on the context's high-priority stream (default 1; 0: on the
   // context stream, GPEMU_CHOL_PRIO=0)
   int chol_prio = 1;
@@ -571,25 +516,6 @@ int launch_gemm_range(gpe_ctx* c, const GemmLaunch& L, hipStream_t st = nullptr)
   return GPE_OK;
 }
 
-// One launch of the cached schedule from its problems: in order_tiles' order, or in the
-// given one (codes into probs), or -- split K, 256 problems or more -- the implicit one.
-void add_launch(Plan& pl, GemmKind kind, const std::vector<GemmProb>& probs, double flops,
-                const std::vector<unsigned>* order = nullptr) {
-  GemmLaunch L = begin_launch(kind, pl.probs, flops);
-  bool listable = probs.size() < 256;
-  for (const GemmProb& p : probs) {
-    push_prob(L, pl.probs, p, true);
-    listable = listable && p.mt <= 4096 && p.nt <= 4096 && p.ksplit <= 1;
-  }
-  if (order) {
-    set_list(L, pl.tiles, *order);
-  } else if (listable) {
-    const std::vector<unsigned> tl = order_tiles(probs);
-    if ((int)tl.size() == L.tiles) set_list(L, pl.tiles, tl);
-  }
-  pl.launches.push_back(L);
-}
-
 bool oz_use(const gpe_ctx* c);
 int oz_chol_split(const gpe_ctx* c, const Fact& F);
 int oz_chol_nest_split(const gpe_ctx* c, const Fact& F, int h);
@@ -632,563 +558,23 @@ int adhoc_gemm(gpe_ctx* c, AdhocSlot slot, const std::vector<AdhocGemm>& g, Gemm
   return GPE_OK;
 }
 
-// Build the (n_pad-dependent, data-independent) GEMM schedule and upload it.
+// Build the (n_pad-dependent, data-independent) GEMM schedule (build_chol_plan,
+// gpemu_chol_sched.hpp) and upload it.
 int build_plan(gpe_ctx* c, Fact& F) {
   Plan& pl = F.plan;
   if (pl.n_pad == F.n_pad && pl.a_ptr == F.A && pl.b_ptr == F.B && !pl.launches.empty()) return GPE_OK;
-  pl = Plan();
-  pl.n_pad = F.n_pad;
-  pl.a_ptr = F.A;
-  pl.b_ptr = F.B;
-  const long long ld = F.n_pad;
-  const int NB = F.NB;
-  const double T = TILE;
-  double* A = F.A;
-  double* B = F.B;
-  auto tile = [&](double* M, int i, int j) { return M + (long long)i * TILE + (long long)j * TILE * ld; };
-  // tile (0, j) of the augmented row (ld TILE); the fused schedule is built without it
-  // and, when the workspace has one, a second time with it (aug in the lambdas below)
-  pl.aug = F.aug && F.Faug;
-  bool aug = false;
-  auto atile = [&](int j) { return F.Faug + (long long)j * TILE * TILE; };
-  // --- Cholesky (right-looking, 128-column steps)
-  pl.fused.assign(NB, -1);
-  pl.fused_aug.assign(NB, -1);
-  if (c->potrf_group) {
-    pl.grp.assign(NB, -1);
-    if (pl.aug) pl.grp_aug.assign(NB, -1);
-  }
-  // One sweep of the schedule: NC tile columns of the sub-matrix whose origin is tile (o, o)
-  // and which has NR tile rows, its launches indexed by global column in ix = {fused,
-  // fused_aug, grp, grp_aug}.  (0, NB, NB) is the whole factorisation.  The split sweep
-  // (Plan::split_h) is (0, h, NB): the first h columns over all rows, every trailing update
-  // clipped to columns < h, so L11 and L21 end final and A22 untouched -- then (h, NB - h,
-  // NB - h), the unsplit schedule of the Schur complement, on its own slices of F.flags,
-  // F.logdet and the diagonal tiles of B, reporting global columns.  t, a, b, g0 below are
-  // local to the sweep; groups and super-blocks go by the rows left (NR - column).
-  auto sweep = [&](const int o, const int NC, const int NR, const std::array<std::vector<int>*, 4>& ix) -> int {
-  auto tile = [&](double* M, int i, int j) { return M + (long long)(o + i) * TILE + (long long)(o + j) * TILE * ld; };
-  auto atile = [&](int j) { return F.Faug + (long long)(o + j) * TILE * TILE; };
-  int* const flags0 = F.flags + o;
-  // Fused schedule, one launch per column block t.  Columns are grouped (widths from
-  // potrf_groups: wide groups while the trailing matrix is large, width 1 at the end).
-  // Launch t, t at position h of group g:
-  //   critical: tile (t,t) updated by its pending columns [p0, t) -- the previous
-  //             group when h = 0, else the earlier columns of g -- then factored and
-  //             inverted in-kernel (G_DIAG); panel tiles (i,t), i > t, updated the
-  //             same way and multiplied by X_t^T once flags[t] is released (G_PANEL);
-  //   bulk:     part h of the trailing update by the previous group (K = its width
-  //             x 128) over columns j > start(g): part h holds column start(g)+h+1
-  //             (factored next) plus a balanced share of the columns after g.
-  // the diagonal tile of step t with K pending columns (from Lp): the pending update runs
-  // as DQ_N G_DQUAD workgroups (dquad, pushed before the tile; none for K = 0) and the
-  // G_DIAG workgroup waits for them, loads the updated tile and factors it
-  int* cnt_dq = flags0 + 4 * NB;
-  auto dquad = [&](int t, const double* Lp, int K, double alpha) {
-    GemmProb p = mkprob(Lp, ld, nullptr, 0, tile(A, t, t), ld, DQ_N, 1, K, G_DQUAD, alpha, 1.0);
-    p.post = cnt_dq + t;
-    p.diag_col0 = (o + t) * TILE;
-    return p;
-  };
-  auto diagprob = [&](int t, const double* Lp, int K, double alpha) {
-    (void)Lp;
-    (void)alpha;
-    GemmProb p = mkprob(nullptr, ld, nullptr, ld, tile(A, t, t), ld, 1, 1, 0, G_DIAG, 1.0, 1.0);
-    if (K > 0) {
-      p.pre0 = cnt_dq + t;
-      p.pre0_n = DQ_N;
-    }
-    p.X = tile(B, t, t);
-    p.ldx = ld;
-    p.logdet = F.logdet + o + t;
-    p.diag_col0 = (o + t) * TILE;
-    p.flag = flags0 + t;
-    p.Ld = tile(A, t, t);
-    p.ldd = ld;
-    return p;
-  };
-  // panel tiles: the G_PHALF0 problem (pending update + rows 0-63 of the substitution) and,
-  // from it, the G_PHALF1 problem (rows 64-127, after every G_PHALF0 tile of the step
-  // stored its update: pc_n of them)
-  int* cnt_pc = flags0 + 5 * NB;
-  auto panelprob = [&](int t, const double* Lp, const double* Lt, int K, double alpha) {
-    GemmProb p = mkprob(Lp, ld, Lt, ld, tile(A, t + 1, t), ld, NR - t - 1, 1, K, G_PANEL | G_PHALF0, alpha, 1.0);
-    p.cpost = cnt_pc + t;
-    p.X = tile(B, t, t);
-    p.ldx = ld;
-    p.flag = flags0 + t;
-    p.diag_col0 = (o + t) * TILE;   // step index for the GEMM_TRACE dev build
-    p.Ld = tile(A, t, t);
-    p.ldd = ld;
-    return p;
-  };
-  // the augmented row's panel tile (aug, t): pending columns [p0, t), then x L_tt^-T
-  auto augpanel = [&](int t, int p0, int K, double alpha) {
-    GemmProb p = mkprob(K ? atile(p0) : nullptr, TILE, K ? tile(A, t, p0) : nullptr, ld, atile(t), TILE, 1, 1, K,
-                        G_PANEL | G_PHALF0, alpha, 1.0);
-    p.cpost = cnt_pc + t;
-    p.X = tile(B, t, t);
-    p.ldx = ld;
-    p.flag = flags0 + t;
-    p.Ld = tile(A, t, t);
-    p.ldd = ld;
-    p.diag_col0 = -TILE;   // (no GEMM_TRACE slot)
-    return p;
-  };
-  auto half1 = [&](const GemmProb& h0, int pc_n) {
-    GemmProb p = h0;
-    p.flags = G_PANEL | G_PHALF1;
-    p.A = p.B = nullptr;
-    p.K = 0;
-    p.alpha = 1.0;
-    p.beta = 0.0;
-    p.pre0 = h0.cpost;
-    p.pre0_n = pc_n;
-    p.pre1 = nullptr;
-    p.pre1_n = 0;
-    p.cpost = nullptr;
-    return p;
-  };
-  // bulk problems: tiles (i, j), i >= j, j in [a, b), updated by columns [g0, g0 + K/128);
-  // with the augmented row also its tiles (aug, j) (not counted as algorithmic flops)
-  auto bulk = [&](std::vector<GemmProb>& fp, double& fl, int a, int b, int g0, int K) {
-    if (a >= b) return;
-    fp.push_back(mkprob(tile(A, a, g0), ld, tile(A, a, g0), ld, tile(A, a, a), ld, b - a, b - a, K,
-                        G_CLOWER, -1.0, 1.0));
-    fl += (double)(b - a) * T * ((double)(b - a) * T + 1.0) * K;
-    if (b < NR) {
-      fp.push_back(mkprob(tile(A, b, g0), ld, tile(A, a, g0), ld, tile(A, b, a), ld, NR - b, b - a, K, 0,
-                          -1.0, 1.0));
-      fl += 2.0 * (NR - b) * T * (double)(b - a) * T * K;
-    }
-    if (aug) fp.push_back(mkprob(atile(g0), TILE, tile(A, a, g0), ld, atile(a), TILE, 1, b - a, K, 0, -1.0, 1.0));
-  };
-  std::vector<int> gs;   // group starts, then NC
-  for (int g = 0; g < NC;) {
-    gs.push_back(g);
-    int w = 1;
-    for (const auto& r : c->potrf_groups)
-      if (NR - g > r.second) { w = r.first; break; }
-    g += std::max(1, std::min(w, NC - g));
-  }
-  gs.push_back(NC);
-  // Super-blocks (lazy far updates).  Group 0 is a super-block of its own; after it, up to
-  // potrf_sb consecutive groups of one width >= 2 form one while more than potrf_sb_min
-  // columns remain (later groups, and width-1 groups, stay single: there the longer pending
-  // update of a super-block's first column lengthens a chain the bulk no longer hides).
-  // For group gi with columns [gb, ge) in super-block [sb, se):
-  //   src0[gi]: start of the columns whose update its own columns still lack when it starts
-  //     -- the previous super-block when gi opens its super-block, else the previous group;
-  //   its launches carry (bulk segments, balanced over its W launches):
-  //     the update by [src0, gb) of its later columns [gb+1, ge) (the column factored next),
-  //     the update by [src0, gb) of the rest of its super-block [ge, se),
-  //     a share of the previous super-block's update of the columns beyond [se, NC)
-  //     (K = 128 x the previous super-block's width: the long-K far update, each far tile
-  //     read and written once per super-block instead of once per group).
-  // Every column j still receives every earlier column's update before it is factored: a
-  // far column gets super-block s's update during super-block s + 1, before s + 2 opens.
-  const int ng = (int)gs.size() - 1;
-  std::vector<int> sbs(ng), sbe(ng), src0(ng, 0);
-  {
-    int cur = 0, cnt = 0;
-    for (int gi = 0; gi < ng; ++gi) {
-      const int w = gs[gi + 1] - gs[gi];
-      const bool open = gi <= 1 || w < 2 || w != gs[gi] - gs[gi - 1] || cnt >= c->potrf_sb ||
-                        NR - gs[gi] <= c->potrf_sb_min;
-      if (open) { cur = gs[gi]; cnt = 0; }
-      sbs[gi] = cur;
-      ++cnt;
-    }
-    for (int gi = ng - 1; gi >= 0; --gi) sbe[gi] = (gi + 1 < ng && sbs[gi + 1] == sbs[gi]) ? sbe[gi + 1] : gs[gi + 1];
-    for (int gi = 1; gi < ng; ++gi) src0[gi] = (sbs[gi] == gs[gi]) ? sbs[gi - 1] : gs[gi - 1];
-  }
-  // bulk segments of group gi: {a, b, g0, K}: columns [a, b) by columns [g0, g0 + K / 128)
-  struct Seg { int a, b, g0, K; };
-  std::vector<std::vector<Seg>> segs(ng);
-  {
-    auto cost = [&](int j, int K) { return (double)(NR - j) * K; };
-    for (int gi = 1; gi < ng; ++gi) {   // a super-block's rest: by src0, within the super-block
-      const int ge = gs[gi + 1], Kb = (gs[gi] - src0[gi]) * TILE;
-      if (ge < sbe[gi]) segs[gi].push_back({ge, sbe[gi], src0[gi], Kb});
-    }
-    // the far update of each super-block [s0, s1) (the previous one of its successor's
-    // groups), split over the successor's groups so their launches carry equal work
-    for (int gi = 1; gi < ng; ++gi) {
-      if (sbs[gi] != gs[gi]) continue;   // once per super-block, at its opening group
-      const int s0 = sbs[gi - 1], s1 = gs[gi], se = sbe[gi], Kf = (s1 - s0) * TILE;
-      std::vector<int> mem;
-      for (int gj = gi; gj < ng && sbs[gj] == sbs[gi]; ++gj) mem.push_back(gj);
-      std::vector<double> fixed(mem.size(), 0.0);
-      double F = 0.0, tot = 0.0;
-      for (int j = se; j < NC; ++j) F += cost(j, Kf);
-      for (size_t m = 0; m < mem.size(); ++m) {
-        const int gj = mem[m], Kb = (gs[gj] - src0[gj]) * TILE;
-        for (int j = gs[gj] + 1; j < gs[gj + 1]; ++j) fixed[m] += cost(j, Kb);
-        for (const Seg& sg : segs[gj])
-          for (int j = sg.a; j < sg.b; ++j) fixed[m] += cost(j, sg.K);
-        tot += fixed[m];
-      }
-      tot += F;
-      int j = se;
-      for (size_t m = 0; m < mem.size(); ++m) {
-        const double want = std::max(0.0, tot / mem.size() - fixed[m]);
-        const int a = j;
-        double got = 0.0;
-        while (j < NC && (m + 1 == mem.size() || got + 0.5 * cost(j, Kf) <= want)) got += cost(j++, Kf);
-        if (j > a) segs[mem[m]].push_back({a, j, s0, Kf});
-      }
-    }
-  }
-  for (int va = 0; va < (pl.aug ? 2 : 1); ++va) {
-  aug = va == 1;
-  std::vector<int>& fidx = *ix[aug ? 1 : 0];
-  for (int gi = 0; gi + 1 < (int)gs.size(); ++gi) {
-    const int gb = gs[gi], ge = gs[gi + 1], W1 = ge - gb;
-    // the group's bulk segments, column by column, split into W1 parts of equal work
-    // (part h also carries column gb + h + 1 by src0: the column factored next)
-    std::vector<std::vector<Seg>> part(W1);
-    if (gi > 0) {
-      const int Kb = (gb - src0[gi]) * TILE;
-      std::vector<double> load(W1, 0.0);
-      for (int h = 0; h + 1 < W1; ++h) load[h] = (double)(NR - (gb + h + 1)) * Kb;
-      double tot = 0.0;
-      for (int h = 0; h < W1; ++h) tot += load[h];
-      std::vector<std::pair<int, int>> cols;   // (column, segment)
-      for (int si = 0; si < (int)segs[gi].size(); ++si)
-        for (int j = segs[gi][si].a; j < segs[gi][si].b; ++j) {
-          cols.push_back({j, si});
-          tot += (double)(NR - j) * segs[gi][si].K;
-        }
-      size_t u = 0;
-      double cum = 0.0;
-      for (int h = 0; h < W1; ++h) {
-        cum += load[h];
-        const double target = tot * (h + 1) / W1;
-        while (u < cols.size()) {
-          const Seg& sg = segs[gi][cols[u].second];
-          const double cj = (double)(NR - cols[u].first) * sg.K;
-          if (h < W1 - 1 && cum + 0.5 * cj > target) break;
-          cum += cj;
-          std::vector<Seg>& ps = part[h];
-          if (!ps.empty() && ps.back().b == cols[u].first && ps.back().g0 == sg.g0 && ps.back().K == sg.K) ++ps.back().b;
-          else ps.push_back({cols[u].first, cols[u].first + 1, sg.g0, sg.K});
-          ++u;
-        }
-      }
-    }
-    for (int h = 0; h < W1; ++h) {
-      const int t = gb + h;
-      const int p0 = (h == 0) ? src0[gi] : gb;
-      const int K = (t - p0) * TILE;
-      const double al = K ? -1.0 : 1.0;
-      const int m = NR - t - 1;
-      std::vector<GemmProb> fp;
-      if (K) fp.push_back(dquad(t, tile(A, t, p0), K, al));
-      fp.push_back(diagprob(t, K ? tile(A, t, p0) : nullptr, K, al));
-      double fl = T * (T + 1.0) * K;
-      const int pc_n = (m >= 1 ? m : 0) + (aug ? 1 : 0);
-      const size_t h0at = fp.size();
-      if (m >= 1) {
-        fp.push_back(panelprob(t, K ? tile(A, t + 1, p0) : nullptr, K ? tile(A, t, p0) : nullptr, K, al));
-        fl += 2.0 * m * T * T * K + (double)m * T * T * T;
-      }
-      if (aug) fp.push_back(augpanel(t, p0, K, al));
-      for (size_t k = h0at, e = fp.size(); k < e; ++k) fp.push_back(half1(fp[k], pc_n));
-      if (gi > 0) {
-        const int g0 = src0[gi], Kb = (gb - g0) * TILE;
-        if (h + 1 < W1) bulk(fp, fl, t + 1, t + 2, g0, Kb);   // the column factored next
-        for (const Seg& sg : part[h]) bulk(fp, fl, sg.a, sg.b, sg.g0, sg.K);
-      }
-      fidx[o + t] = (int)pl.launches.size();
-      add_launch(pl, GEMM_FUSED, fp, fl);
-      pl.launches.back().ticket = flags0 + 3 * NB + t;
-    }
-  }
-  // the group schedule: one launch per group of width >= 2.  Its tile list (= dispatch
-  // order): the first step's diagonal tile; the previous group's updates of the group's
-  // later columns (counted per column in cnt_col); the previous group's update of the
-  // columns after the group, in order_tiles' order; spliced into it, step h's chain tiles
-  // (its diagonal tile, then its panels, counted per step in cnt_pan) at list position
-  // grp_p0 + h grp_stride (step 0's first panel at 256: workgroup 0's CU partner).
-  // Step h >= 1 waits for step h-1's panels and its column's update, so every wait points
-  // to earlier tiles; one drain per group instead of one per step.
-  if (c->potrf_group) {
-    std::vector<int>& gidx = *ix[aug ? 3 : 2];
-    int* cnt_col = flags0 + NB;
-    int* cnt_pan = flags0 + 2 * NB;
-    for (int gi = 0; gi + 1 < (int)gs.size(); ++gi) {
-      const int gb = gs[gi], ge = gs[gi + 1], W1 = ge - gb;
-      if (W1 < 2) {
-        gidx[o + gb] = fidx[o + gb];
-        continue;
-      }
-      const int g0 = src0[gi], Kb = (gb - g0) * TILE;
-      std::vector<GemmProb> fp;
-      double fl = 0.0;
-      auto codes = [&](int pi, std::vector<unsigned>& out) {
-        const GemmProb& q = fp[pi];
-        for (int ti = 0; ti < q.mt; ++ti)
-          for (int tj = 0; tj < q.nt && ((q.flags & G_CLOWER) == 0 || tj <= ti); ++tj)
-            out.push_back(tile_code(pi, ti, tj));
-      };
-      std::vector<unsigned> early, bulkc;
-      std::vector<std::vector<unsigned>> seg(W1);
-      std::vector<int> ncol(W1, 0), npan(W1, 0);
-      if (gi > 0)
-        for (int h = 1; h < W1; ++h) {   // column gb+h by the previous group
-          const size_t b0 = fp.size();
-          bulk(fp, fl, gb + h, gb + h + 1, g0, Kb);
-          for (size_t k = b0; k < fp.size(); ++k) {
-            fp[k].post = cnt_col + gb + h;
-            const size_t e0 = early.size();
-            codes((int)k, early);
-            ncol[h] += (int)(early.size() - e0);
-          }
-        }
-      for (int h = 0; h < W1; ++h) {
-        const int t = gb + h;
-        const int p0 = (h == 0) ? g0 : gb;
-        const int K = (t - p0) * TILE;
-        const double al = K ? -1.0 : 1.0;
-        const int m = NR - t - 1;
-        auto wire = [&](GemmProb& q) {
-          if (h == 0) return;
-          q.pre0 = cnt_pan + t - 1;
-          q.pre0_n = npan[h - 1];
-          if (gi > 0) {
-            q.pre1 = cnt_col + t;
-            q.pre1_n = ncol[h];
-          }
-        };
-        if (K) {   // the step's hand-offs gate its diagonal tile's quadrants
-          GemmProb dq = dquad(t, tile(A, t, p0), K, al);
-          wire(dq);
-          fp.push_back(dq);
-          codes((int)fp.size() - 1, seg[h]);
-        }
-        GemmProb d = diagprob(t, K ? tile(A, t, p0) : nullptr, K, al);
-        if (!K) wire(d);
-        fp.push_back(d);
-        codes((int)fp.size() - 1, seg[h]);
-        fl += T * (T + 1.0) * K;
-        const int pc_n = (m >= 1 ? m : 0) + (aug ? 1 : 0);
-        const size_t h0at = fp.size();
-        if (m >= 1) {
-          GemmProb q = panelprob(t, K ? tile(A, t + 1, p0) : nullptr, K ? tile(A, t, p0) : nullptr, K, al);
-          wire(q);
-          q.post = cnt_pan + t;
-          fp.push_back(q);
-          codes((int)fp.size() - 1, seg[h]);
-          fl += 2.0 * m * T * T * K + (double)m * T * T * T;
-        }
-        if (aug) {
-          GemmProb pa = augpanel(t, p0, K, al);
-          wire(pa);
-          pa.post = cnt_pan + t;
-          fp.push_back(pa);
-          codes((int)fp.size() - 1, seg[h]);
-        }
-        for (size_t k = h0at, e = fp.size(); k < e; ++k) {   // the rows 64-127 halves
-          fp.push_back(half1(fp[k], pc_n));
-          codes((int)fp.size() - 1, seg[h]);
-        }
-        npan[h] += 2 * pc_n;   // both halves of every panel tile post cnt_pan
-      }
-      if (gi > 0 && !segs[gi].empty()) {   // the group's bulk segments (the rest of its super-block, a far share)
-        const size_t b0 = fp.size();
-        for (const Seg& sg : segs[gi]) bulk(fp, fl, sg.a, sg.b, sg.g0, sg.K);
-        std::vector<GemmProb> sub(fp.begin() + b0, fp.end());
-        for (unsigned code : order_tiles(sub)) bulkc.push_back(code + ((unsigned)b0 << 24));
-      }
-      // assemble: diag(gb) (after its quadrants), early, bulk; step 0's panels at grp_p0
-      // (its first beside the diagonal tile), step h's chain at grp_p0 + h grp_stride
-      const size_t head = gi > 0 ? DQ_N + 1 : 1;   // step 0: quadrant blocks (when K > 0) and diagonal tile
-      std::vector<unsigned> base(seg[0].begin(), seg[0].begin() + head);
-      base.insert(base.end(), early.begin(), early.end());
-      base.insert(base.end(), bulkc.begin(), bulkc.end());
-      std::vector<unsigned> rest0(seg[0].begin() + head, seg[0].end());
-      // step h's tiles go before base position min(|base|, p0 + h stride), for h >= 1 not
-      // before the column updates they wait on: the positions do not decrease with h, so
-      // the steps stay in order even where they clamp
-      std::vector<unsigned> order;
-      auto pos = [&](int h) {
-        size_t at = (size_t)c->grp_p0 + (size_t)h * c->grp_stride;
-        at = std::max(at, h >= 1 ? head + early.size() : head);   // after the step's diagonal tile
-        return std::min(base.size(), at);
-      };
-      int h = 0;
-      for (size_t i = 0; i <= base.size(); ++i) {
-        while (h < W1 && pos(h) == i) {
-          const std::vector<unsigned>& sg = h == 0 ? rest0 : seg[h];
-          order.insert(order.end(), sg.begin(), sg.end());
-          ++h;
-        }
-        if (i < base.size()) order.push_back(base[i]);
-      }
-      // The first 512 workgroups of a launch on an idle GPU fill two slots per CU in
-      // order, workgroup 256 + k beside workgroup k (tools/hip/placement_probe.hip): step
-      // 0's first panel tile goes to 256 + (head - 1), beside the diagonal tile, so the
-      // factorisation has its CU's SIMDs to itself.  (Pinning the later steps' diagonal
-      // tiles the same way measured no faster: DESIGN.md section 10.)
-      auto move_to = [&](unsigned code, size_t at) {
-        const auto it = std::find(order.begin(), order.end(), code);
-        order.erase(it);
-        order.insert(order.begin() + std::min(at, order.size()), code);
-      };
-      if (!rest0.empty() && order.size() > 256 + head) {   // the first panel tile beside the diagonal
-        const auto it = std::find(order.begin(), order.end(), rest0.front());
-        if ((size_t)(it - order.begin()) > 255 + head) move_to(rest0.front(), 255 + head);
-      }
-      // every tile may wait only on tiles before it in the list (the dispatch order):
-      // then the earliest unfinished tile can always run.  Checked, not assumed.
-      if (!waits_point_back(fp.data(), order))
-        return fail(c, GPE_ERR_HIP, "internal error: group schedule waits on a later tile");
-      gidx[o + gb] = (int)pl.launches.size();
-      add_launch(pl, GEMM_FUSED, fp, fl, &order);
-      pl.launches.back().ticket = flags0 + 3 * NB + gb;
-    }
-  }
-  }
-  return GPE_OK;
-  };
-  CHK(sweep(0, NB, NB, {&pl.fused, &pl.fused_aug, &pl.grp, &pl.grp_aug}));
-  // --- triangular inverse X = L^-1 in B (diagonal tiles already hold Dinv)
-  // the two problems of block pair pr = {t0, h, t1}, appended to a level's two launches
-  auto tri_pair = [&](const std::array<int, 3>& pr, std::vector<GemmProb>& pa, std::vector<GemmProb>& pb, double& fa,
-                      double& fb) {
-    const int t0 = pr[0], h = pr[1], t1 = pr[2];
-    const int a = h - t0, b = t1 - h;
-    // T^T (a x b tiles, stored in the upper block rows t0:h, cols h:t1 of B)
-    //   = X11^T L21^T ;  opA(m,k) = X11(k,m): K-contiguous, upper -> kbeg = ti*128
-    pa.push_back(mkprob(tile(B, t0, t0), ld, tile(A, h, t0), ld, tile(B, t0, h), ld, a, b,
-                        a * TILE, G_KBEG_TI, 1.0, 0.0));
-    fa += (double)a * T * a * T * b * T;   // triangular a x a times a x b
-    // X21 = -X22 T ;  opA = X22 lower -> kend = (ti+1)*128 ; opB(k,n) = T^T(n,k)
-    pb.push_back(mkprob(tile(B, h, h), ld, tile(B, t0, h), ld, tile(B, h, t0), ld, b, a,
-                        b * TILE, G_KEND_TI, -1.0, 0.0));
-    fb += (double)b * T * b * T * a * T;
-  };
-  for (int s = 2; s / 2 < NB; s *= 2) {
-    std::vector<GemmProb> pa, pb;
-    const std::vector<std::array<int, 3>> prs = trtri_level_pairs(NB, s);
-    double fa = 0.0, fb = 0.0;
-    for (const auto& pr : prs) tri_pair(pr, pa, pb, fa, fb);
-    if (pa.empty()) continue;
-    pl.tri_pairs.push_back(prs);
-    split_k(pa, F.part, F.tcnt);
-    split_k(pb, F.part, F.tcnt);
-    pl.trtri.push_back((int)pl.launches.size());
-    add_launch(pl, GEMM_AK, pa, fa);
-    pl.trtri.push_back((int)pl.launches.size());
-    add_launch(pl, GEMM_PLAIN, pb, fb);
-  }
-  // --- A^-1 = X^T X (lower tiles), written over L in A
-  pl.lauum = (int)pl.launches.size();
-  {
-    const double N = (double)F.n_pad;
-    std::vector<GemmProb> lp = {mkprob(B, ld, B, ld, A, ld, NB, NB, (int)F.n_pad, G_CLOWER | G_KBEG_TI, 1.0, 0.0)};
-    split_k(lp, F.part, F.tcnt);
-    add_launch(pl, GEMM_AK_BK, lp, N * N * N / 3.0);
-  }
+  const FactBufs fb = {F.A, F.B, F.aug ? F.Faug : nullptr, F.n_pad, F.NB, F.flags, F.logdet, F.part, F.tcnt};
+  // the training matrix's sweep may be split, and its first phase once more
+  const int h = (&F == &c->tr) ? oz_chol_split(c, F) : 0;
+  const int q = h ? oz_chol_nest_split(c, F, h) : 0;
   const int limit = (F.desc_base == 0) ? AUX_DESC_BASE : ADHOC_DESC_BASE - AUX_DESC_BASE;
-  // --- the split sweep of the training matrix (potrf with split): columns [0, h), the Schur
-  // complement S = A22 - L21 L21^T on the int8 cores (chol_schur), then chol(S); between the
-  // phases the augmented row's trailing part takes the first h columns' update in one launch.
-  // Left out (the sweep stays whole) when its descriptors would not fit
-  if (const int h = (&F == &c->tr) ? oz_chol_split(c, F) : 0) {
-    const size_t nl = pl.launches.size(), np = pl.probs.size(), nt = pl.tiles.size();
-    pl.sfused.assign(NB, -1);
-    pl.sfused_aug.assign(NB, -1);
-    if (c->potrf_group) {
-      pl.sgrp.assign(NB, -1);
-      if (pl.aug) pl.sgrp_aug.assign(NB, -1);
-    }
-    const std::array<std::vector<int>*, 4> ix = {&pl.sfused, &pl.sfused_aug, &pl.sgrp, &pl.sgrp_aug};
-    CHK(sweep(0, h, NB, ix));
-    CHK(sweep(h, NB - h, NB - h, ix));
-    if (pl.aug) {
-      pl.aug_mid = (int)pl.launches.size();
-      add_launch(pl, GEMM_PLAIN, {mkprob(F.Faug, TILE, tile(A, h, 0), ld, F.Faug + (long long)h * TILE * TILE, TILE, 1, NB - h,
-                                h * TILE, 0, -1.0, 1.0)}, 0.0);
-    }
-    pl.split_h = h;
-    if ((int)pl.probs.size() > limit) {
-      pl.launches.resize(nl);
-      pl.probs.resize(np);
-      pl.tiles.resize(nt);
-      pl.split_h = 0;
-      pl.aug_mid = -1;
-    }
-    // --- the TRTRI levels below the top one by side of h (a power of two: no pair of theirs
-    // straddles it), so X11 can be formed while the sweep's second phase runs (tri_ahead).  Each
-    // side's launch splits K as the level's one launch does: the same sums, bit for bit.  Left
-    // out the same way
-    if (pl.split_h) {
-      const size_t nl1 = pl.launches.size(), np1 = pl.probs.size(), nt1 = pl.tiles.size();
-      for (size_t lv = 0; lv < pl.tri_pairs.size(); ++lv) {
-        std::array<int, 4> side = {-1, -1, -1, -1};
-        std::vector<GemmProb> wa, wb;
-        double f0 = 0.0, f1 = 0.0;
-        for (const auto& pr : pl.tri_pairs[lv]) tri_pair(pr, wa, wb, f0, f1);
-        int ta = 0, tb = 0, ka = 0, kb = 0;
-        for (const GemmProb& q : wa) { ta += prob_tiles(q); ka = std::max(ka, q.K); }
-        for (const GemmProb& q : wb) { tb += prob_tiles(q); kb = std::max(kb, q.K); }
-        for (int sd = 0; sd < 2; ++sd) {
-          std::vector<GemmProb> pa, pb;
-          double fa = 0.0, fb = 0.0;
-          for (const auto& pr : trtri_side_pairs(pl.tri_pairs[lv], h, sd)) tri_pair(pr, pa, pb, fa, fb);
-          if (pa.empty()) continue;
-          split_k(pa, F.part, F.tcnt, ta, ka);
-          split_k(pb, F.part, F.tcnt, tb, kb);
-          side[2 * sd] = (int)pl.launches.size();
-          add_launch(pl, GEMM_AK, pa, fa);
-          side[2 * sd + 1] = (int)pl.launches.size();
-          add_launch(pl, GEMM_PLAIN, pb, fb);
-        }
-        pl.trtri_side.push_back(side);
-      }
-      pl.sides = true;
-      if ((int)pl.probs.size() > limit) {
-        pl.launches.resize(nl1);
-        pl.probs.resize(np1);
-        pl.tiles.resize(nt1);
-        pl.sides = false;
-      }
-    }
-    // --- the nested split: phase A once more at q = h / 2, the trapezoid's update by the columns
-    // [0, q) a second int8 product (chol_schur at q): columns [0, q) over all rows, then [q, h)
-    // over the rows from q on, then the Schur complement's sweep as above; before the middle sweep
-    // the augmented row's tiles [q, h) take the first q columns' update in one launch (its tiles
-    // [h, NB) still take all h columns' at h: aug_mid).  Left out the same way
-    if (const int q = pl.split_h ? oz_chol_nest_split(c, F, h) : 0) {
-      const size_t nl2 = pl.launches.size(), np2 = pl.probs.size(), nt2 = pl.tiles.size();
-      pl.nfused.assign(NB, -1);
-      pl.nfused_aug.assign(NB, -1);
-      if (c->potrf_group) {
-        pl.ngrp.assign(NB, -1);
-        if (pl.aug) pl.ngrp_aug.assign(NB, -1);
-      }
-      const std::array<std::vector<int>*, 4> nx = {&pl.nfused, &pl.nfused_aug, &pl.ngrp, &pl.ngrp_aug};
-      CHK(sweep(0, q, NB, nx));
-      CHK(sweep(q, h - q, NB - q, nx));
-      for (int v = 0; v < 4; ++v)   // (h, NB - h, NB - h): the split sweep's own launches
-        for (int t = h; t < NB && !nx[v]->empty(); ++t) (*nx[v])[t] = (*ix[v])[t];
-      if (pl.aug) {
-        pl.aug_q = (int)pl.launches.size();
-        add_launch(pl, GEMM_PLAIN, {mkprob(F.Faug, TILE, tile(A, q, 0), ld, F.Faug + (long long)q * TILE * TILE, TILE, 1, h - q,
-                                  q * TILE, 0, -1.0, 1.0)}, 0.0);
-      }
-      pl.split_q = q;
-      if ((int)pl.probs.size() > limit) {
-        pl.launches.resize(nl2);
-        pl.probs.resize(np2);
-        pl.tiles.resize(nt2);
-        pl.split_q = 0;
-        pl.aug_q = -1;
-      }
-    }
+  const bool built = build_chol_plan(pl, fb, c->sched, h, q, limit);
+  const bool fits = (int)pl.probs.size() <= limit;
+  if (!built || !fits) {
+    pl = Plan();   // (not a plan to find cached at the next call)
+    return built ? fail(c, GPE_ERR_UNSUPPORTED, "GEMM schedule too large")
+                 : fail(c, GPE_ERR_HIP, "internal error: group schedule waits on a later tile");
   }
-  if ((int)pl.probs.size() > limit) return fail(c, GPE_ERR_UNSUPPORTED, "GEMM schedule too large");
   for (auto& L : pl.launches) L.first += F.desc_base;
   HIPCHK(c, hipMemcpy(c->dprobs + F.desc_base, pl.probs.data(), pl.probs.size() * sizeof(GemmProb),
                       hipMemcpyHostToDevice));
@@ -1297,8 +683,8 @@ int kbuild(gpe_ctx* c, int kernel, double nu, double s2, double rscale) {
 }
 
 // Right-looking blocked Cholesky, fused: one launch per column step (or per column group,
-// Plan::grp); the diagonal tile of each step is factored by the first workgroup of its
-// launch and the step's panel tiles follow in-launch (build_plan).
+// Plan::idx); the diagonal tile of each step is factored by the first workgroup of its
+// launch and the step's panel tiles follow in-launch (add_sweep, gpemu_chol_sched.hpp).
 // Every launcher of a workspace's schedule first makes sure it is built: growing the
 // tile-list array for one workspace's plan resets the other's (build_plan), e.g. the
 // aux plan of gpe_noise_sample between gpe_factor and a later on-demand TRTRI / LAUUM.
@@ -1325,11 +711,9 @@ int potrf(gpe_ctx* c, Fact& F, bool with_aug = false, bool split = false, bool a
   const bool wa = with_aug && pl.aug;
   const bool tri_ahead = hs && ahead && pl.sides && c->tri_ahead_on && c->chol_prio;
   F.xclear(tri_ahead ? hs : 0);   // the sweep leaves only X's diagonal 16 x 16 blocks (ensure_xdiag)
-  const bool grp = c->potrf_group &&
+  const bool grp = c->sched.group &&
                    (c->potrf_mode == 1 || (c->potrf_mode == 0 && g_inflight[c->device & 63].load() <= 1));
-  const std::vector<int>& fidx = qs ? (grp ? (wa ? pl.ngrp_aug : pl.ngrp) : (wa ? pl.nfused_aug : pl.nfused))
-                                 : hs ? (grp ? (wa ? pl.sgrp_aug : pl.sgrp) : (wa ? pl.sfused_aug : pl.sfused))
-                                      : (grp ? (wa ? pl.grp_aug : pl.grp) : (wa ? pl.fused_aug : pl.fused));
+  const std::vector<int>& fidx = pl.steps(qs ? SWEEP_NESTED : hs ? SWEEP_SPLIT : SWEEP_WHOLE, grp, wa);
   if (c->chol_prio) {
     // the whole sweep on the context's high-priority stream: with two tries in flight
     // its chain workgroups are dispatched ahead of the other try's inverse tiles
@@ -2063,11 +1447,11 @@ gpe_ctx* gpe_create(int32_t device) {
     const char* e2 = std::getenv("GPEMU_POTRF");
     if (e2) {
       const std::string m(e2);
-      c->potrf_group = m == "group" || m == "auto";
+      c->sched.group = m == "group" || m == "auto";
       c->potrf_mode = m == "group" ? 1 : (m == "auto" ? 0 : 2);
     }
-    if (const char* eg = std::getenv("GPEMU_GROUP_P0")) c->grp_p0 = std::max(1, std::atoi(eg));
-    if (const char* eg = std::getenv("GPEMU_GROUP_STRIDE")) c->grp_stride = std::max(0, std::atoi(eg));
+    if (const char* eg = std::getenv("GPEMU_GROUP_P0")) c->sched.grp_p0 = std::max(1, std::atoi(eg));
+    if (const char* eg = std::getenv("GPEMU_GROUP_STRIDE")) c->sched.grp_stride = std::max(0, std::atoi(eg));
     if (const char* ep = std::getenv("GPEMU_CHOL_PRIO")) c->chol_prio = std::atoi(ep) != 0;
     if (const char* et = std::getenv("GPEMU_TINY")) c->tiny = std::atoi(et) != 0;
     if (const char* ed = std::getenv("GPEMU_DEBUG_SKIP_WAIT")) c->dbg_skip_wait = std::atoi(ed);
@@ -2082,11 +1466,11 @@ gpe_ctx* gpe_create(int32_t device) {
     if (const char* ec = std::getenv("GPEMU_OZAKI_CHOL_NEST_MIN")) c->oz_nest_min = std::max(256, std::atoi(ec));
     if (const char* ea = std::getenv("GPEMU_TRTRI_AHEAD")) c->tri_ahead_on = std::atoi(ea) != 0;
     if (const char* es = std::getenv("GPEMU_POTRF_SB")) {
-      c->potrf_sb = std::max(1, std::min(8, std::atoi(es)));
-      if (const char* colon = std::strchr(es, ':')) c->potrf_sb_min = std::max(0, std::atoi(colon + 1));
+      c->sched.sb = std::max(1, std::min(8, std::atoi(es)));
+      if (const char* colon = std::strchr(es, ':')) c->sched.sb_min = std::max(0, std::atoi(colon + 1));
     }
     if (const char* e3 = std::getenv("GPEMU_POTRF_W")) {
-      c->potrf_groups.clear();
+      c->sched.groups.clear();
       std::string spec(e3);
       size_t pos = 0;
       while (pos < spec.size()) {
@@ -2096,7 +1480,7 @@ gpe_ctx* gpe_create(int32_t device) {
         const size_t colon = item.find(':');
         const int w = std::atoi(item.substr(0, colon).c_str());
         const int lim = colon == std::string::npos ? 0 : std::atoi(item.substr(colon + 1).c_str());
-        if (w >= 1 && w <= 8) c->potrf_groups.push_back({w, lim});
+        if (w >= 1 && w <= 8) c->sched.groups.push_back({w, lim});
         pos = end + 1;
       }
     }

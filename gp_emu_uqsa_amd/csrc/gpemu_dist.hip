@@ -988,7 +988,7 @@ int ensure_grad(gpe_dist* h) {
   DCHK(dalloc(h, &h->dT2, (size_t)Pc * Pc, &h->shared_bytes));
   DCHK(dalloc(h, &h->cpart, (size_t)NB * (NB + 1) / 2 * (d + 3), &h->shared_bytes));
 
-  // X = L^-1 by the recursive TRTRI of the single-GPU path (gpemu.hip build_plan), level
+  // X = L^-1 by the recursive TRTRI of the single-GPU path (build_chol_plan, gpemu_chol_sched.hpp), level
   // by level (block pairs [t0, h), [h, t1) of s tile columns, s = 2, 4, ...; the
   // diagonal tiles X(t,t) = Dinv_t were kept from the sweep), on the tile rows each rank
   // owns:

@@ -1,7 +1,7 @@
 // gpemu_gemm_sched.hpp -- host side of the grouped GEMM (k_gemm, gpemu_kernels.hpp): which
 // instance a launch takes, the launch record, the descriptors of one launch, split K, the
 // XCD-aware tile order and the one place that issues k_gemm.  The single-GPU schedules
-// (gpemu.hip) and the row-block ones (gpemu_dist.hip) are both assembled from these;
+// (gpemu_chol_sched.hpp, gpemu.hip) and the row-block ones (gpemu_dist.hip) are both assembled from these;
 // tests/host/gemm_sched_check.cpp checks them without a GPU.
 #pragma once
 

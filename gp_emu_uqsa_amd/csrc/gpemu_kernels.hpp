@@ -2547,7 +2547,7 @@ static __global__ void k_scale_points(const double* X, const double* inv_delta, 
 
 // The augmented tile row of the fused Cholesky: [f H]^T as rows under the matrix
 // (TILE x n_pad, ld = TILE): Faug(p, i) = F(i, p) for p < P, rows P..127 zero.  The
-// sweep leaves (L^-1 [f H])^T there (build_plan).
+// sweep leaves (L^-1 [f H])^T there (build_chol_plan).
 static __global__ void k_aug_init(const double* F, long long ldf, int P, long long n_pad, double* Faug) {
   const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= n_pad * TILE) return;

@@ -975,7 +975,7 @@ inline hipError_t oz_product_launch(hipStream_t st, const OzConst& k, const OzPr
 // The block pairs (t0, h, t1) of the TRTRI level of span s tiles (s = 2, 4, ... while
 // s / 2 < NB; tile units of 128): X(t0:h, t0:h) and X(h:t1, h:t1) are inverted, the level fills
 // X(h:t1, t0:h).  The last pair of a level is ragged (t1 = NB) and a block without a lower
-// half has no pair.  One definition for the fp64 schedule (build_plan) and the int8 plans.
+// half has no pair.  One definition for the fp64 schedule (build_chol_plan) and the int8 plans.
 inline std::vector<std::array<int, 3>> trtri_level_pairs(int NB, int s) {
   std::vector<std::array<int, 3>> prs;
   for (int t0 = 0; t0 < NB; t0 += s) {

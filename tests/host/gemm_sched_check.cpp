@@ -53,7 +53,7 @@ static GemmProb plain(int mt, int nt, int K, int flags = 0, double beta = 0.0, i
   return p;
 }
 
-// One fused Cholesky step as build_plan assembles it: the diagonal tile's pending update in
+// One fused Cholesky step shaped as chain_step and SweepProbs::bulk (gpemu_chol_sched.hpp) assemble it: the diagonal tile's pending update in
 // quadrant blocks (K > 0), the diagonal tile, m panel tiles in two halves, then the trailing
 // update of nb columns (a lower-triangular block and the rows under it).
 static std::vector<GemmProb> fused_step(int K, int m, int nb, int rows_under) {

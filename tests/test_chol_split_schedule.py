@@ -1,126 +1,52 @@
-"""Host-side check of the split Cholesky schedule (build_plan's sweep(o, NC, NR), gpemu.hip): a
-Python mirror of its column bookkeeping -- the groups, the super-blocks with their lazy far
-updates and the balanced bulk segments -- for the per-step (fused) and the group launches.
-
-sweep(NC, NR) here lists, launch by launch, the factored columns with their pending sources and
-the bulk updates (columns [a, b) by columns [g0, g0 + k)), in local tile columns.  Checked for
-NB = 8 ... 130, the default widths / super-blocks and widths 1-8:
+"""Host-side check of the split Cholesky schedule (add_sweep(o, NC, NR), gpemu_chol_sched.hpp), on
+the launches the real builder makes: tests/host/chol_sched_check.cpp builds the plan of every size
+and, with --emit, lists launch by launch the factored columns with their pending sources and the
+bulk updates (columns [a, b) by columns [g0, g0 + k)) as it reads them off the descriptors -- the
+target columns from the C pointer, the source column from the A pointer, the width from K -- in
+the sweep's local tile columns.  Checked here for NB = 8 ... 130, the default widths /
+super-blocks and widths 1-8, for the per-step (fused) and the group launches:
   phase A = sweep(h, NB) (h the largest power of two below NB): no column >= h is written, and
       every column < h has received every earlier column exactly once when it is factored, each
       from a column factored before;
   phase C = sweep(NB - h, NB - h) is the unsplit schedule of NB - h columns: the same function
-      the whole factorisation uses, which passes the same check, and whose groups do not depend
-      on the origin.
+      the whole factorisation (NB, NB) uses, which passes the same check;
+  the nested split's sweeps (q, NB) and (h - q, NB - q), q = h / 2, where h is a multiple of 4.
 """
+import subprocess
+
 import numpy as np
 import pytest
 
-DEFAULT = ([(4, 48), (2, 24)], 2, 80)   # potrf_groups, potrf_sb, potrf_sb_min
+from test_chol_sched_host import build_check
+
+DEFAULT = ([(4, 48), (2, 24)], 2, 80)   # CholSchedParams: groups, sb, sb_min
 
 
-def sweep(NC, NR, groups, sb, sb_min):
-    """-> (fused launches, group launches); a launch is a list of ("bulk", a, b, g0, k) and
-    ("factor", t, p0) entries in an order its waits allow."""
-    gs, g = [], 0
-    while g < NC:
-        gs.append(g)
-        w = 1
-        for wd, lim in groups:
-            if NR - g > lim:
-                w = wd
-                break
-        g += max(1, min(w, NC - g))
-    gs.append(NC)
-    ng = len(gs) - 1
-    sbs, sbe, src0 = [0] * ng, [0] * ng, [0] * ng
-    cur = cnt = 0
-    for gi in range(ng):
-        w = gs[gi + 1] - gs[gi]
-        if gi <= 1 or w < 2 or w != gs[gi] - gs[gi - 1] or cnt >= sb or NR - gs[gi] <= sb_min:
-            cur, cnt = gs[gi], 0
-        sbs[gi] = cur
-        cnt += 1
-    for gi in range(ng - 1, -1, -1):
-        sbe[gi] = sbe[gi + 1] if gi + 1 < ng and sbs[gi + 1] == sbs[gi] else gs[gi + 1]
-    for gi in range(1, ng):
-        src0[gi] = sbs[gi - 1] if sbs[gi] == gs[gi] else gs[gi - 1]
+@pytest.fixture(scope="module")
+def sched_check(tmp_path_factory):
+    return build_check(tmp_path_factory)
 
-    def cost(j, k):
-        return float(NR - j) * k
 
-    segs = [[] for _ in range(ng)]   # (a, b, g0, k): k source columns from g0
-    for gi in range(1, ng):
-        if gs[gi + 1] < sbe[gi]:
-            segs[gi].append((gs[gi + 1], sbe[gi], src0[gi], gs[gi] - src0[gi]))
-    for gi in range(1, ng):
-        if sbs[gi] != gs[gi]:
-            continue
-        s0, s1, se = sbs[gi - 1], gs[gi], sbe[gi]
-        kf = s1 - s0
-        mem = [gj for gj in range(gi, ng) if sbs[gj] == sbs[gi]]
-        fixed = []
-        for gj in mem:
-            kb = gs[gj] - src0[gj]
-            fx = sum(cost(j, kb) for j in range(gs[gj] + 1, gs[gj + 1]))
-            fx += sum(cost(j, k) for a, b, _, k in segs[gj] for j in range(a, b))
-            fixed.append(fx)
-        tot = sum(fixed) + sum(cost(j, kf) for j in range(se, NC))
-        j = se
-        for m, gj in enumerate(mem):
-            want = max(0.0, tot / len(mem) - fixed[m])
-            a, got = j, 0.0
-            while j < NC and (m + 1 == len(mem) or got + 0.5 * cost(j, kf) <= want):
-                got += cost(j, kf)
-                j += 1
-            if j > a:
-                segs[gj].append((a, j, s0, kf))
-
-    fused, grp = [], []
-    for gi in range(ng):
-        gb, ge = gs[gi], gs[gi + 1]
-        W1 = ge - gb
-        part = [[] for _ in range(W1)]
-        if gi > 0:
-            kb = gb - src0[gi]
-            load = [float(NR - (gb + h + 1)) * kb if h + 1 < W1 else 0.0 for h in range(W1)]
-            tot = sum(load)
-            cols = []
-            for si, (a, b, _, k) in enumerate(segs[gi]):
-                for j in range(a, b):
-                    cols.append((j, si))
-                    tot += float(NR - j) * k
-            u, cum = 0, 0.0
-            for h in range(W1):
-                cum += load[h]
-                target = tot * (h + 1) / W1
-                while u < len(cols):
-                    j, si = cols[u]
-                    _, _, g0, k = segs[gi][si]
-                    cj = float(NR - j) * k
-                    if h < W1 - 1 and cum + 0.5 * cj > target:
-                        break
-                    cum += cj
-                    part[h].append((j, j + 1, g0, k))
-                    u += 1
-            assert u == len(cols)
-        for h in range(W1):
-            t = gb + h
-            launch = [("factor", t, src0[gi] if h == 0 else gb)]
-            if gi > 0:
-                if h + 1 < W1:
-                    launch.append(("bulk", t + 1, t + 2, src0[gi], gb - src0[gi]))
-                launch += [("bulk",) + sg for sg in part[h]]
-            fused.append(launch)
-        if W1 < 2:
-            grp.append(fused[-1])
-            continue
-        launch = []
-        if gi > 0:
-            launch += [("bulk", gb + h, gb + h + 1, src0[gi], gb - src0[gi]) for h in range(1, W1)]
-        launch += [("factor", gb + h, src0[gi] if h == 0 else gb) for h in range(W1)]
-        launch += [("bulk",) + sg for sg in segs[gi]]
-        grp.append(launch)
-    return fused, grp
+def emitted(exe, env, ci):
+    """{(NB, NC, NR): [per-step launches, group launches]} of configuration ci; a launch is a list
+    of ("bulk", a, b, g0, k) and ("factor", t, p0) entries in its problems' order."""
+    run = subprocess.run([exe, "--emit", str(ci)], capture_output=True, text=True, env=env)
+    assert run.returncode == 0, run.stdout[-2000:] + run.stderr[-4000:]
+    out = {}
+    for line in run.stdout.splitlines():
+        head, *ls = line.split(" |")
+        tag, cfg, NB, NC, NR, grp = head.split()
+        assert tag == "SWEEP" and int(cfg) == ci
+        launches = []
+        for l in ls:
+            tok, launch, i = l.split(), [], 0
+            while i < len(tok):
+                n = 3 if tok[i] == "F" else 5
+                launch.append(("factor" if tok[i] == "F" else "bulk",) + tuple(int(x) for x in tok[i + 1:i + n]))
+                i += n
+            launches.append(launch)
+        out.setdefault((int(NB), int(NC), int(NR)), [None, None])[int(grp)] = launches
+    return out
 
 
 def check(launches, NC):
@@ -151,13 +77,17 @@ CONFIGS = ([DEFAULT] + [([(w, 0)], 2, 80) for w in range(1, 9)] + [([(w, 0)], 1,
 
 
 @pytest.mark.parametrize("cfg", CONFIGS, ids=lambda c: f"w{c[0]}-sb{c[1]}-{c[2]}")
-def test_split_schedule(cfg):
+def test_split_schedule(sched_check, cfg):
+    got = emitted(*sched_check, CONFIGS.index(cfg))   # (chol_sched_check.cpp's coverage_configs: the same list)
     for NB in range(8, 131):
         h = 1
         while 2 * h < NB:
             h *= 2
-        for NC, NR in ((h, NB), (NB - h, NB - h), (NB, NB)):   # phase A, phase C, unsplit
-            fused, grp = sweep(NC, NR, *cfg)
+        sweeps = [(h, NB), (NB - h, NB - h), (NB, NB)]   # phase A, phase C, unsplit
+        if h % 4 == 0:
+            sweeps += [(h // 2, NB), (h - h // 2, NB - h // 2)]   # the nested split's
+        for NC, NR in sweeps:
+            fused, grp = got[(NB, NC, NR)]
             check(fused, NC)
             check(grp, NC)
 
