@@ -20,13 +20,14 @@
 #include <cstring>
 #include <limits>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/gpemu.h"
 #include "gpemu_kernels.hpp"
 #include "gpemu_gemm_sched.hpp"
 #include "gpemu_chol_sched.hpp"
-#include "gpemu_small.hpp"
+#include "gpemu_objective.hpp"   // (with gpemu_small.hpp)
 #include "gpemu_tiny.hpp"
 #include "gpemu_snb.hpp"
 #include "gpemu_ozaki.hpp"
@@ -445,16 +446,22 @@ static bool onel_lds_attr(int tiny_bytes, int snb_bytes) {
          hipFuncSetAttribute((const void*)k_snb<32, FAM>, at, snb_bytes) == hipSuccess;
 }
 
-// The correlation family a.fam selects the instantiation (FAM_GAUSS: the kernels as they
-// were before the Matern families).
+// f(std::integral_constant<int, FAM>()) for the correlation family fam (a FAM_*; any other
+// value runs FAM_GAUSS, the kernels as they were before the Matern families): the one place
+// where a run-time family becomes a kernel's template argument
+template <class F>
+static void with_fam(int fam, F&& f) {
+  if (fam == FAM_MATERN32) f(std::integral_constant<int, FAM_MATERN32>());
+  else if (fam == FAM_MATERN52) f(std::integral_constant<int, FAM_MATERN52>());
+  else f(std::integral_constant<int, FAM_GAUSS>());
+}
+
 int launch_pairs(gpe_ctx* c, const PairArgs& a, int nblocks) {
   if (a.fam != FAM_GAUSS && a.fam != FAM_MATERN32 && a.fam != FAM_MATERN52)
     return fail(c, GPE_ERR_ARG, "internal error: bad correlation family");
   if (a.d > 32) {   // any d: coordinates staged through LDS in chunks of 32
     const dim3 g(nblocks), b(256);
-    if (a.fam == FAM_MATERN32) hipLaunchKernelGGL(k_pairs_wide<FAM_MATERN32>, g, b, 0, c->stream, a);
-    else if (a.fam == FAM_MATERN52) hipLaunchKernelGGL(k_pairs_wide<FAM_MATERN52>, g, b, 0, c->stream, a);
-    else hipLaunchKernelGGL(k_pairs_wide<FAM_GAUSS>, g, b, 0, c->stream, a);
+    with_fam(a.fam, [&](auto F) { hipLaunchKernelGGL(k_pairs_wide<decltype(F)::value>, g, b, 0, c->stream, a); });
     HIPCHK(c, hipGetLastError());
     return GPE_OK;
   }
@@ -468,9 +475,7 @@ int launch_pairs(gpe_ctx* c, const PairArgs& a, int nblocks) {
   PairArgs a2 = a;
   while (a2.csplit < 4 && nblocks * a2.csplit * 2 <= 512) a2.csplit *= 2;
   const dim3 g(nblocks * a2.csplit), b(256);
-  if (a.fam == FAM_MATERN32) launch_pairs_fam<FAM_MATERN32>(dm, g, b, c->stream, a2);
-  else if (a.fam == FAM_MATERN52) launch_pairs_fam<FAM_MATERN52>(dm, g, b, c->stream, a2);
-  else launch_pairs_fam<FAM_GAUSS>(dm, g, b, c->stream, a2);
+  with_fam(a.fam, [&](auto F) { launch_pairs_fam<decltype(F)::value>(dm, g, b, c->stream, a2); });
   HIPCHK(c, hipGetLastError());
   return GPE_OK;
 }
@@ -629,13 +634,8 @@ int ensure_fact(gpe_ctx* c, Fact& F, long long n_pad) {
 // scaled points for the training set
 int scale_training(gpe_ctx* c, const double* delta) {
   CHK(ensure_pinned(c, (size_t)c->d + 64));
-  for (int k = 0; k < c->d; ++k) {
-    // zero or NaN length scale: the reference's covariance is NaN there and its Cholesky
-    // raises LinAlgError (-> `return None`, _emulatoroptimise.py:374-376, :489-491)
-    if (!(delta[k] > 0.0) && !(delta[k] < 0.0))
-      return fail(c, GPE_NOT_PD, "length scale delta[" + std::to_string(k) + "] is zero or NaN");
-    c->hpin[k] = 1.0 / delta[k];
-  }
+  const int bad = inv_length_scales(delta, c->d, c->hpin);
+  if (bad >= 0) return fail(c, GPE_NOT_PD, bad_length_scale(bad));
   HIPCHK(c, hipMemcpyAsync(c->dinvdelta, c->hpin, c->d * sizeof(double), hipMemcpyHostToDevice,
                            c->stream));
   const long long tot = c->n_pad * c->d;
@@ -643,29 +643,6 @@ int scale_training(gpe_ctx* c, const double* delta) {
                      c->dX, c->dinvdelta, c->d, (int)c->n, (int)c->n_pad, c->dXw);
   HIPCHK(c, hipGetLastError());
   return GPE_OK;
-}
-
-// A kernel code is the nugget convention (bit 0) OR-ed with the correlation family
-// (GPE_KERNEL_MATERN32 / GPE_KERNEL_MATERN52, 0 = Gaussian).
-constexpr int KERNEL_FAMILY_BITS = GPE_KERNEL_MATERN32 | GPE_KERNEL_MATERN52;
-inline bool kernel_ok(int kernel) {
-  return (kernel & ~(KERNEL_FAMILY_BITS | GPE_KERNEL_ALT_NUG)) == 0 &&
-         (kernel & KERNEL_FAMILY_BITS) != KERNEL_FAMILY_BITS;
-}
-inline bool kernel_alt(int kernel) { return (kernel & GPE_KERNEL_ALT_NUG) != 0; }
-// the device kernels' FAM_* of a valid kernel code
-inline int kernel_fam(int kernel) {
-  return (kernel & GPE_KERNEL_MATERN32) ? FAM_MATERN32 : (kernel & GPE_KERNEL_MATERN52) ? FAM_MATERN52 : FAM_GAUSS;
-}
-
-void kernel_consts(int kernel, double nu, bool predict, double* coff, double* cdiag) {
-  if (kernel_alt(kernel)) {
-    *coff = 1.0;
-    *cdiag = predict ? 1.0 + nu * nu : 1.0;
-  } else {
-    *coff = 1.0 - nu;
-    *cdiag = predict ? 1.0 : 1.0 - nu;
-  }
 }
 
 // K-build of the training matrix into dA (lower tiles)
@@ -1514,6 +1491,7 @@ gpe_ctx* gpe_create(int32_t device) {
          hipFuncSetAttribute((const void*)k_xasm, hipFuncAttributeMaxDynamicSharedMemorySize,
                              (int)(DB_LDS_DOUBLES * sizeof(double))) == hipSuccess;
     const int tl = (G_LDS_LAUNCH_DOUBLES + 2 * TILE * TINY_ZP) * (int)sizeof(double);
+    // every family's instances, not one chosen at run time as with_fam does
     ok = ok && onel_lds_attr<FAM_GAUSS>(tl, SNB_LDS_DOUBLES * 8) && onel_lds_attr<FAM_MATERN32>(tl, SNB_LDS_DOUBLES * 8) &&
          onel_lds_attr<FAM_MATERN52>(tl, SNB_LDS_DOUBLES * 8);
     if (!ok) c->err = "hipFuncSetAttribute(max dynamic LDS) failed";
@@ -1665,231 +1643,58 @@ int gpe_gemm_stats(gpe_ctx* c, double* ms_out, double* launches_out, double* flo
   return GPE_OK;
 }
 
-// The objective of a training set of at most 128 points (gpemu_tiny.hpp): ONE launch of
-// k_tiny (workgroup 0: L, X = L^-1, Z, Gram and, with the gradient, the q x q algebra and W;
-// nine helper workgroups: the K-build and the contraction of M = A^-1 - W W^T), which
-// writes Gram, log|L|, the failed column and the d + 3 sums straight into the pinned host
-// buffer; the host's small_from_gram / small_grad (the general path's) give the LLH and the
-// gradient.  No memset (the sync words count up over the calls; zeroed only after a call
-// that did not end cleanly) and no copy.
-int tiny_objective(gpe_ctx* c, bool gp4ml, int kernel, const double* hp, int n_hp, bool fitnug, double nu,
-                   double s2, double rscale, bool want_grad, double* llh_out, double* grad_out, double* sigma2_out) {
-  const int d = c->d, q = c->q, P = q + 1;
-  TinyArgs a;
-  for (int k = 0; k < d; ++k) {
-    // as scale_training: a zero or NaN length scale is the reference's LinAlgError
-    if (!(hp[k] > 0.0) && !(hp[k] < 0.0))
-      return fail(c, GPE_NOT_PD, "length scale delta[" + std::to_string(k) + "] is zero or NaN");
-    a.invd[k] = 1.0 / hp[k];
-  }
+}  // extern "C"
+
+namespace {
+
+// What the two one-launch objectives (tiny_objective, snb_objective) do before their own
+// workspace and sync-word bookkeeping: the length scales (as scale_training), the cached state
+// an evaluation invalidates, the second stream's drain, the pinned result buffer of `pinned`
+// doubles, and the fields TinyArgs and SnbArgs have in common.
+template <class Args>
+int onel_prologue(gpe_ctx* c, const ObjArgs& o, int kernel, const double* hp, bool want_grad, size_t pinned, Args& a) {
+  const int d = c->d;
+  const int bad = inv_length_scales(hp, d, a.invd);
+  if (bad >= 0) return fail(c, GPE_NOT_PD, bad_length_scale(bad));
   for (int k = d; k < TINY_DM; ++k) a.invd[k] = 0.0;
   c->linv_valid = false;
   c->zaug_valid = false;
   c->tr.xclear();
   HIPCHK(c, hipStreamSynchronize(c->stream2));   // (a failed sweep's leftovers, as factor_and_invert)
-  constexpr size_t tiny_doubles = 36 * DB_BS + TILE * 32;
-  if (!c->dtiny) CHK(dalloc(c, &c->dtiny, tiny_doubles));
-  CHK(ensure_pinned(c, (size_t)P * P + 2 * d + 64 + TINY_NH * 64));
-  if (c->tiny_dirty || c->tiny_ek > (1 << 26)) {   // the sync words and the abort flag
-    HIPCHK(c, hipMemsetAsync(c->dinfo + 1, 0, (TINY_SYNC_INTS + 1) * sizeof(int), c->stream));
-    c->tiny_ek = c->tiny_eg = 0;
-    c->tiny_dirty = false;
-  }
-  ev_rec(c, 0);
-  a.X = c->dX; a.F = c->dF;
-  a.r = (c->has_r && rscale != 0.0) ? c->dr : nullptr;
-  a.rdiag = (gp4ml && !kernel_alt(kernel) && c->has_r) ? c->dr : nullptr;
-  a.xw = c->dXw; a.L = c->tr.A; a.Xo = c->tr.B; a.Z = c->dZ; a.small = c->hpin; a.abort_flag = c->dinfo + 1 + TINY_SYNC_INTS;
-  a.K = c->tr.A; a.Xp = c->dtiny; a.Wg = c->dtiny + 36 * DB_BS; a.sync = c->dinfo + 1;
-  a.n = (int)c->n; a.d = d; a.P = P; a.want_grad = want_grad ? 1 : 0; a.mucm = gp4ml ? 0 : 1;
-  a.ek = ++c->tiny_ek;
-  a.eg = want_grad ? ++c->tiny_eg : c->tiny_eg;
-  a.s2 = s2; a.rscale = rscale;
+  CHK(ensure_pinned(c, pinned));
+  a.X = c->dX; a.F = c->dF; a.xw = c->dXw; a.small = c->hpin;
+  a.r = (c->has_r && o.rscale != 0.0) ? c->dr : nullptr;
+  a.rdiag = (o.gp4ml && !kernel_alt(kernel) && c->has_r) ? c->dr : nullptr;
+  a.n = (int)c->n; a.d = d; a.P = c->q + 1; a.want_grad = want_grad ? 1 : 0; a.mucm = o.gp4ml ? 0 : 1;
+  a.s2 = o.s2; a.rscale = o.rscale;
   a.dbg_skip = c->dbg_skip_wait;
   a.tag = ++c->onel_tag;
-  kernel_consts(kernel, nu, true, &a.coff, &a.cdiag);
+  kernel_consts(kernel, o.nu, true, &a.coff, &a.cdiag);
   // (the Matern families' pivot floor, as factor_and_invert's k_pivot_floor)
   a.floor_rel = 4.0 * (double)c->n_pad * std::numeric_limits<double>::epsilon();
-  const size_t lds = (G_LDS_LAUNCH_DOUBLES + 2 * TILE * TINY_ZP) * sizeof(double);
-  c->hpin[P * P + 1] = -2.0;   // (workgroup 0 overwrites it on every path; -2: it did not)
-  c->tiny_dirty = true;   // (until this call has ended cleanly: its sync words are then consistent)
-  const int fam = kernel_fam(kernel);
-  if (fam == FAM_MATERN32) launch_tiny_fam<FAM_MATERN32>(d, lds, c->stream, a);
-  else if (fam == FAM_MATERN52) launch_tiny_fam<FAM_MATERN52>(d, lds, c->stream, a);
-  else launch_tiny_fam<FAM_GAUSS>(d, lds, c->stream, a);
-  HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipStreamSynchronize(c->stream));   // (the kernel wrote its outputs to hpin)
-  const int info = (int)c->hpin[P * P + 1];
-  if (info < 0) {   // a wait ran out (-1) or workgroup 0 never reported (-2): not the matrix's doing
-    c->err = info == -1 ? std::string("k_tiny: a workgroup wait timed out") : "k_tiny: workgroup 0 did not complete";
-    return GPE_ERR_HIP;   // (tiny_dirty stays set: the next call zeroes the sync words)
-  }
-  if (info != 0) {
-    c->err = "matrix not positive definite (pivot " + std::to_string(info) + ")";
-    return GPE_NOT_PD;
-  }
-  const double logdetA = 2.0 * c->hpin[P * P];
-  std::vector<double> G(c->hpin, c->hpin + (size_t)P * P);
-  SmallAlgebra sa = small_from_gram(G, P);
-  if (!sa.ok) {
-    c->err = "H^T A^-1 H not positive definite";
-    return GPE_NOT_PD;
-  }
-  const double n = (double)c->n;
-  double llh, sig2, cfac, gscale;
-  if (gp4ml) {
-    llh = 0.5 * (sa.quad + logdetA + sa.logdetQ + (n - q) * std::log(2.0 * M_PI));
-    sig2 = s2;
-    cfac = 1.0;
-    gscale = s2;
-  } else {
-    sig2 = sa.quad / (n - q - 2.0);
-    llh = 0.5 * ((n - q) * std::log(sig2) + logdetA + sa.logdetQ);
-    cfac = (n - q) / (sig2 * (n - q - 2.0));
-    gscale = sig2;
-  }
-  *llh_out = llh;
-  if (sigma2_out) *sigma2_out = sig2;
-  if (want_grad) {
-    // the device's own Cholesky of Q (same arithmetic) refusing a Q the host's accepted
-    if (c->hpin[P * P + 2 + d + 3] != 0.0) {
-      c->err = "H^T A^-1 H not positive definite";
-      return GPE_NOT_PD;
-    }
-    (void)cfac;   // (the device's T2 carries sqrt(cfac))
-    double red[TINY_DM + 3];
-    const double* part = c->hpin + (size_t)P * P + 2 + d + 4;
-    for (int h = 0; h < TINY_NH; ++h)   // every helper's sums are this call's (a helper that gave up a wait never tags them)
-      if (part[h * 64 + 63] != a.tag) {
-        c->err = "k_tiny: helper " + std::to_string(h) + " did not finish (a wait timed out)";
-        return GPE_ERR_HIP;
-      }
-    for (int k = 0; k < d + 3; ++k) {   // the helpers' partials in helper order
-      double v = 0.0;
-      for (int h = 0; h < TINY_NH; ++h) v += part[h * 64 + k];
-      red[k] = v;
-    }
-    small_grad(red, d, kernel_alt(kernel), nu, fitnug, gp4ml, gscale, s2, a.coff, a.cdiag, n_hp,
-               grad_out, a.rdiag != nullptr);
-  }
-  if (c->prof) {   // (one phase: the whole evaluation)
-    ev_rec(c, 7);
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    float ms = 0.f;
-    (void)hipEventElapsedTime(&ms, c->ev[0], c->ev[7]);
-    for (int i = 0; i < 8; ++i) c->phase_ms[i] = 0.0;
-    c->phase_ms[6] = ms;
-  }
-  c->tiny_dirty = false;
   return GPE_OK;
 }
 
-// The objective of 2-4 tiles (128 < n <= 512, gpemu_snb.hpp): ONE launch of k_snb
-// (workgroup 0: the diagonal factors, the Gram and the q x q algebra; SNB_NH = 48 helper workgroups:
-// K-build, panels and updates with [f H]^T as an augmented row, X = L^-1, W and the
-// contraction), outputs straight into the pinned host buffer; the host's small_from_gram /
-// small_grad as in tiny_objective.
-int snb_objective(gpe_ctx* c, bool gp4ml, int kernel, const double* hp, int n_hp, bool fitnug, double nu,
-                  double s2, double rscale, bool want_grad, double* llh_out, double* grad_out, double* sigma2_out) {
-  const int d = c->d, q = c->q, P = q + 1, NB = c->NB;
-  const long long np = c->n_pad;
-  SnbArgs a;
-  for (int k = 0; k < d; ++k) {
-    if (!(hp[k] > 0.0) && !(hp[k] < 0.0))
-      return fail(c, GPE_NOT_PD, "length scale delta[" + std::to_string(k) + "] is zero or NaN");
-    a.invd[k] = 1.0 / hp[k];
-  }
-  for (int k = d; k < TINY_DM; ++k) a.invd[k] = 0.0;
-  c->linv_valid = false;
-  c->zaug_valid = false;
-  c->tr.xclear();
-  HIPCHK(c, hipStreamSynchronize(c->stream2));
-  if (c->snb_np != np) {
-    c->snb_np = 0;
-    CHK(dalloc(c, &c->dsnb, (size_t)np * np + 3 * 32 * (size_t)np + TINY_DM * TINY_ZP + TILE * TILE));
-    c->snb_np = np;
-  }
-  CHK(ensure_pinned(c, (size_t)P * P + NB + 2 * d + 64 + SNB_NH * 64));
-  if (c->snb_dirty || c->snb_hc > (1 << 24)) {
-    HIPCHK(c, hipMemsetAsync(c->dinfo + 8, 0, (SNB_SYNC_INTS + 1) * sizeof(int), c->stream));
-    c->snb_hc = c->snb_mf = 0;
-    c->snb_dirty = false;
-  }
-  ev_rec(c, 0);
-  a.X = c->dX; a.F = c->dF;
-  a.r = (c->has_r && rscale != 0.0) ? c->dr : nullptr;
-  a.rdiag = (gp4ml && !kernel_alt(kernel) && c->has_r) ? c->dr : nullptr;
-  a.xw = c->dXw; a.A = c->tr.A; a.Lb = c->tr.B; a.Xt = c->dsnb;
-  a.Zt = a.Xt + np * np; a.Zo = a.Zt + 32 * np; a.Wg = a.Zo + 32 * np; a.T2g = a.Wg + 32 * np;
-  a.Xscr = a.T2g + TINY_DM * TINY_ZP;
-  a.small = c->hpin; a.sync = c->dinfo + 8; a.abort_flag = c->dinfo + 8 + SNB_SYNC_INTS;
-  a.n = (int)c->n; a.np = (int)np; a.NB = NB; a.d = d; a.P = P; a.want_grad = want_grad ? 1 : 0;
-  a.mucm = gp4ml ? 0 : 1;
-  a.hcb = c->snb_hc; a.mfb = c->snb_mf;
-  a.s2 = s2; a.rscale = rscale;
-  a.dbg_skip = c->dbg_skip_wait;
-  a.tag = ++c->onel_tag;
-  kernel_consts(kernel, nu, true, &a.coff, &a.cdiag);
-  // (the Matern families' pivot floor, as factor_and_invert's k_pivot_floor)
-  a.floor_rel = 4.0 * (double)c->n_pad * std::numeric_limits<double>::epsilon();
-  const size_t lds = SNB_LDS_DOUBLES * sizeof(double);
-  c->hpin[P * P + NB] = -2.0;   // (workgroup 0 overwrites it on every path; -2: it did not)
-  c->snb_dirty = true;   // (until this call has ended cleanly)
-  const int fam = kernel_fam(kernel);
-  if (fam == FAM_MATERN32) launch_snb_fam<FAM_MATERN32>(d, lds, c->stream, a);
-  else if (fam == FAM_MATERN52) launch_snb_fam<FAM_MATERN52>(d, lds, c->stream, a);
-  else launch_snb_fam<FAM_GAUSS>(d, lds, c->stream, a);
+// What they share after the launch: the kernel's outputs are in the pinned buffer r reads
+// (OneLaunchResult, gpemu_objective.hpp) once the stream has drained; the host's
+// small_from_gram / objective_value / objective_grad (the general path's) give the LLH and
+// the gradient.  One profiling phase: the whole evaluation.
+int onel_epilogue(gpe_ctx* c, const ObjArgs& o, int kernel, int n_hp, bool want_grad, const OneLaunchResult& r,
+                  bool std_r, double* llh_out, double* grad_out, double* sigma2_out) {
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipStreamSynchronize(c->stream));   // (the kernel wrote its outputs to hpin)
-  const double* h = c->hpin;
-  const int info = (int)h[P * P + NB];
-  if (info != 0) {
-    c->err = info == -1   ? std::string("k_snb: a workgroup wait timed out")
-             : info < 0 ? std::string("k_snb: workgroup 0 did not complete")
-                        : "matrix not positive definite (pivot " + std::to_string(info) + ")";
-    return info < 0 ? GPE_ERR_HIP : GPE_NOT_PD;
-  }
-  double logdetA = 0.0;
-  for (int k = 0; k < NB; ++k) logdetA += h[P * P + k];
-  logdetA *= 2.0;
-  std::vector<double> G(h, h + (size_t)P * P);
-  SmallAlgebra sa = small_from_gram(G, P);
-  if (!sa.ok) {
-    c->err = "H^T A^-1 H not positive definite";
-    return GPE_NOT_PD;
-  }
-  const double n = (double)c->n;
-  double llh, sig2, gscale;
-  if (gp4ml) {
-    llh = 0.5 * (sa.quad + logdetA + sa.logdetQ + (n - q) * std::log(2.0 * M_PI));
-    sig2 = s2;
-    gscale = s2;
-  } else {
-    sig2 = sa.quad / (n - q - 2.0);
-    llh = 0.5 * ((n - q) * std::log(sig2) + logdetA + sa.logdetQ);
-    gscale = sig2;
-  }
-  *llh_out = llh;
-  if (sigma2_out) *sigma2_out = sig2;
-  if (want_grad) {
-    if (h[P * P + NB + 1 + d + 3] != 0.0) {
-      c->err = "H^T A^-1 H not positive definite";
-      return GPE_NOT_PD;
-    }
+  CHK(r.status(&c->err));   // (on failure the caller's dirty flag stays set: the next call zeroes the sync words)
+  const SmallAlgebra sa = small_from_gram(std::vector<double>(r.h, r.h + (size_t)r.P * r.P), r.P);
+  if (!sa.ok) return fail(c, GPE_NOT_PD, Q_NOT_PD);
+  const ObjValue v = objective_value(sa, r.logdetA(), (double)c->n, c->q, o.gp4ml, o.s2);
+  *llh_out = v.llh;
+  if (sigma2_out) *sigma2_out = v.sig2;
+  if (want_grad) {   // (the device's T2 carries sqrt(cfac))
+    // the device's own Cholesky of Q (same arithmetic) refusing a Q the host's accepted
+    if (r.q_refused()) return fail(c, GPE_NOT_PD, Q_NOT_PD);
     double red[TINY_DM + 3];
-    const double* part = h + (size_t)P * P + NB + 1 + d + 4;
-    for (int g = 0; g < SNB_NH; ++g)   // every helper's sums are this call's
-      if (part[g * 64 + 63] != a.tag) {
-        c->err = "k_snb: helper " + std::to_string(g) + " did not finish (a wait timed out)";
-        return GPE_ERR_HIP;
-      }
-    for (int k = 0; k < d + 3; ++k) {   // the helpers' partials in helper order
-      double v = 0.0;
-      for (int g = 0; g < SNB_NH; ++g) v += part[g * 64 + k];
-      red[k] = v;
-    }
-    small_grad(red, d, kernel_alt(kernel), nu, fitnug, gp4ml, gscale, s2, a.coff, a.cdiag, n_hp,
-               grad_out, a.rdiag != nullptr);
+    CHK(r.sums(red, &c->err));
+    objective_grad(red, r.d, kernel, o.nu, o.fitnug, o.gp4ml, v.gscale, o.s2, n_hp, grad_out, std_r);
   }
   if (c->prof) {
     ev_rec(c, 7);
@@ -1899,12 +1704,84 @@ int snb_objective(gpe_ctx* c, bool gp4ml, int kernel, const double* hp, int n_hp
     for (int i = 0; i < 8; ++i) c->phase_ms[i] = 0.0;
     c->phase_ms[6] = ms;
   }
+  return GPE_OK;
+}
+
+// The objective of a training set of at most 128 points (gpemu_tiny.hpp): ONE launch of
+// k_tiny (workgroup 0: L, X = L^-1, Z, Gram and, with the gradient, the q x q algebra and W;
+// nine helper workgroups: the K-build and the contraction of M = A^-1 - W W^T), which
+// writes Gram, log|L|, the failed column and the d + 3 sums straight into the pinned host
+// buffer (onel_epilogue).  No memset (the sync words count up over the calls; zeroed only
+// after a call that did not end cleanly) and no copy.
+int tiny_objective(gpe_ctx* c, const ObjArgs& o, int kernel, const double* hp, int n_hp, bool want_grad,
+                   double* llh_out, double* grad_out, double* sigma2_out) {
+  const int d = c->d, P = c->q + 1;
+  TinyArgs a;
+  CHK(onel_prologue(c, o, kernel, hp, want_grad, (size_t)P * P + 2 * d + 64 + TINY_NH * 64, a));
+  constexpr size_t tiny_doubles = 36 * DB_BS + TILE * 32;
+  if (!c->dtiny) CHK(dalloc(c, &c->dtiny, tiny_doubles));
+  if (c->tiny_dirty || c->tiny_ek > (1 << 26)) {   // the sync words and the abort flag
+    HIPCHK(c, hipMemsetAsync(c->dinfo + 1, 0, (TINY_SYNC_INTS + 1) * sizeof(int), c->stream));
+    c->tiny_ek = c->tiny_eg = 0;
+    c->tiny_dirty = false;
+  }
+  ev_rec(c, 0);
+  a.L = c->tr.A; a.Xo = c->tr.B; a.Z = c->dZ; a.abort_flag = c->dinfo + 1 + TINY_SYNC_INTS;
+  a.K = c->tr.A; a.Xp = c->dtiny; a.Wg = c->dtiny + 36 * DB_BS; a.sync = c->dinfo + 1;
+  a.ek = ++c->tiny_ek;
+  a.eg = want_grad ? ++c->tiny_eg : c->tiny_eg;
+  const size_t lds = (G_LDS_LAUNCH_DOUBLES + 2 * TILE * TINY_ZP) * sizeof(double);
+  c->hpin[P * P + 1] = -2.0;   // (workgroup 0 overwrites it on every path; -2: it did not)
+  c->tiny_dirty = true;   // (until this call has ended cleanly: its sync words are then consistent)
+  with_fam(kernel_fam(kernel), [&](auto F) { launch_tiny_fam<decltype(F)::value>(d, lds, c->stream, a); });
+  CHK(onel_epilogue(c, o, kernel, n_hp, want_grad, OneLaunchResult{c->hpin, P, d, 1, TINY_NH, a.tag, "k_tiny"},
+                    a.rdiag != nullptr, llh_out, grad_out, sigma2_out));
+  c->tiny_dirty = false;
+  return GPE_OK;
+}
+
+// The objective of 2-4 tiles (128 < n <= 512, gpemu_snb.hpp): ONE launch of k_snb
+// (workgroup 0: the diagonal factors, the Gram and the q x q algebra; SNB_NH = 48 helper workgroups:
+// K-build, panels and updates with [f H]^T as an augmented row, X = L^-1, W and the
+// contraction), outputs straight into the pinned host buffer (onel_epilogue).
+int snb_objective(gpe_ctx* c, const ObjArgs& o, int kernel, const double* hp, int n_hp, bool want_grad,
+                  double* llh_out, double* grad_out, double* sigma2_out) {
+  const int d = c->d, P = c->q + 1, NB = c->NB;
+  const long long np = c->n_pad;
+  SnbArgs a;
+  CHK(onel_prologue(c, o, kernel, hp, want_grad, (size_t)P * P + NB + 2 * d + 64 + SNB_NH * 64, a));
+  if (c->snb_np != np) {
+    c->snb_np = 0;
+    CHK(dalloc(c, &c->dsnb, (size_t)np * np + 3 * 32 * (size_t)np + TINY_DM * TINY_ZP + TILE * TILE));
+    c->snb_np = np;
+  }
+  if (c->snb_dirty || c->snb_hc > (1 << 24)) {
+    HIPCHK(c, hipMemsetAsync(c->dinfo + 8, 0, (SNB_SYNC_INTS + 1) * sizeof(int), c->stream));
+    c->snb_hc = c->snb_mf = 0;
+    c->snb_dirty = false;
+  }
+  ev_rec(c, 0);
+  a.A = c->tr.A; a.Lb = c->tr.B; a.Xt = c->dsnb;
+  a.Zt = a.Xt + np * np; a.Zo = a.Zt + 32 * np; a.Wg = a.Zo + 32 * np; a.T2g = a.Wg + 32 * np;
+  a.Xscr = a.T2g + TINY_DM * TINY_ZP;
+  a.sync = c->dinfo + 8; a.abort_flag = c->dinfo + 8 + SNB_SYNC_INTS;
+  a.np = (int)np; a.NB = NB;
+  a.hcb = c->snb_hc; a.mfb = c->snb_mf;
+  const size_t lds = SNB_LDS_DOUBLES * sizeof(double);
+  c->hpin[P * P + NB] = -2.0;   // (workgroup 0 overwrites it on every path; -2: it did not)
+  c->snb_dirty = true;   // (until this call has ended cleanly)
+  with_fam(kernel_fam(kernel), [&](auto F) { launch_snb_fam<decltype(F)::value>(d, lds, c->stream, a); });
+  CHK(onel_epilogue(c, o, kernel, n_hp, want_grad, OneLaunchResult{c->hpin, P, d, NB, SNB_NH, a.tag, "k_snb"},
+                    a.rdiag != nullptr, llh_out, grad_out, sigma2_out));
   c->snb_hc += want_grad ? 4 * NB - 1 : 2 * NB;
   c->snb_mf += NB + (want_grad ? 1 : 0);
   c->snb_dirty = false;
   return GPE_OK;
 }
 
+}  // namespace
+
+extern "C" {
 
 int gpe_objective(gpe_ctx* c, int32_t variant, int32_t kernel, const double* hp, int32_t n_hp,
                   double nu_fixed, int32_t want_grad, double* llh_out, double* grad_out,
@@ -1912,18 +1789,11 @@ int gpe_objective(gpe_ctx* c, int32_t variant, int32_t kernel, const double* hp,
   CHK(check_ready(c));
   const InflightGuard inflight(c->device);
   if (!hp || !llh_out) return fail(c, GPE_ERR_ARG, "null output");
-  if (variant != GPE_GP4ML && variant != GPE_MUCM) return fail(c, GPE_ERR_ARG, "bad variant");
-  if (!kernel_ok(kernel)) return fail(c, GPE_ERR_ARG, "bad kernel");
   const int d = c->d, q = c->q;
-  const bool gp4ml = variant == GPE_GP4ML;
-  const int base = gp4ml ? d + 1 : d;
-  if (n_hp != base && n_hp != base + 1) return fail(c, GPE_ERR_ARG, "n_hp inconsistent with d");
+  ObjArgs o;
+  CHK(objective_args(variant, kernel, d, hp, n_hp, nu_fixed, &o, &c->err));
+  if (!kernel_ok(kernel)) return fail(c, GPE_ERR_ARG, "bad kernel");
   if (want_grad && !grad_out) return fail(c, GPE_ERR_ARG, "grad_out is NULL");
-  const bool fitnug = (n_hp == base + 1);
-  const double nu = fitnug ? hp[d] : nu_fixed;
-  const double sigma = gp4ml ? hp[n_hp - 1] : 1.0;
-  const double s2 = gp4ml ? sigma * sigma : 1.0;
-  const double rscale = (gp4ml && kernel_alt(kernel)) ? 1.0 : 0.0;
   c->factor_valid = false;
   c->ainv_valid = false;
   c->x32_valid = false;
@@ -1936,15 +1806,13 @@ int gpe_objective(gpe_ctx* c, int32_t variant, int32_t kernel, const double* hp,
   }
   const bool one_launch = c->tiny;
   if (one_launch && c->NB == 1 && d <= TINY_DM && q + 1 <= TINY_DM)
-    return tiny_objective(c, gp4ml, kernel, hp, n_hp, fitnug, nu, s2, rscale, want_grad != 0, llh_out, grad_out,
-                          sigma2_out);
+    return tiny_objective(c, o, kernel, hp, n_hp, want_grad != 0, llh_out, grad_out, sigma2_out);
   if (one_launch && c->NB >= 2 && c->NB <= SNB_MAXNB && d <= TINY_DM && q + 1 <= TINY_DM)
-    return snb_objective(c, gp4ml, kernel, hp, n_hp, fitnug, nu, s2, rscale, want_grad != 0, llh_out, grad_out,
-                         sigma2_out);
+    return snb_objective(c, o, kernel, hp, n_hp, want_grad != 0, llh_out, grad_out, sigma2_out);
 
   // z, w = L^-1 [f H] come out of the factorisation (augmented row); value only runs
   // no L^-1 at all
-  CHK(factor_and_invert(c, kernel, hp, nu, s2, rscale, want_grad != 0, true));
+  CHK(factor_and_invert(c, kernel, hp, o.nu, o.s2, o.rscale, want_grad != 0, true));
   const int P = q + 1;
   const long long np = c->n_pad;
   const int NBt = c->tr.NB;
@@ -1967,30 +1835,12 @@ int gpe_objective(gpe_ctx* c, int32_t variant, int32_t kernel, const double* hp,
   double logdetA = 0.0;
   for (int k = 0; k < NBt; ++k) logdetA += c->hpin[P * P + k];
   logdetA *= 2.0;
-  if (info != 0) {
-    c->err = "matrix not positive definite (pivot " + std::to_string(info) + ")";
-    return GPE_NOT_PD;
-  }
-  SmallAlgebra sa = small_from_gram(G, P);
-  if (!sa.ok) {
-    c->err = "H^T A^-1 H not positive definite";
-    return GPE_NOT_PD;
-  }
-  const double n = (double)c->n;
-  double llh, sig2, cfac, gscale;
-  if (gp4ml) {
-    llh = 0.5 * (sa.quad + logdetA + sa.logdetQ + (n - q) * std::log(2.0 * M_PI));
-    sig2 = s2;
-    cfac = 1.0;
-    gscale = s2;
-  } else {
-    sig2 = sa.quad / (n - q - 2.0);
-    llh = 0.5 * ((n - q) * std::log(sig2) + logdetA + sa.logdetQ);
-    cfac = (n - q) / (sig2 * (n - q - 2.0));
-    gscale = sig2;
-  }
-  *llh_out = llh;
-  if (sigma2_out) *sigma2_out = sig2;
+  if (info != 0) return fail(c, GPE_NOT_PD, not_pd_pivot(info));
+  const SmallAlgebra sa = small_from_gram(G, P);
+  if (!sa.ok) return fail(c, GPE_NOT_PD, Q_NOT_PD);
+  const ObjValue v = objective_value(sa, logdetA, (double)c->n, q, o.gp4ml, o.s2);
+  *llh_out = v.llh;
+  if (sigma2_out) *sigma2_out = v.sig2;
   if (!want_grad) {
     ev_rec(c, 6);
     ev_rec(c, 7);
@@ -1999,34 +1849,27 @@ int gpe_objective(gpe_ctx* c, int32_t variant, int32_t kernel, const double* hp,
   {
     // R2 = [sqrt(c)(z - w B), w Kq^-T] ; [sqrt(c) alpha, W] = L^-T R2
     CHK(ensure_pinned(c, (size_t)P * P + 8));
-    const std::vector<double> T2 = small_t2(sa, q, cfac);
+    const std::vector<double> T2 = small_t2(sa, q, v.cfac);
     std::memcpy(c->hpin, T2.data(), T2.size() * sizeof(double));
     HIPCHK(c, hipMemcpyAsync(c->dT2, c->hpin, T2.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
     CHK(apply_small(c, c->dZ, np, P, c->dT2, P, c->dR2, np, (int)np, c->dinfo));
     CHK(skinny(c, true, c->tr.B, np, c->NB, c->NB, true, c->dR2, np, P, c->dWa, np));
     ev_rec(c, 6);
     // contraction; sum_i M_ii r_i for the std kernel's sigma gradient when r is set
-    const double* rdiag = (gp4ml && !kernel_alt(kernel) && c->has_r) ? c->dr : nullptr;
+    const double* rdiag = (o.gp4ml && !kernel_alt(kernel) && c->has_r) ? c->dr : nullptr;
     const int nblk = c->NB * (c->NB + 1) / 2;
     int cs = 1;   // few tiles (small n): each tile's columns over up to 4 workgroups
     if (!(d > 32 || P > 33))
       while (cs < 4 && nblk * cs * 2 <= 512) cs *= 2;
     const dim3 gc(nblk * cs);
-    const int fam = kernel_fam(kernel);
-    if (fam == FAM_MATERN32) launch_contract<FAM_MATERN32>(c, d, P, gc, nblk, rdiag, cs);
-    else if (fam == FAM_MATERN52) launch_contract<FAM_MATERN52>(c, d, P, gc, nblk, rdiag, cs);
-    else launch_contract<FAM_GAUSS>(c, d, P, gc, nblk, rdiag, cs);
+    with_fam(kernel_fam(kernel), [&](auto F) { launch_contract<decltype(F)::value>(c, d, P, gc, nblk, rdiag, cs); });
     HIPCHK(c, hipGetLastError());
     hipLaunchKernelGGL(k_reduce_rows, dim3(d + 3), dim3(256), 0, c->stream, c->dcpart, nblk * cs, d + 3, c->dcsum);
     HIPCHK(c, hipGetLastError());
     ev_rec(c, 7);
     HIPCHK(c, hipMemcpyAsync(c->hpin, c->dcsum, (d + 3) * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    const double* red = c->hpin;
-    double coff, cdiag;
-    kernel_consts(kernel, nu, true, &coff, &cdiag);
-    small_grad(red, d, kernel_alt(kernel), nu, fitnug, gp4ml, gscale, s2, coff, cdiag, n_hp,
-               grad_out, rdiag != nullptr);
+    objective_grad(c->hpin, d, kernel, o.nu, o.fitnug, o.gp4ml, v.gscale, o.s2, n_hp, grad_out, rdiag != nullptr);
   }
 done:
   if (c->prof) {
@@ -2070,10 +1913,7 @@ int gpe_factor(gpe_ctx* c, int32_t kernel, const double* delta, double nu, doubl
   int info = 0;
   double logdet = 0.0;
   CHK(read_info_logdet(c, c->tr, &info, &logdet));
-  if (info != 0) {
-    c->err = "matrix not positive definite (pivot " + std::to_string(info) + ")";
-    return GPE_NOT_PD;
-  }
+  if (info != 0) return fail(c, GPE_NOT_PD, not_pd_pivot(info));
   c->factor_valid = true;
   c->x32_valid = false;
   c->px_valid = false;
@@ -2288,7 +2128,7 @@ int gpe_beta(gpe_ctx* c, double* beta_out) {
   std::vector<double> G((size_t)P * P);
   CHK(gram(c, c->dZ, np, P, (int)np, G.data()));
   SmallAlgebra sa = small_from_gram(G, P);
-  if (!sa.ok) return fail(c, GPE_NOT_PD, "H^T A^-1 H not positive definite");
+  if (!sa.ok) return fail(c, GPE_NOT_PD, Q_NOT_PD);
   for (int i = 0; i < c->q; ++i) beta_out[i] = sa.beta[i];
   return GPE_OK;
 }
@@ -2310,7 +2150,7 @@ int gpe_loo(gpe_ctx* c, double sigma, double* mean_out, double* var_out, double*
   std::vector<double> G((size_t)P * P);
   CHK(gram(c, c->dZ, np, P, (int)np, G.data()));
   SmallAlgebra sa = small_from_gram(G, P);
-  if (!sa.ok) return fail(c, GPE_NOT_PD, "H^T A^-1 H not positive definite");
+  if (!sa.ok) return fail(c, GPE_NOT_PD, Q_NOT_PD);
   CHK(ensure_pinned(c, (size_t)std::max<long long>(2 * np, (long long)P * P) + 8));
   const std::vector<double> T2 = small_t2(sa, q, 1.0);
   std::memcpy(c->hpin, T2.data(), T2.size() * sizeof(double));
@@ -2397,9 +2237,7 @@ void launch_post_grad_fam(int d, dim3 g, hipStream_t st, const PostGradArgs& a) 
 
 template <bool WB>
 void launch_post_grad(int fam, int d, dim3 g, hipStream_t st, const PostGradArgs& a) {
-  if (fam == FAM_MATERN32) launch_post_grad_fam<FAM_MATERN32, WB>(d, g, st, a);
-  else if (fam == FAM_MATERN52) launch_post_grad_fam<FAM_MATERN52, WB>(d, g, st, a);
-  else launch_post_grad_fam<FAM_GAUSS, WB>(d, g, st, a);
+  with_fam(fam, [&](auto F) { launch_post_grad_fam<decltype(F)::value, WB>(d, g, st, a); });
 }
 
 // One chunk of points as cov_block reads it
@@ -2471,7 +2309,7 @@ struct Posterior : PostReq {
     std::vector<double> Kq((size_t)q * q);
     for (int i = 0; i < q; ++i)
       for (int j = 0; j < q; ++j) Kq[i * q + j] = G[(i + 1) * P + (j + 1)];
-    if (!small_chol(Kq, q)) return fail(c, GPE_NOT_PD, "H^T A^-1 H not positive definite");
+    if (!small_chol(Kq, q)) return fail(c, GPE_NOT_PD, Q_NOT_PD);
     Kinv = small_trinv(Kq, q);
     kernel_consts(c->f_kernel, c->f_nu, true, &coff, &cdiag);
     fam = kernel_fam(c->f_kernel);
@@ -2802,9 +2640,7 @@ struct Posterior : PostReq {
         launch_groupgram(a.gpi * G, dim3((unsigned)((a.ngroups + a.gpi - 1) / a.gpi), (unsigned)f.nseg), a);
         HIPCHK(c, hipGetLastError());
         const dim3 fg((unsigned)((a.ngroups * GG + 255) / 256));
-        if (fam == FAM_MATERN32) hipLaunchKernelGGL(k_post_groupcov<FAM_MATERN32>, fg, dim3(256), 0, c->stream, f);
-        else if (fam == FAM_MATERN52) hipLaunchKernelGGL(k_post_groupcov<FAM_MATERN52>, fg, dim3(256), 0, c->stream, f);
-        else hipLaunchKernelGGL(k_post_groupcov<FAM_GAUSS>, fg, dim3(256), 0, c->stream, f);
+        with_fam(fam, [&](auto F) { hipLaunchKernelGGL(k_post_groupcov<decltype(F)::value>, fg, dim3(256), 0, c->stream, f); });
         HIPCHK(c, hipGetLastError());
         if (c->prof) {   // (profiling only: one synchronisation per chunk)
           float ms = 0.f;
@@ -3034,9 +2870,7 @@ int posterior_mean_impl(gpe_ctx* c, int64_t m, const double* Xs, const double* H
     a.n = (int)c->n; a.np = (int)np; a.mp = (int)mp; a.d = d;
     const dim3 grid((unsigned)(mp / (d > 32 ? PM_LANES : PM_PTS)), (unsigned)nseg);
     if (c->prof) HIPCHK(c, hipEventRecord(c->ev[4], c->stream));
-    if (S.fam == FAM_MATERN32) launch_post_mean_fam<FAM_MATERN32>(d, grid, c->stream, a);
-    else if (S.fam == FAM_MATERN52) launch_post_mean_fam<FAM_MATERN52>(d, grid, c->stream, a);
-    else launch_post_mean_fam<FAM_GAUSS>(d, grid, c->stream, a);
+    with_fam(S.fam, [&](auto F) { launch_post_mean_fam<decltype(F)::value>(d, grid, c->stream, a); });
     HIPCHK(c, hipGetLastError());
     if (c->prof) {   // (profiling only: one synchronisation per chunk)
       float ms = 0.f;
@@ -3687,10 +3521,7 @@ int gpe_cholesky(gpe_ctx* c, int64_t m, const double* A, double* L_out, double* 
   int info = 0;
   double logdet = 0.0;
   CHK(read_info_logdet(c, F, &info, &logdet));
-  if (info != 0) {
-    c->err = "matrix not positive definite (pivot " + std::to_string(info) + ")";
-    return GPE_NOT_PD;
-  }
+  if (info != 0) return fail(c, GPE_NOT_PD, not_pd_pivot(info));
   if (logdet_out) *logdet_out = logdet;
   auto fetch_lower = [&](const double* dsrc, double* out, bool full_sym) -> int {
     HIPCHK(c, hipMemcpy(c->hpin, dsrc, tot * sizeof(double), hipMemcpyDeviceToHost));

@@ -56,7 +56,7 @@
 #include "../../include/gpemu_dist.h"
 #include "gpemu_kernels.hpp"
 #include "gpemu_gemm_sched.hpp"
-#include "gpemu_small.hpp"
+#include "gpemu_objective.hpp"   // (with gpemu_small.hpp)
 #include "gpemu_ozaki.hpp"
 
 using namespace gpe;
@@ -1239,13 +1239,7 @@ int trtri_all(gpe_dist* h) {
 
 int kbuild(gpe_dist* h, int kernel, double nu, double s2, double rscale) {
   double coff, cdiag;
-  if (kernel == GPE_KERNEL_ALT_NUG) {
-    coff = 1.0;
-    cdiag = 1.0 + nu * nu;
-  } else {
-    coff = 1.0 - nu;
-    cdiag = 1.0;
-  }
+  kernel_consts(kernel, nu, true, &coff, &cdiag);
   for (Rank& R : h->ranks) {
     if (R.nloc == 0) continue;   // more ranks than tile rows
     DistPairArgs a;
@@ -1629,30 +1623,20 @@ int gpe_dist_objective(gpe_dist* h, int32_t variant, int32_t kernel, const doubl
   if (h->n <= 0) return dfail(h, GPE_ERR_STATE, "gpe_dist_set_data has not been called");
   if (!hp || !llh_out) return dfail(h, GPE_ERR_ARG, "null argument");
   if (want_grad && !grad_out) return dfail(h, GPE_ERR_ARG, "grad_out is NULL");
-  if (variant != GPE_GP4ML && variant != GPE_MUCM) return dfail(h, GPE_ERR_ARG, "bad variant");
-  // a valid Matern code (one family bit, with or without the alt-nugget bit)
-  const int fam_bits = kernel & (GPE_KERNEL_MATERN32 | GPE_KERNEL_MATERN52);
-  if ((kernel & ~(GPE_KERNEL_ALT_NUG | fam_bits)) == 0 &&
-      (fam_bits == GPE_KERNEL_MATERN32 || fam_bits == GPE_KERNEL_MATERN52))
+  const int d = h->d, q = h->q, Pc = q + 1, P = h->P, NB = h->NB;
+  ObjArgs o;
+  DCHK(objective_args(variant, kernel, d, hp, n_hp, nu_fixed, &o, &h->err));
+  if (!kernel_ok(kernel)) return dfail(h, GPE_ERR_ARG, "bad kernel");
+  if (kernel_fam(kernel) != FAM_GAUSS)   // a valid Matern code
     return dfail(h, GPE_ERR_UNSUPPORTED,
                  "the row-block distributed objective has Gaussian correlations only: train a Matern "
                  "kernel on one GPU or with replicas");
-  if (kernel != GPE_KERNEL_STD && kernel != GPE_KERNEL_ALT_NUG) return dfail(h, GPE_ERR_ARG, "bad kernel");
   DCHK_HIP(h, hipSetDevice(h->device));
   // a previous call that failed inside group_sweep may have left chain work queued on the
   // critical stream, never joined into the compute stream: drain it before this call's
   // host staging and memsets (idle in the normal case)
   DCHK_HIP(h, hipStreamSynchronize(h->crit));
-  const int d = h->d, q = h->q, Pc = q + 1, P = h->P, NB = h->NB;
   const long long np = h->n_pad;
-  const bool gp4ml = variant == GPE_GP4ML;
-  const int base = gp4ml ? d + 1 : d;
-  if (n_hp != base && n_hp != base + 1) return dfail(h, GPE_ERR_ARG, "n_hp inconsistent with d");
-  const bool fitnug = n_hp == base + 1;
-  const double nu = fitnug ? hp[d] : nu_fixed;
-  const double sigma = gp4ml ? hp[n_hp - 1] : 1.0;
-  const double s2 = gp4ml ? sigma * sigma : 1.0;
-  const double rscale = (gp4ml && kernel == GPE_KERNEL_ALT_NUG) ? 1.0 : 0.0;
   if (want_grad) DCHK(ensure_grad(h));
   h->grad_now = want_grad != 0;
   h->ev = 0;
@@ -1660,11 +1644,8 @@ int gpe_dist_objective(gpe_dist* h, int32_t variant, int32_t kernel, const doubl
   Rank& R0 = h->ranks[0];   // every rank holds the reduced results; read this process's first
 
   DCHK(pinned(h, (size_t)NB + 1 + (size_t)Pc * Pc + (size_t)(d + 3) + 64));
-  for (int k = 0; k < d; ++k) {
-    if (!(hp[k] > 0.0) && !(hp[k] < 0.0))   // as the single-GPU path: not positive definite
-      return dfail(h, GPE_NOT_PD, "length scale delta[" + std::to_string(k) + "] is zero or NaN");
-    h->hpin[k] = 1.0 / hp[k];
-  }
+  const int bad = inv_length_scales(hp, d, h->hpin);
+  if (bad >= 0) return dfail(h, GPE_NOT_PD, bad_length_scale(bad));   // (as the single-GPU path)
   DCHK_HIP(h, hipEventRecord(h->e0, h->stream));
   DCHK_HIP(h, hipMemcpyAsync(h->dinvdelta, h->hpin, d * sizeof(double), hipMemcpyHostToDevice, h->stream));
   DCHK_HIP(h, hipMemsetAsync(h->dinfo, 0, sizeof(int), h->stream));
@@ -1677,7 +1658,7 @@ int gpe_dist_objective(gpe_dist* h, int32_t variant, int32_t kernel, const doubl
     if (h->grad_now && R.nlx > 0)
       DCHK_HIP(h, hipMemsetAsync(R.X, 0, (size_t)R.ld * NB * TILE * sizeof(double), h->stream));
   }
-  DCHK(kbuild(h, kernel, nu, s2, rscale));
+  DCHK(kbuild(h, kernel, o.nu, o.s2, o.rscale));
   DCHK_HIP(h, hipMemsetAsync(h->dq, 0, 6 * (size_t)NB * sizeof(int), h->stream));
   DCHK(group_sweep(h));
   // P = 1: the sweep's factors stored L and the leaf inverses only (flag mode): the
@@ -1733,8 +1714,7 @@ int gpe_dist_objective(gpe_dist* h, int32_t variant, int32_t kernel, const doubl
   }
   if (info != 0) {
     (void)hipStreamSynchronize(h->stream);   // the queued inverse steps skip themselves (abort flag)
-    h->err = "matrix not positive definite (pivot " + std::to_string(info) + ")";
-    return GPE_NOT_PD;
+    return dfail(h, GPE_NOT_PD, not_pd_pivot(info));
   }
   double logdetA = 0.0;
   for (int k = 0; k < NB; ++k) logdetA += hld[k];
@@ -1742,31 +1722,18 @@ int gpe_dist_objective(gpe_dist* h, int32_t variant, int32_t kernel, const doubl
   std::vector<double> G((size_t)Pc * Pc);
   for (int i = 0; i < Pc; ++i)   // from the lower triangle (tiles above the diagonal are not formed)
     for (int j = 0; j < Pc; ++j) G[(size_t)i * Pc + j] = -hgram[std::max(i, j) + (size_t)std::min(i, j) * Pc];
-  SmallAlgebra sa = small_from_gram(G, Pc);
+  const SmallAlgebra sa = small_from_gram(G, Pc);
   if (!sa.ok) {
     (void)hipStreamSynchronize(h->stream);
-    h->err = "H^T A^-1 H not positive definite";
-    return GPE_NOT_PD;
+    return dfail(h, GPE_NOT_PD, Q_NOT_PD);
   }
-  const double n = (double)h->n;
-  double llh, sig2, cfac, gscale;
-  if (gp4ml) {
-    llh = 0.5 * (sa.quad + logdetA + sa.logdetQ + (n - q) * std::log(2.0 * M_PI));
-    sig2 = s2;
-    cfac = 1.0;
-    gscale = s2;
-  } else {
-    sig2 = sa.quad / (n - q - 2.0);
-    llh = 0.5 * ((n - q) * std::log(sig2) + logdetA + sa.logdetQ);
-    cfac = (n - q) / (sig2 * (n - q - 2.0));
-    gscale = sig2;
-  }
-  *llh_out = llh;
-  if (sigma2_out) *sigma2_out = sig2;
+  const ObjValue v = objective_value(sa, logdetA, (double)h->n, q, o.gp4ml, o.s2);
+  *llh_out = v.llh;
+  if (sigma2_out) *sigma2_out = v.sig2;
 
   if (h->grad_now) {
     // R2 = Z T2; [sqrt(c) alpha, W] = X^T R2 = sum over ranks of X_r^T R2_r
-    const std::vector<double> T2 = small_t2(sa, q, cfac);
+    const std::vector<double> T2 = small_t2(sa, q, v.cfac);
     std::memcpy(h->hpin, T2.data(), T2.size() * sizeof(double));
     DCHK_HIP(h, hipMemcpyAsync(h->dT2, h->hpin, T2.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
     for (size_t s = 0; s < h->ranks.size(); ++s) {
@@ -1791,7 +1758,7 @@ int gpe_dist_objective(gpe_dist* h, int32_t variant, int32_t kernel, const doubl
     const int nblk = NB * (NB + 1) / 2;
     const long long lds = (long long)h->slab_rows * TILE;
     // sum_i M_ii r_i for the std kernel's sigma gradient when r is set (small_grad)
-    const double* rdiag = (gp4ml && kernel == GPE_KERNEL_STD && h->has_r) ? h->dr : nullptr;
+    const double* rdiag = (o.gp4ml && kernel == GPE_KERNEL_STD && h->has_r) ? h->dr : nullptr;
     for (size_t s = 0; s < h->ranks.size(); ++s) {
       Rank& R = h->ranks[s];
       DCHK_HIP(h, hipMemsetAsync(R.csum, 0, (size_t)(d + 3) * sizeof(double), h->stream));
@@ -1816,19 +1783,9 @@ int gpe_dist_objective(gpe_dist* h, int32_t variant, int32_t kernel, const doubl
     DCHK_HIP(h, hipMemcpyAsync(h->hpin, R0.csum, (size_t)(d + 3) * sizeof(double), hipMemcpyDeviceToHost,
                                h->stream));
   DCHK_HIP(h, hipStreamSynchronize(h->stream));
-  if (h->grad_now) {
-    double coff, cdiag;
-    if (kernel == GPE_KERNEL_ALT_NUG) {
-      coff = 1.0;
-      cdiag = 1.0 + nu * nu;
-    } else {
-      coff = 1.0 - nu;
-      cdiag = 1.0;
-    }
-    std::vector<double> red(h->hpin, h->hpin + d + 3);
-    small_grad(red.data(), d, kernel == GPE_KERNEL_ALT_NUG, nu, fitnug, gp4ml, gscale, s2, coff, cdiag, n_hp,
-               grad_out, gp4ml && kernel == GPE_KERNEL_STD && h->has_r);
-  }
+  if (h->grad_now)
+    objective_grad(h->hpin, d, kernel, o.nu, o.fitnug, o.gp4ml, v.gscale, o.s2, n_hp, grad_out,
+                   o.gp4ml && kernel == GPE_KERNEL_STD && h->has_r);
   {
     float ms = 0.f;
     (void)hipEventElapsedTime(&ms, h->e0, h->e1);

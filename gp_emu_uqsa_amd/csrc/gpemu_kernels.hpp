@@ -22,6 +22,7 @@
 #include <cstdlib>
 
 #include "gpemu_diag.hpp"
+#include "gpemu_objective.hpp"   // FAM_*
 
 namespace gpe {
 
@@ -64,7 +65,6 @@ struct PairArgs {
 // g is the factor of d rho / d(2 log delta_k) = g u_k^2, u_k = (x_k - x'_k) / delta_k (the
 // part exp_save plays in the reference's grad_delta_A).  One sqrt and one exp, then FMAs;
 // nothing divides by r, so coincident points (s = 0) give rho = 1 and g = 3/2, 5/6.
-enum : int { FAM_GAUSS = 0, FAM_MATERN32 = 1, FAM_MATERN52 = 2 };
 
 template <int FAM>
 __device__ inline void matern_rho_g(double s, double& rho, double& g) {
