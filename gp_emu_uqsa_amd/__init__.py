@@ -12,7 +12,8 @@ gfx950, C-ABI in include/gpemu.h); there is no CPU fallback.
 """
 from .api import (loo, plot, posterior, posterior_gradient, posterior_groups, posterior_mean,  # noqa: F401
                   posterior_sample, setup, train)
+from . import multioutput  # noqa: F401  (p outputs with one correlation matrix: multioutput.setup / train / posterior)
 
 __all__ = ["setup", "train", "plot", "posterior", "posterior_sample", "loo", "posterior_gradient",
-           "posterior_mean", "posterior_groups"]
+           "posterior_mean", "posterior_groups", "multioutput"]
 __version__ = "0.1.0"

@@ -35,6 +35,7 @@
 #include "gpemu_imse.hpp"
 #include "gpemu_postgrad.hpp"
 #include "gpemu_postmean.hpp"
+#include "gpemu_postmean_multi.hpp"
 #include "gpemu_postgroup.hpp"
 #include "gpemu_host_alloc.hpp"
 
@@ -277,6 +278,18 @@ struct gpe_ctx {
   double* dPm = nullptr;
   size_t pm_cap = 0;
   long long mean_chunk = 65536;
+  // p outputs on the resident data (gpe_set_outputs; 0: none): [F H] (n_pad x (p + q),
+  // column-major), its images Z, R2 and W of the multi-output objective (as dZ, dR2, dWa for
+  // [f H]; the first p columns of dWm are Gamma for gpe_posterior_mean_multi), and
+  // k_post_mean_multi's segment sums and chunk result
+  int mo_p = 0;
+  double* dFm = nullptr;
+  double* dZm = nullptr;
+  double* dR2m = nullptr;
+  double* dWm = nullptr;
+  size_t fm_cap = 0, zm_cap = 0, r2m_cap = 0, wm_cap = 0;
+  double* dPmm = nullptr;
+  size_t pmm_cap = 0;
   // the covariance inside groups (gpe_posterior_groups): k_post_groupgram's segment sums
   double* dPgc = nullptr;
   size_t pgc_cap = 0;
@@ -481,21 +494,22 @@ int launch_pairs(gpe_ctx* c, const PairArgs& a, int nblocks) {
 }
 
 // The gradient contraction of gpe_objective for one correlation family: k_contract<.., FAM>
-// by bucket of d and P = q + 1, k_contract_wide<FAM> beyond the register-resident sizes.
+// by bucket of d and the P columns of W (q + 1; p + q for p outputs), k_contract_wide<FAM> beyond
+// the register-resident sizes.
 template <int FAM>
-static void launch_contract(gpe_ctx* c, int d, int P, dim3 gc, int nblk, const double* rdiag, int cs) {
+static void launch_contract(gpe_ctx* c, int d, int P, dim3 gc, int nblk, const double* rdiag, int cs, const double* Wa) {
   const long long np = c->n_pad;
   const int bucket = std::max(d, P);
   if (d > 32 || P > 33) {   // any d and q: staged through LDS in chunks of 32
-    hipLaunchKernelGGL(k_contract_wide<FAM>, dim3(nblk), dim3(256), 0, c->stream, c->tr.A, np, c->dXw, d, c->dWa, np, P, (int)c->n, c->dcpart, c->dinfo, 0, 0ll, rdiag);
+    hipLaunchKernelGGL(k_contract_wide<FAM>, dim3(nblk), dim3(256), 0, c->stream, c->tr.A, np, c->dXw, d, Wa, np, P, (int)c->n, c->dcpart, c->dinfo, 0, 0ll, rdiag);
   } else if (d == 10 && P <= 13) {   // the headline configuration: no padded dimensions
-    hipLaunchKernelGGL((k_contract<10, 13, FAM>), gc, dim3(256), 0, c->stream, c->tr.A, np, c->dXw, d, c->dWa, np, P, (int)c->n, c->dcpart, c->dinfo, 0, 0ll, rdiag, cs);
+    hipLaunchKernelGGL((k_contract<10, 13, FAM>), gc, dim3(256), 0, c->stream, c->tr.A, np, c->dXw, d, Wa, np, P, (int)c->n, c->dcpart, c->dinfo, 0, 0ll, rdiag, cs);
   } else if (bucket <= 8) {
-    hipLaunchKernelGGL((k_contract<8, 9, FAM>), gc, dim3(256), 0, c->stream, c->tr.A, np, c->dXw, d, c->dWa, np, P, (int)c->n, c->dcpart, c->dinfo, 0, 0ll, rdiag, cs);
+    hipLaunchKernelGGL((k_contract<8, 9, FAM>), gc, dim3(256), 0, c->stream, c->tr.A, np, c->dXw, d, Wa, np, P, (int)c->n, c->dcpart, c->dinfo, 0, 0ll, rdiag, cs);
   } else if (bucket <= 16) {
-    hipLaunchKernelGGL((k_contract<16, 17, FAM>), gc, dim3(256), 0, c->stream, c->tr.A, np, c->dXw, d, c->dWa, np, P, (int)c->n, c->dcpart, c->dinfo, 0, 0ll, rdiag, cs);
+    hipLaunchKernelGGL((k_contract<16, 17, FAM>), gc, dim3(256), 0, c->stream, c->tr.A, np, c->dXw, d, Wa, np, P, (int)c->n, c->dcpart, c->dinfo, 0, 0ll, rdiag, cs);
   } else {
-    hipLaunchKernelGGL((k_contract<32, 33, FAM>), gc, dim3(256), 0, c->stream, c->tr.A, np, c->dXw, d, c->dWa, np, P, (int)c->n, c->dcpart, c->dinfo, 0, 0ll, rdiag, cs);
+    hipLaunchKernelGGL((k_contract<32, 33, FAM>), gc, dim3(256), 0, c->stream, c->tr.A, np, c->dXw, d, Wa, np, P, (int)c->n, c->dcpart, c->dinfo, 0, 0ll, rdiag, cs);
   }
 }
 
@@ -984,7 +998,14 @@ void ev_rec(gpe_ctx* c, int i) {
   if (c->prof) hipEventRecord(c->ev[i], c->stream);
 }
 
-int z_from_factor(gpe_ctx* c);
+// The columns a factorisation carries and solves for: [f H] of gpe_set_data into dZ (the
+// default everywhere), or [F H] of gpe_set_outputs into dZm (the multi-output entries)
+struct Cols {
+  const double* F;
+  int P;
+  double* Z;
+};
+int z_from_factor(gpe_ctx* c, const Cols* cols = nullptr, bool cols_in_aug = false);
 int trsv_lower(gpe_ctx* c, Fact& F, const double* R, long long ldr, int P, double* Y, long long ldy);
 
 // K-build and Cholesky of the training matrix; with invert, also X = L^-1 (TRTRI) into
@@ -992,7 +1013,7 @@ int trsv_lower(gpe_ctx* c, Fact& F, const double* R, long long ldr, int P, doubl
 // substitution (trsv_lower) needs: the value-only objective and gpe_beta skip the n^3/3
 // flops of the inverse, and the posterior-side entries run it on demand (ensure_linv).
 int factor_and_invert(gpe_ctx* c, int kernel, const double* delta, double nu, double s2,
-                      double rscale, bool invert = true, bool objective = false) {
+                      double rscale, bool invert = true, bool objective = false, const Cols* cols = nullptr) {
   c->linv_valid = false;
   c->oz_l21_valid = false;
   // a call that failed inside the sweep may have left Cholesky launches on the
@@ -1004,22 +1025,23 @@ int factor_and_invert(gpe_ctx* c, int kernel, const double* delta, double nu, do
   ev_rec(c, 0);
   CHK(scale_training(c, delta));
   CHK(kbuild(c, kernel, nu, s2, rscale));
-  const int P = c->q + 1;
+  const int P = cols ? cols->P : c->q + 1;
   // without the inverse (value only, gpe_factor) the sweep carries [f H]^T in the
   // augmented row and leaves L^-1 [f H] there; with it, L^-1 [f H] is one skinny product
   // with L^-1 and the sweep stays lean
-  c->zaug_valid = !invert && c->tr.plan.aug && P <= TILE;   // the row holds at most 128 columns
-  if (c->zaug_valid) {
+  const bool aug = !invert && c->tr.plan.aug && P <= TILE;   // the row holds at most 128 columns
+  c->zaug_valid = aug && !cols;   // (other columns in the row are their caller's alone)
+  if (aug) {
     const long long tot = c->n_pad * TILE;
-    hipLaunchKernelGGL(k_aug_init, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, c->stream, c->dF,
-                       c->n_pad, P, c->n_pad, c->tr.Faug);
+    hipLaunchKernelGGL(k_aug_init, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, c->stream,
+                       cols ? cols->F : c->dF, c->n_pad, P, c->n_pad, c->tr.Faug);
     HIPCHK(c, hipGetLastError());
   }
   ev_rec(c, 1);
   CHK(build_plan(c, c->tr));
   // the objective's sweep may split (its gradient evaluations; the value-only ones when asked)
   // ... and nest with its gradient evaluations (and gpe_factor's sweep under the test switch 3)
-  CHK(potrf(c, c->tr, c->zaug_valid, objective && (invert || c->oz_chol >= 2), objective && invert,
+  CHK(potrf(c, c->tr, aug, objective && (invert || c->oz_chol >= 2), objective && invert,
             objective && (invert || c->oz_chol == 3)));
   if (kernel_fam(kernel) != FAM_GAUSS) {
     // Matern families: a pivot within the factorisation's backward error of zero is not
@@ -1038,7 +1060,7 @@ int factor_and_invert(gpe_ctx* c, int kernel, const double* delta, double nu, do
     CHK(trtri(c, c->tr, true));   // (only the objective's gradient inverts here)
     c->linv_valid = true;
   }
-  CHK(z_from_factor(c));
+  CHK(z_from_factor(c, cols, aug));
   ev_rec(c, 3);
   return GPE_OK;
 }
@@ -1046,18 +1068,20 @@ int factor_and_invert(gpe_ctx* c, int kernel, const double* delta, double nu, do
 // Z = L^-1 [f H] of the resident factor into c->dZ (n_pad x P, column-major): from the
 // augmented row when the fused sweep carried it, else as L^-1 times [f H] when L^-1 is
 // resident, else by forward substitution
-int z_from_factor(gpe_ctx* c) {
-  const int P = c->q + 1;
+int z_from_factor(gpe_ctx* c, const Cols* cols, bool cols_in_aug) {
+  const int P = cols ? cols->P : c->q + 1;
+  const double* F = cols ? cols->F : c->dF;
+  double* Z = cols ? cols->Z : c->dZ;
   const long long np = c->n_pad;
-  if (c->zaug_valid) {
+  if (cols ? cols_in_aug : c->zaug_valid) {
     const long long tot = np * P;
     hipLaunchKernelGGL(k_aug_to_cols, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, c->stream,
-                       c->tr.Faug, P, np, c->dZ, np);
+                       c->tr.Faug, P, np, Z, np);
     HIPCHK(c, hipGetLastError());
     return GPE_OK;
   }
-  if (c->linv_valid) return skinny(c, false, c->tr.B, np, c->NB, c->NB, true, c->dF, np, P, c->dZ, np);
-  return trsv_lower(c, c->tr, c->dF, np, P, c->dZ, np);
+  if (c->linv_valid) return skinny(c, false, c->tr.B, np, c->NB, c->NB, true, F, np, P, Z, np);
+  return trsv_lower(c, c->tr, F, np, P, Z, np);
 }
 
 // X = L^-1 of the resident factor into tr.B if the factorisation skipped it
@@ -1513,7 +1537,8 @@ void gpe_destroy(gpe_ctx* c) {
                     c->aux.logdet, c->dinvdelta, c->dZ,
                     c->dR2, c->dWa, c->dskp, c->dgpart, c->dgram, c->dT2, c->dcpart, c->dcsum,
                     c->dW1, c->dW2, c->dW3, c->dXs, c->dXsw, c->dsmall, c->dtiny, c->dsnb, c->dRn, c->dNU,
-                    c->dVall, c->dXall, c->dTall, c->dPc, c->dPcL, c->dIm, c->dImC, c->dPg, c->dPm, c->dPgc};
+                    c->dVall, c->dXall, c->dTall, c->dPc, c->dPcL, c->dIm, c->dImC, c->dPg, c->dPm, c->dPgc,
+                    c->dFm, c->dZm, c->dR2m, c->dWm, c->dPmm};
   for (double* b : bufs)
     if (b) hipFree(b);
   if (c->dinfo) hipFree(c->dinfo);
@@ -1574,6 +1599,7 @@ int gpe_set_data(gpe_ctx* c, int64_t n, int32_t d, int32_t q, const double* X, c
   const long long n_pad = ((n + TILE - 1) / TILE) * TILE;
   const bool resize = (n_pad != c->n_pad) || (d != c->d) || (q != c->q);
   c->n = n; c->d = d; c->q = q; c->n_pad = n_pad; c->NB = (int)(n_pad / TILE);
+  c->mo_p = 0;   // (outputs belong to the data they were set for)
   c->factor_valid = false;
   c->ainv_valid = false;
   c->x32_valid = false;
@@ -1779,6 +1805,37 @@ int snb_objective(gpe_ctx* c, const ObjArgs& o, int kernel, const double* hp, in
   return GPE_OK;
 }
 
+// gpe_phase_times / gpe_gemm_stats / gpe_ozaki_stats of a general-path objective call whose
+// work is queued (profiling on; nothing otherwise)
+int objective_phase_times(gpe_ctx* c) {
+  if (!c->prof) return GPE_OK;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  float ms;
+  // kbuild, cholesky, trtri, inverse (LAUUM), skinny (L^-1 [f H] + Gram), contract
+  // (L^-T R2 + the fused contraction), total
+  const int pairs[7][2] = {{0, 1}, {1, 2}, {2, 3}, {4, 5}, {3, 4}, {5, 7}, {0, 7}};
+  for (int i = 0; i < 7; ++i) {
+    ms = 0.f;
+    (void)hipEventElapsedTime(&ms, c->ev[pairs[i][0]], c->ev[pairs[i][1]]);
+    c->phase_ms[i] = ms;
+  }
+  double g = 0.0;
+  for (size_t i = 0; i + 1 < c->gev_used; i += 2) {
+    ms = 0.f;
+    (void)hipEventElapsedTime(&ms, c->gev[i], c->gev[i + 1]);
+    g += ms;
+  }
+  c->gemm_ms = g;
+  g = 0.0;
+  for (size_t i = 0; i + 1 < c->oev_used; i += 2) {
+    ms = 0.f;
+    (void)hipEventElapsedTime(&ms, c->oev[i], c->oev[i + 1]);
+    g += ms;
+  }
+  c->oz_ms = g;
+  return GPE_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1862,7 +1919,7 @@ int gpe_objective(gpe_ctx* c, int32_t variant, int32_t kernel, const double* hp,
     if (!(d > 32 || P > 33))
       while (cs < 4 && nblk * cs * 2 <= 512) cs *= 2;
     const dim3 gc(nblk * cs);
-    with_fam(kernel_fam(kernel), [&](auto F) { launch_contract<decltype(F)::value>(c, d, P, gc, nblk, rdiag, cs); });
+    with_fam(kernel_fam(kernel), [&](auto F) { launch_contract<decltype(F)::value>(c, d, P, gc, nblk, rdiag, cs, c->dWa); });
     HIPCHK(c, hipGetLastError());
     hipLaunchKernelGGL(k_reduce_rows, dim3(d + 3), dim3(256), 0, c->stream, c->dcpart, nblk * cs, d + 3, c->dcsum);
     HIPCHK(c, hipGetLastError());
@@ -1872,33 +1929,114 @@ int gpe_objective(gpe_ctx* c, int32_t variant, int32_t kernel, const double* hp,
     objective_grad(c->hpin, d, kernel, o.nu, o.fitnug, o.gp4ml, v.gscale, o.s2, n_hp, grad_out, rdiag != nullptr);
   }
 done:
-  if (c->prof) {
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    float ms;
-    // kbuild, cholesky, trtri, inverse (LAUUM), skinny (L^-1 [f H] + Gram), contract
-    // (L^-T R2 + the fused contraction), total
-    const int pairs[7][2] = {{0, 1}, {1, 2}, {2, 3}, {4, 5}, {3, 4}, {5, 7}, {0, 7}};
-    for (int i = 0; i < 7; ++i) {
-      ms = 0.f;
-      (void)hipEventElapsedTime(&ms, c->ev[pairs[i][0]], c->ev[pairs[i][1]]);
-      c->phase_ms[i] = ms;
-    }
-    double g = 0.0;
-    for (size_t i = 0; i + 1 < c->gev_used; i += 2) {
-      ms = 0.f;
-      (void)hipEventElapsedTime(&ms, c->gev[i], c->gev[i + 1]);
-      g += ms;
-    }
-    c->gemm_ms = g;
-    g = 0.0;
-    for (size_t i = 0; i + 1 < c->oev_used; i += 2) {
-      ms = 0.f;
-      (void)hipEventElapsedTime(&ms, c->oev[i], c->oev[i + 1]);
-      g += ms;
-    }
-    c->oz_ms = g;
-  }
+  return objective_phase_times(c);
+}
+
+int gpe_set_outputs(gpe_ctx* c, int32_t p, const double* F) {
+  CHK(check_ready(c));
+  const int q = c->q;
+  const long long n = c->n, np = c->n_pad;
+  if (p < 1 || p > PMM_MAXP || !F) return fail(c, GPE_ERR_ARG, "bad outputs (1 <= p <= 64, F not NULL)");
+  if (n < (long long)p + q + 3) return fail(c, GPE_ERR_ARG, "p outputs need n >= p + q + 3 training points");
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  c->mo_p = 0;
+  const int P = p + q;
+  const size_t cols = (size_t)np * std::max(SK_PMAX, P);
+  CHK(ensure_shape_bufs(c, c->d, P));
+  CHK(grow_buf(c, &c->dFm, &c->fm_cap, (size_t)np * P));
+  CHK(grow_buf(c, &c->dZm, &c->zm_cap, cols));
+  CHK(grow_buf(c, &c->dR2m, &c->r2m_cap, cols));
+  CHK(grow_buf(c, &c->dWm, &c->wm_cap, cols));
+  // [F H] column-major, padded rows 0: F from the host, H as gpe_set_data left it in [f H]
+  const size_t nf = (size_t)np * p;
+  CHK(ensure_pinned(c, nf));
+  std::memset(c->hpin, 0, nf * sizeof(double));
+  for (long long i = 0; i < n; ++i)
+    for (int a = 0; a < p; ++a) c->hpin[i + (long long)a * np] = F[i * p + a];
+  HIPCHK(c, hipMemcpy(c->dFm, c->hpin, nf * sizeof(double), hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(c->dFm + nf, c->dF + np, (size_t)np * q * sizeof(double), hipMemcpyDeviceToDevice));
+  c->mo_p = p;
   return GPE_OK;
+}
+
+int gpe_objective_multi(gpe_ctx* c, int32_t kernel, const double* hp, int32_t n_hp, double nu_fixed,
+                        int32_t want_grad, double* llh_out, double* grad_out, double* Sigma_out, double* B_out) {
+  CHK(check_ready(c));
+  if (!c->mo_p) return fail(c, GPE_ERR_STATE, "gpe_set_outputs has not been called for this data");
+  const InflightGuard inflight(c->device);
+  if (!hp || !llh_out || !Sigma_out) return fail(c, GPE_ERR_ARG, "null output");
+  const int d = c->d, q = c->q, p = c->mo_p, P = p + q;
+  ObjArgs o;
+  CHK(objective_args(GPE_MUCM, kernel, d, hp, n_hp, nu_fixed, &o, &c->err));
+  if (!kernel_ok(kernel)) return fail(c, GPE_ERR_ARG, "bad kernel");
+  if (want_grad && !grad_out) return fail(c, GPE_ERR_ARG, "grad_out is NULL");
+  c->factor_valid = false;
+  c->ainv_valid = false;
+  c->x32_valid = false;
+  c->px_valid = false;
+  if (c->prof) {
+    c->gev_used = 0;
+    c->gemm_launches = c->gemm_flops = c->gemm_ms = 0.0;
+    c->oev_used = 0;
+    c->oz_ms = c->oz_launches = c->oz_ops = c->oz_flops64 = 0.0;
+  }
+  // the general path of gpe_objective at every n, on the p + q columns of [F H]
+  const Cols cols{c->dFm, P, c->dZm};
+  CHK(factor_and_invert(c, kernel, hp, o.nu, o.s2, o.rscale, want_grad != 0, true, &cols));
+  const long long np = c->n_pad;
+  const int NBt = c->tr.NB;
+  CHK(ensure_pinned(c, (size_t)P * P + NBt + 64));
+  CHK(gram_async(c, c->dZm, np, P, (int)np));
+  HIPCHK(c, hipMemcpyAsync(c->hpin + P * P, c->tr.logdet, NBt * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->hpin + P * P + NBt, c->dinfo, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipEventRecord(c->ev_host, c->stream));
+  ev_rec(c, 4);
+  if (want_grad) CHK(oz_use(c) ? lauum_ozaki(c, c->tr) : lauum(c, c->tr));
+  ev_rec(c, 5);
+  HIPCHK(c, hipEventSynchronize(c->ev_host));
+  const std::vector<double> G(c->hpin, c->hpin + (size_t)P * P);
+  int info = 0;
+  std::memcpy(&info, c->hpin + P * P + NBt, sizeof(int));
+  if (info == GEMM_WAIT_TIMEOUT) return fail(c, GPE_ERR_HIP, "internal error: Cholesky panel wait timed out");
+  double logdetA = 0.0;
+  for (int k = 0; k < NBt; ++k) logdetA += c->hpin[P * P + k];
+  logdetA *= 2.0;
+  if (info != 0) return fail(c, GPE_NOT_PD, not_pd_pivot(info));
+  const SmallMulti sm = small_multi_from_gram(G, p, q);
+  if (!sm.ok()) return fail(c, GPE_NOT_PD, sm.refused == 1 ? Q_NOT_PD : S_NOT_PD);
+  const ObjValueMulti v = objective_value_multi(sm, logdetA, (double)c->n);
+  *llh_out = v.llh;
+  std::memcpy(Sigma_out, v.Sigma.data(), v.Sigma.size() * sizeof(double));
+  if (B_out) std::memcpy(B_out, sm.B.data(), sm.B.size() * sizeof(double));
+  if (!want_grad) {
+    ev_rec(c, 6);
+    ev_rec(c, 7);
+    return objective_phase_times(c);
+  }
+  // W = L^-T Z T2 = [sqrt((n - q) / p) P F C^-T, G Kq^-T], then the contraction of
+  // M = A^-1 - W W^T as for one output
+  CHK(ensure_pinned(c, (size_t)P * P + 8));
+  const std::vector<double> T2 = small_multi_t2(sm, v.cfac);
+  std::memcpy(c->hpin, T2.data(), T2.size() * sizeof(double));
+  HIPCHK(c, hipMemcpyAsync(c->dT2, c->hpin, T2.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  CHK(apply_small(c, c->dZm, np, P, c->dT2, P, c->dR2m, np, (int)np, c->dinfo));
+  CHK(skinny(c, true, c->tr.B, np, c->NB, c->NB, true, c->dR2m, np, P, c->dWm, np));
+  ev_rec(c, 6);
+  const int nblk = c->NB * (c->NB + 1) / 2;
+  int cs = 1;   // few tiles (small n): each tile's columns over up to 4 workgroups
+  if (!(d > 32 || P > 33))
+    while (cs < 4 && nblk * cs * 2 <= 512) cs *= 2;
+  const dim3 gc(nblk * cs);
+  with_fam(kernel_fam(kernel),
+           [&](auto F) { launch_contract<decltype(F)::value>(c, d, P, gc, nblk, nullptr, cs, c->dWm); });
+  HIPCHK(c, hipGetLastError());
+  hipLaunchKernelGGL(k_reduce_rows, dim3(d + 3), dim3(256), 0, c->stream, c->dcpart, nblk * cs, d + 3, c->dcsum);
+  HIPCHK(c, hipGetLastError());
+  ev_rec(c, 7);
+  HIPCHK(c, hipMemcpyAsync(c->hpin, c->dcsum, (d + 3) * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  objective_grad(c->hpin, d, kernel, o.nu, o.fitnug, false, v.gscale, 1.0, n_hp, grad_out, false);
+  return objective_phase_times(c);
 }
 
 int gpe_factor(gpe_ctx* c, int32_t kernel, const double* delta, double nu, double s2, double r_scale) {
@@ -2130,6 +2268,23 @@ int gpe_beta(gpe_ctx* c, double* beta_out) {
   SmallAlgebra sa = small_from_gram(G, P);
   if (!sa.ok) return fail(c, GPE_NOT_PD, Q_NOT_PD);
   for (int i = 0; i < c->q; ++i) beta_out[i] = sa.beta[i];
+  return GPE_OK;
+}
+
+int gpe_beta_multi(gpe_ctx* c, double* B_out) {
+  CHK(check_ready(c));
+  if (!c->factor_valid) return fail(c, GPE_ERR_STATE, "no resident factor (call gpe_factor)");
+  if (!c->mo_p) return fail(c, GPE_ERR_STATE, "gpe_set_outputs has not been called for this data");
+  if (!B_out) return fail(c, GPE_ERR_ARG, "B_out is NULL");
+  const int p = c->mo_p, P = p + c->q;
+  const long long np = c->n_pad;
+  const Cols cols{c->dFm, P, c->dZm};
+  CHK(z_from_factor(c, &cols));
+  std::vector<double> G((size_t)P * P);
+  CHK(gram(c, c->dZm, np, P, (int)np, G.data()));
+  const SmallMulti sm = small_multi_from_gram(G, p, c->q);
+  if (sm.refused == 1) return fail(c, GPE_NOT_PD, Q_NOT_PD);   // (B needs Q alone)
+  std::memcpy(B_out, sm.B.data(), sm.B.size() * sizeof(double));
   return GPE_OK;
 }
 
@@ -2918,9 +3073,145 @@ int posterior_mean_impl(gpe_ctx* c, int64_t m, const double* Xs, const double* H
   return rc;
 }
 
+// k_post_mean_multi<DMAX, FAM, WIDE, NCB> for d inputs (launch_post_mean_fam's widths) and p
+// outputs in NCB blocks of 16
+template <int FAM, int NCB>
+void launch_post_mean_multi_ncb(int d, dim3 g, hipStream_t st, const PostMeanMultiArgs& a) {
+  const dim3 b(PM_LANES);
+  if (d > 32) hipLaunchKernelGGL((k_post_mean_multi<PM_WIDE, FAM, true, NCB>), g, b, 0, st, a);
+  else if (d <= 4) hipLaunchKernelGGL((k_post_mean_multi<4, FAM, false, NCB>), g, b, 0, st, a);
+  else if (d <= 8) hipLaunchKernelGGL((k_post_mean_multi<8, FAM, false, NCB>), g, b, 0, st, a);
+  else if (d <= 12) hipLaunchKernelGGL((k_post_mean_multi<12, FAM, false, NCB>), g, b, 0, st, a);
+  else if (d <= 16) hipLaunchKernelGGL((k_post_mean_multi<16, FAM, false, NCB>), g, b, 0, st, a);
+  else hipLaunchKernelGGL((k_post_mean_multi<32, FAM, false, NCB>), g, b, 0, st, a);
+}
+template <int FAM>
+void launch_post_mean_multi_fam(int d, dim3 g, hipStream_t st, const PostMeanMultiArgs& a) {
+  switch ((a.p + 15) / 16) {
+    case 1: launch_post_mean_multi_ncb<FAM, 1>(d, g, st, a); break;
+    case 2: launch_post_mean_multi_ncb<FAM, 2>(d, g, st, a); break;
+    case 3: launch_post_mean_multi_ncb<FAM, 3>(d, g, st, a); break;
+    default: launch_post_mean_multi_ncb<FAM, 4>(d, g, st, a); break;
+  }
+}
+
+// The posterior means of the p outputs of gpe_set_outputs (gpe_posterior_mean_multi):
+// Gamma = A^-1 (F - H B) by posterior_mean_impl's route to gamma (L^-1, then L^-T, of the
+// columns) into dWm, then posterior_mean_impl's pipeline with k_post_mean_multi and p values
+// per point.  Device workspace: the chunk's points twice and its (nseg + 1) p sums per point.
+int posterior_mean_multi_impl(gpe_ctx* c, int64_t m, const double* Xs, const double* Hs, const double* B,
+                              double* mean_out) {
+  CHK(check_ready(c));
+  if (!c->factor_valid) return fail(c, GPE_ERR_STATE, "no resident factor (call gpe_factor)");
+  if (!c->mo_p) return fail(c, GPE_ERR_STATE, "gpe_set_outputs has not been called for this data");
+  if (m <= 0 || !Xs || !Hs || !B || !mean_out)
+    return fail(c, GPE_ERR_ARG, "bad posterior_mean_multi args (m >= 1; Xs, Hs, B and mean_out not NULL)");
+  if (c->prof)   // phase 0: k_post_mean_multi's device time over the chunks, phase 1: the chunks
+    for (int i = 0; i < 8; ++i) c->phase_ms[i] = 0.0;
+  CHK(ensure_linv(c));
+  const int d = c->d, q = c->q, p = c->mo_p, P = p + q;
+  const long long np = c->n_pad, CH = c->mean_chunk;
+  auto pad_pts = [](long long v) { return ((v + PM_PTS - 1) / PM_PTS) * PM_PTS; };
+  static_assert(PM_PTS % PMM_PTS == 0, "a padded chunk is whole workgroups of k_post_mean_multi");
+  const long long mp0 = pad_pts(std::min<long long>(CH, m));
+  const int nrt = (int)(np / PM_RI), nseg = (nrt + PM_SEG - 1) / PM_SEG;
+  CHK(grow_buf(c, &c->dXs, &c->xs_cap, (size_t)mp0 * d));
+  CHK(grow_buf(c, &c->dXsw, &c->xsw_cap, (size_t)mp0 * d));
+  CHK(grow_buf(c, &c->dPmm, &c->pmm_cap, (size_t)(nseg + 1) * p * mp0));
+  double* dY = c->dPmm + (size_t)nseg * p * mp0;
+  CHK(ensure_pinned(c, 2 * (size_t)mp0 * d + 2 * (size_t)mp0 * p + d + (size_t)P * p + 64));
+  double* pin_in[2] = {c->hpin, c->hpin + (size_t)mp0 * d};
+  double* pin_out[2] = {pin_in[1] + (size_t)mp0 * d, pin_in[1] + (size_t)mp0 * d + (size_t)mp0 * p};
+  double* pin_dl = pin_out[1] + (size_t)mp0 * p;   // 1 / delta
+  double* pin_t = pin_dl + d;                      // [I; -B] (P x p, column-major)
+  for (int k = 0; k < d; ++k) pin_dl[k] = 1.0 / c->f_delta[k];
+  HIPCHK(c, hipMemcpyAsync(c->dinvdelta, pin_dl, d * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  std::memset(pin_t, 0, (size_t)P * p * sizeof(double));
+  for (int a = 0; a < p; ++a) {
+    pin_t[a + (size_t)a * P] = 1.0;
+    for (int i = 0; i < q; ++i) pin_t[(p + i) + (size_t)a * P] = -B[i * p + a];
+  }
+  HIPCHK(c, hipMemcpyAsync(c->dT2, pin_t, (size_t)P * p * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  CHK(apply_small(c, c->dFm, np, P, c->dT2, p, c->dR2m, np, (int)np, nullptr));
+  CHK(skinny(c, false, c->tr.B, np, c->NB, c->NB, true, c->dR2m, np, p, c->dZm, np));   // L^-1 (F - H B)
+  CHK(skinny(c, true, c->tr.B, np, c->NB, c->NB, true, c->dZm, np, p, c->dWm, np));    // Gamma
+  double coff, cdiag;
+  kernel_consts(c->f_kernel, c->f_nu, true, &coff, &cdiag);
+  const int fam = kernel_fam(c->f_kernel);
+  if (!c->ev_pipe[0])
+    for (hipEvent_t& e : c->ev_pipe) HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  auto dev_chunk = [&](long long s0, int slot) -> int {
+    const long long mc = std::min(CH, m - s0), mp = pad_pts(mc);
+    std::memcpy(pin_in[slot], Xs + s0 * d, (size_t)mc * d * sizeof(double));
+    // (k_scale_points reads the mc points only and writes zeros for the padded ones)
+    HIPCHK(c, hipMemcpyAsync(c->dXs, pin_in[slot], (size_t)mc * d * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_scale_points, dim3((unsigned)((mp * d + 255) / 256)), dim3(256), 0, c->stream, c->dXs,
+                       c->dinvdelta, d, (int)mc, (int)mp, c->dXsw);
+    HIPCHK(c, hipGetLastError());
+    // one workgroup per PMM_PTS points and segment of rows
+    PostMeanMultiArgs a;
+    a.xw = c->dXw; a.xsw = c->dXsw; a.gam = c->dWm; a.part = c->dPmm; a.coff = coff;
+    a.n = (int)c->n; a.np = (int)np; a.mp = (int)mp; a.d = d; a.p = p;
+    const dim3 grid((unsigned)(mp / PMM_PTS), (unsigned)nseg);
+    if (c->prof) HIPCHK(c, hipEventRecord(c->ev[4], c->stream));
+    with_fam(fam, [&](auto F) { launch_post_mean_multi_fam<decltype(F)::value>(d, grid, c->stream, a); });
+    HIPCHK(c, hipGetLastError());
+    if (c->prof) {   // (profiling only: one synchronisation per chunk)
+      float ms = 0.f;
+      HIPCHK(c, hipEventRecord(c->ev[5], c->stream));
+      HIPCHK(c, hipEventSynchronize(c->ev[5]));
+      (void)hipEventElapsedTime(&ms, c->ev[4], c->ev[5]);
+      c->phase_ms[0] += ms;
+      c->phase_ms[1] += 1.0;
+    }
+    hipLaunchKernelGGL(k_post_mean_multi_fin, dim3((unsigned)((mp * p + 255) / 256)), dim3(256), 0, c->stream,
+                       c->dPmm, nseg, p, (int)mp, dY);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(pin_out[slot], dY, (size_t)mc * p * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipEventRecord(c->ev_pipe[slot], c->stream));
+    return GPE_OK;
+  };
+  auto host_chunk = [&](long long s0, const double* y) {
+    const long long mc = std::min(CH, m - s0);
+    for (long long s = 0; s < mc; ++s) {
+      const double* hs = Hs + (s0 + s) * q;
+      for (int a = 0; a < p; ++a) {
+        double mu = y[s * p + a];
+        for (int i = 0; i < q; ++i) mu += hs[i] * B[i * p + a];
+        mean_out[(s0 + s) * p + a] = mu;
+      }
+    }
+  };
+  auto pipeline = [&]() -> int {
+    int slot = 0;
+    long long prev = -1;
+    for (long long s0 = 0; s0 < m; s0 += CH, slot ^= 1) {
+      CHK(dev_chunk(s0, slot));
+      if (prev >= 0) {
+        HIPCHK(c, hipEventSynchronize(c->ev_pipe[slot ^ 1]));
+        host_chunk(prev, pin_out[slot ^ 1]);
+      }
+      prev = s0;
+    }
+    HIPCHK(c, hipEventSynchronize(c->ev_pipe[slot ^ 1]));
+    host_chunk(prev, pin_out[slot ^ 1]);
+    return GPE_OK;
+  };
+  const int rc = pipeline();
+  // (a failed step may leave copies into the pinned slots queued: drained before the staging
+  // buffer can be reused or regrown)
+  if (rc != GPE_OK) (void)hipStreamSynchronize(c->stream);
+  return rc;
+}
+
 }  // namespace
 
 extern "C" {
+
+int gpe_posterior_mean_multi(gpe_ctx* c, int64_t m, const double* Xs, const double* Hs, const double* B,
+                             double* mean_out) {
+  return posterior_mean_multi_impl(c, m, Xs, Hs, B, mean_out);
+}
 
 int gpe_posterior(gpe_ctx* c, int64_t m, const double* Xs, const double* Hs, const double* beta,
                   double sigma, int32_t full_var, int32_t precision, double* mean_out, double* var_out) {

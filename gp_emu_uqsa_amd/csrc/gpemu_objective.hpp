@@ -95,6 +95,29 @@ inline ObjValue objective_value(const SmallAlgebra& sa, double logdetA, double n
   return v;
 }
 
+// The separable multi-output objective (gpe_objective_multi) from the small
+// algebra and log|A|: Sigma-hat = S / (n - q - 2) (p x p row-major),
+// llh = 1/2 [(n - q) log|Sigma-hat| + p log|A| + p log|Q|], the factor of the first p columns
+// of T2 (small_multi_t2) and the gradient's scale: the gradient is p times small_grad's (gscale
+// 1) of the contraction sums, the plain derivative of llh.
+constexpr const char* S_NOT_PD = "F^T P F not positive definite";
+struct ObjValueMulti {
+  double llh, cfac, gscale;
+  std::vector<double> Sigma;
+};
+inline ObjValueMulti objective_value_multi(const SmallMulti& sm, double logdetA, double n) {
+  ObjValueMulti v;
+  const int p = sm.p, q = sm.q;
+  const double dof = n - q - 2.0;
+  v.Sigma.resize((size_t)p * p);
+  for (size_t e = 0; e < v.Sigma.size(); ++e) v.Sigma[e] = sm.S[e] / dof;
+  const double logdetSigma = sm.logdetS - p * std::log(dof);
+  v.llh = 0.5 * ((n - q) * logdetSigma + p * logdetA + p * sm.logdetQ);
+  v.cfac = (n - q) / p;
+  v.gscale = p;
+  return v;
+}
+
 // the gradient from the d + 3 contraction sums (small_grad with the K-build's constants)
 inline void objective_grad(const double* red, int d, int kernel, double nu, bool fitnug, bool gp4ml, double gscale,
                            double s2, int n_hp, double* grad, bool std_r) {

@@ -87,6 +87,11 @@ SIGNATURES = {
     "gpe_posterior_grad": (_ct.c_int, [_VP, _ct.c_int64, _D, _D, _D, _ct.POINTER(_ct.c_int32), _D, _ct.c_double,
                                        _D, _D, _D, _D]),
     "gpe_posterior_mean": (_ct.c_int, [_VP, _ct.c_int64, _D, _D, _D, _D]),
+    "gpe_set_outputs": (_ct.c_int, [_VP, _ct.c_int32, _D]),
+    "gpe_objective_multi": (_ct.c_int, [_VP, _ct.c_int32, _D, _ct.c_int32, _ct.c_double, _ct.c_int32, _D, _D, _D,
+                                        _D]),
+    "gpe_beta_multi": (_ct.c_int, [_VP, _D]),
+    "gpe_posterior_mean_multi": (_ct.c_int, [_VP, _ct.c_int64, _D, _D, _D, _D]),
     "gpe_posterior_groups": (_ct.c_int, [_VP, _ct.c_int64, _ct.c_int32, _D, _D, _D, _ct.c_double, _D, _D]),
     "gpe_noise_sample": (_ct.c_int, [_VP, _ct.c_int64, _D, _D, _D, _ct.c_double, _D, _ct.c_double,
                                      _D, _ct.c_int32, _D, _D, _D]),
@@ -207,7 +212,9 @@ class Context:
         self._h = h
         self.device = device
         self.n = self.d = self.q = 0
+        self.p = 0                         # outputs of set_outputs (0: none)
         self._data_key = None
+        self._out_key = None
         self._factor_key = None
 
     # -- lifetime
@@ -245,6 +252,8 @@ class Context:
         self._keep = (X, f, H, rr)
         self._data_key = None
         self._factor_key = None
+        self._out_key = None               # (gpe_set_data drops the outputs)
+        self.p = 0
         self._check(self.lib.gpe_set_data(self._h, n, d, q, _ptr(X), _ptr(f), _ptr(H), _ptr(rr)),
                     "gpe_set_data")
         self.n, self.d, self.q = n, d, q
@@ -276,6 +285,62 @@ class Context:
             self._factor_key = None
             self.factor(kernel, delta, nu, s2, r_scale)
             self._factor_key = key
+
+    # -- p outputs sharing one correlation matrix (the separable multi-output emulator)
+    def set_outputs(self, F):
+        """The outputs F (n x p, 1 <= p <= 64) of the resident data (gpe_set_outputs); the
+        data's own f, its digest and the resident factor stay as they are."""
+        F = _f64(F)
+        if F.ndim == 1:
+            F = F.reshape(-1, 1)
+        if self.n and F.shape[0] != self.n:   # (without data the library answers GPE_ERR_STATE)
+            raise ValueError("set_outputs: F must have one row per training point")
+        self._out_key = None
+        self.p = 0
+        self._check(self.lib.gpe_set_outputs(self._h, F.shape[1], _ptr(F)), "gpe_set_outputs")
+        self.p = F.shape[1]
+
+    def ensure_outputs(self, F):
+        """set_outputs unless this exact F is already resident for the resident data."""
+        key = (self._digest(F), self._data_key)
+        if key != self._out_key or self._data_key is None:
+            self.set_outputs(F)
+            self._out_key = key
+
+    def objective_multi(self, kernel, hp, nu_fixed=0.0, want_grad=True):
+        """(llh, grad or None, Sigma (p x p), B (q x p)) of the multi-output objective
+        (gpe_objective_multi; hp = [delta, nu if fitted]); raises NotPositiveDefinite."""
+        hp = _f64(hp).ravel()
+        llh = _ct.c_double(0.0)
+        grad = _np.zeros(hp.size) if want_grad else None
+        Sigma = _np.zeros((max(self.p, 1), max(self.p, 1)))
+        B = _np.zeros((self.q, max(self.p, 1)))
+        self._factor_key = None            # the objective reuses the factor buffers
+        rc = self.lib.gpe_objective_multi(self._h, int(kernel), _ptr(hp), hp.size, float(nu_fixed),
+                                          1 if want_grad else 0, _ct.byref(llh), _ptr(grad), _ptr(Sigma), _ptr(B))
+        self._check(rc, "gpe_objective_multi")
+        return llh.value, grad, Sigma, B
+
+    def beta_multi(self):
+        """B (q x p) of the resident factor and outputs (gpe_beta_multi)."""
+        out = _np.zeros((self.q, max(self.p, 1)))
+        self._check(self.lib.gpe_beta_multi(self._h, _ptr(out)), "gpe_beta_multi")
+        return out
+
+    def posterior_mean_multi(self, Xs, Hs, B):
+        """The posterior means of the p outputs at Xs (m x p; gpe_posterior_mean_multi): one fused
+        kernel forms every correlation once for all p outputs; any m, the result does not
+        depend on the chunk length."""
+        Xs = _f64(Xs)
+        if Xs.ndim == 1:
+            Xs = Xs.reshape(-1, 1)
+        m = Xs.shape[0]
+        Hs = _f64(Hs, (m, self.q))
+        B = _f64(B, (self.q, max(self.p, 1)))
+        mean = _np.zeros((m, max(self.p, 1)))
+        self._check(self.lib.gpe_posterior_mean_multi(self._h, m, _ptr(Xs), _ptr(Hs), _ptr(B), _ptr(mean)),
+                    "gpe_posterior_mean_multi")
+        return mean
 
     # -- objective
     def objective(self, variant, kernel, hp, nu_fixed=0.0, want_grad=True):

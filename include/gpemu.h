@@ -36,7 +36,8 @@ extern "C" {
                                 gpe_device_synchronize, gpe_build_id;
                                 9: gpe_dist_local_rows takes the basis width q;
                                 10: gpe_ozaki_stats (gpe_loo, gpe_posterior_pivchol,
-                                gpe_posterior_imse, gpe_posterior_grad, gpe_posterior_mean, gpe_posterior_groups and the test
+                                gpe_posterior_imse, gpe_posterior_grad, gpe_posterior_mean, gpe_posterior_groups,
+                                gpe_set_outputs, gpe_objective_multi, gpe_beta_multi, gpe_posterior_mean_multi and the test
                                 hooks gpe_test_oz_product, gpe_test_oz_planes and gpe_test_gemm_group were
                                 added within 10: additions, nothing existing changed) */
 
@@ -214,6 +215,61 @@ int gpe_posterior_grad(gpe_ctx* ctx, int64_t m, const double* Xs, const double* 
  * GPE_NOT_PD if H^T A^-1 H is not positive definite, as gpe_posterior. */
 int gpe_posterior_mean(gpe_ctx* ctx, int64_t m, const double* Xs, const double* Hs,
                        const double* beta, double* mean_out);
+
+/* ---- Separable multi-output emulator (additions within ABI 10; MUCM's ProcBuildMultiOutputGPSep,
+ * Conti & O'Hagan 2010): p outputs F (n x p) share one correlation matrix A = what
+ * gpe_objective(GPE_MUCM, kernel, hp, nu_fixed) factors (s2 = 1, the same treatment of r), the
+ * p x p between-output covariance Sigma is estimated in closed form as MUCM's sigma-hat^2 is.
+ * With G = A^-1 H, Q = H^T G, P = A^-1 - G Q^-1 G^T, S = F^T P F, x = 2 log hp:
+ *   B = Q^-1 G^T F (q x p, the GLS coefficients, one column per output),
+ *   Sigma-hat = S / (n - q - 2),
+ *   llh = 1/2 [(n - q) log|Sigma-hat| + p log|A| + p log|Q|],
+ *   d llh / d x_k = 1/2 tr(M dA/dx_k),  M = p [A^-1 - W W^T],
+ *   W = [sqrt((n - q) / p) P F C^-T, G Kq^-T],  S = C C^T, Q = Kq Kq^T.
+ * At p = 1: llh and Sigma-hat are gpe_objective's llh_out and sigma2_out, and the gradient is its
+ * MUCM grad_out divided by sigma2_out (the plain derivative of llh, without the reference's
+ * sigma-hat^2 scaling).  Posterior at x with the factor gpe_factor(kernel, delta, nu, 1, r_scale):
+ * mean (p values) = h(x)^T B + K*(x)^T Gamma, Gamma = A^-1 (F - H B); the covariance of output a
+ * at x and output b at x' is Sigma-hat_ab c(x, x') with c what gpe_posterior(sigma = 1) returns.
+ * The existing entries are unaffected by resident outputs (same bits with and without). */
+
+/* The outputs: F n x p row-major for the resident data of gpe_set_data (whose own f stays as
+ * it is), 1 <= p <= 64.  Dropped by the next gpe_set_data.  GPE_ERR_STATE without data;
+ * GPE_ERR_ARG for a bad p, a NULL pointer or n < p + q + 3. */
+int gpe_set_outputs(gpe_ctx* ctx, int32_t p, const double* F);
+
+/* The objective above.  hp, n_hp and nu_fixed are read as gpe_objective reads them for GPE_MUCM
+ * (hp = [delta (d), nu if fitted]); every kernel code gpe_objective accepts.  Runs
+ * gpe_objective's general path (the K-build, the Cholesky with its int8 products, the skinny
+ * solves, the Gram, the contraction) at every n on the p + q columns of [F H]; want_grad == 0:
+ * no triangular inverse and no A^-1.  *llh_out; grad_out (n_hp, may be NULL when want_grad == 0);
+ * Sigma_out p x p row-major; B_out q x p row-major or NULL.
+ * GPE_NOT_PD as gpe_objective (failed pivot, bad length scale, H^T A^-1 H), and with
+ * "F^T P F not positive definite" when S is not: outputs linearly dependent given H.  For Q and
+ * S a pivot at or below 64 (p + q) eps times its column's diagonal entry of the Gram matrix of
+ * L^-1 [F H] counts as not positive: a repeated basis column or a duplicated output leaves a
+ * rounding residue of either sign where the exact pivot is zero.
+ * GPE_ERR_STATE without outputs. */
+int gpe_objective_multi(gpe_ctx* ctx, int32_t kernel, const double* hp, int32_t n_hp, double nu_fixed,
+                        int32_t want_grad, double* llh_out, double* grad_out, double* Sigma_out,
+                        double* B_out);
+
+/* B (q x p row-major) for the resident factor, as gpe_beta gives beta for f. */
+int gpe_beta_multi(gpe_ctx* ctx, double* B_out);
+
+/* The posterior means of the p outputs at m points: mean_out m x p row-major,
+ *   mean_sc = hs . B[:, c] + sum_i Gamma_ic K*_is,   Gamma = A^-1 (F - H B)
+ * from the resident factor (B q x p row-major, Xs and Hs as for gpe_posterior_mean).  One fused
+ * kernel (gpemu_postmean_multi.hpp) forms every K*_is once, with gpe_posterior_mean's arithmetic,
+ * and uses it for all p outputs on the fp64 matrix cores; nothing of size n x m is written.
+ * Any m; chunks (GPEMU_MEAN_CHUNK), the two pinned slots and the summation contract are
+ * gpe_posterior_mean's: segments of 192 training rows added in index order, a result that does not
+ * depend on the chunk length, the same bits on every call, no floating-point atomics.  The device
+ * workspace is (2 d + (n / 192 + 2) p) doubles per point of a chunk.
+ * GPE_ERR_STATE without a resident factor or without outputs; GPE_ERR_ARG for m <= 0 or a NULL
+ * pointer. */
+int gpe_posterior_mean_multi(gpe_ctx* ctx, int64_t m, const double* Xs, const double* Hs,
+                             const double* B, double* mean_out);
 
 /* Posterior covariance inside groups of G consecutive points (an addition within ABI 10): the
  * block diagonal of the m x m covariance in blocks of G, which the m^2 entries of full_var = 1
@@ -539,6 +595,9 @@ int gpe_posterior_imse(gpe_ctx* ctx, int64_t m, int64_t mc, const double* Xs, co
  * number of chunks (one synchronisation per chunk is added).
  * After gpe_posterior_mean: [0] k_post_mean's device time summed over the chunks, [1] the
  * number of chunks (one synchronisation per chunk is added).
+ * After gpe_posterior_mean_multi: [0] k_post_mean_multi's device time summed over the chunks, [1] the
+ * number of chunks (one synchronisation per chunk is added).  After gpe_objective_multi: as after
+ * gpe_objective.
  * After gpe_posterior_groups: [0] the device time of k_post_groupgram and k_post_groupcov
  * summed over the chunks, [1] the number of chunks (one synchronisation per chunk is added).
  * Only filled when profiling is on. */
