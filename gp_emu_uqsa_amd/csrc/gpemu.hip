@@ -21,6 +21,7 @@
 #include <limits>
 #include <string>
 #include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "../../include/gpemu.h"
@@ -28,6 +29,7 @@
 #include "gpemu_gemm_sched.hpp"
 #include "gpemu_chol_sched.hpp"
 #include "gpemu_objective.hpp"   // (with gpemu_small.hpp)
+#include "gpemu_chunk_pipe.hpp"
 #include "gpemu_tiny.hpp"
 #include "gpemu_snb.hpp"
 #include "gpemu_ozaki.hpp"
@@ -407,58 +409,6 @@ int ensure_small(gpe_ctx* c, size_t doubles) {
 }
 
 // ------------------------------------------------------------------ launches
-// k_pairs<DMAX, FAM> for the padded width dm (one of launch_pairs' widths)
-template <int FAM>
-static void launch_pairs_fam(int dm, dim3 g, dim3 b, hipStream_t st, const PairArgs& a2) {
-  switch (dm) {
-    case 2: hipLaunchKernelGGL((k_pairs<2, FAM>), g, b, 0, st, a2); break;
-    case 4: hipLaunchKernelGGL((k_pairs<4, FAM>), g, b, 0, st, a2); break;
-    case 6: hipLaunchKernelGGL((k_pairs<6, FAM>), g, b, 0, st, a2); break;
-    case 8: hipLaunchKernelGGL((k_pairs<8, FAM>), g, b, 0, st, a2); break;
-    case 10: hipLaunchKernelGGL((k_pairs<10, FAM>), g, b, 0, st, a2); break;
-    case 12: hipLaunchKernelGGL((k_pairs<12, FAM>), g, b, 0, st, a2); break;
-    case 16: hipLaunchKernelGGL((k_pairs<16, FAM>), g, b, 0, st, a2); break;
-    case 20: hipLaunchKernelGGL((k_pairs<20, FAM>), g, b, 0, st, a2); break;
-    case 24: hipLaunchKernelGGL((k_pairs<24, FAM>), g, b, 0, st, a2); break;
-    default: hipLaunchKernelGGL((k_pairs<32, FAM>), g, b, 0, st, a2); break;
-  }
-}
-
-// k_tiny<DM, FAM> / k_snb<DM, FAM> for the padded width DM >= d of the one-launch kernels
-template <int FAM>
-static void launch_tiny_fam(int d, size_t lds, hipStream_t st, const TinyArgs& a) {
-  const dim3 g(1 + TINY_NH), b(256);
-  if (d <= 4) hipLaunchKernelGGL((k_tiny<4, FAM>), g, b, lds, st, a);
-  else if (d <= 8) hipLaunchKernelGGL((k_tiny<8, FAM>), g, b, lds, st, a);
-  else if (d <= 12) hipLaunchKernelGGL((k_tiny<12, FAM>), g, b, lds, st, a);
-  else if (d <= 16) hipLaunchKernelGGL((k_tiny<16, FAM>), g, b, lds, st, a);
-  else hipLaunchKernelGGL((k_tiny<32, FAM>), g, b, lds, st, a);
-}
-template <int FAM>
-static void launch_snb_fam(int d, size_t lds, hipStream_t st, const SnbArgs& a) {
-  const dim3 g(1 + SNB_NH), b(256);
-  if (d <= 4) hipLaunchKernelGGL((k_snb<4, FAM>), g, b, lds, st, a);
-  else if (d <= 8) hipLaunchKernelGGL((k_snb<8, FAM>), g, b, lds, st, a);
-  else if (d <= 12) hipLaunchKernelGGL((k_snb<12, FAM>), g, b, lds, st, a);
-  else if (d <= 16) hipLaunchKernelGGL((k_snb<16, FAM>), g, b, lds, st, a);
-  else hipLaunchKernelGGL((k_snb<32, FAM>), g, b, lds, st, a);
-}
-// the dynamic LDS sizes of every width of one family's k_tiny and k_snb
-template <int FAM>
-static bool onel_lds_attr(int tiny_bytes, int snb_bytes) {
-  const auto at = hipFuncAttributeMaxDynamicSharedMemorySize;
-  return hipFuncSetAttribute((const void*)k_tiny<4, FAM>, at, tiny_bytes) == hipSuccess &&
-         hipFuncSetAttribute((const void*)k_tiny<8, FAM>, at, tiny_bytes) == hipSuccess &&
-         hipFuncSetAttribute((const void*)k_tiny<12, FAM>, at, tiny_bytes) == hipSuccess &&
-         hipFuncSetAttribute((const void*)k_tiny<16, FAM>, at, tiny_bytes) == hipSuccess &&
-         hipFuncSetAttribute((const void*)k_tiny<32, FAM>, at, tiny_bytes) == hipSuccess &&
-         hipFuncSetAttribute((const void*)k_snb<4, FAM>, at, snb_bytes) == hipSuccess &&
-         hipFuncSetAttribute((const void*)k_snb<8, FAM>, at, snb_bytes) == hipSuccess &&
-         hipFuncSetAttribute((const void*)k_snb<12, FAM>, at, snb_bytes) == hipSuccess &&
-         hipFuncSetAttribute((const void*)k_snb<16, FAM>, at, snb_bytes) == hipSuccess &&
-         hipFuncSetAttribute((const void*)k_snb<32, FAM>, at, snb_bytes) == hipSuccess;
-}
-
 // f(std::integral_constant<int, FAM>()) for the correlation family fam (a FAM_*; any other
 // value runs FAM_GAUSS, the kernels as they were before the Matern families): the one place
 // where a run-time family becomes a kernel's template argument
@@ -467,6 +417,42 @@ static void with_fam(int fam, F&& f) {
   if (fam == FAM_MATERN32) f(std::integral_constant<int, FAM_MATERN32>());
   else if (fam == FAM_MATERN52) f(std::integral_constant<int, FAM_MATERN52>());
   else f(std::integral_constant<int, FAM_GAUSS>());
+}
+
+// The register widths (DMAX) the kernels are instantiated for: the pair kernel's, and those of
+// the one-launch objectives and the fused posterior kernels (their d > 32 has a wide instance
+// of its own, chosen by the launcher).
+// (Widest first: the compiler emits the instances of a list's last width first, and the code
+// object keeps them in ascending order, as the chains of `d <= W` this replaces left them.)
+using PairWidths = std::integer_sequence<int, 32, 24, 20, 16, 12, 10, 8, 6, 4, 2>;
+using RegWidths = std::integer_sequence<int, 32, 16, 12, 8, 4>;
+// f(std::integral_constant<int, W>()) for the smallest W of the list with d <= W (zero-padded
+// dimensions cost one FMA each), the widest beyond it: the one place where a run-time input
+// width becomes a kernel's template argument
+template <int... Ws, class F>
+static void with_width(std::integer_sequence<int, Ws...>, int d, F&& f) {
+  int w = std::max({Ws...});
+  ((w = d <= Ws && Ws < w ? Ws : w), ...);
+  (void)((w == Ws && (f(std::integral_constant<int, Ws>()), true)) || ...);
+}
+
+// k_tiny<DM, FAM> / k_snb<DM, FAM> for the padded width DM >= d of the one-launch kernels
+template <int FAM>
+static void launch_tiny_fam(int d, size_t lds, hipStream_t st, const TinyArgs& a) {
+  const dim3 g(1 + TINY_NH), b(256);
+  with_width(RegWidths(), d, [&](auto W) { hipLaunchKernelGGL((k_tiny<decltype(W)::value, FAM>), g, b, lds, st, a); });
+}
+template <int FAM>
+static void launch_snb_fam(int d, size_t lds, hipStream_t st, const SnbArgs& a) {
+  const dim3 g(1 + SNB_NH), b(256);
+  with_width(RegWidths(), d, [&](auto W) { hipLaunchKernelGGL((k_snb<decltype(W)::value, FAM>), g, b, lds, st, a); });
+}
+// the dynamic LDS sizes of every width of one family's k_tiny and k_snb
+template <int FAM, int... Ws>
+static bool onel_lds_attr(std::integer_sequence<int, Ws...>, int tiny_bytes, int snb_bytes) {
+  const auto at = hipFuncAttributeMaxDynamicSharedMemorySize;
+  return ((hipFuncSetAttribute((const void*)k_tiny<Ws, FAM>, at, tiny_bytes) == hipSuccess) && ...) &&
+         ((hipFuncSetAttribute((const void*)k_snb<Ws, FAM>, at, snb_bytes) == hipSuccess) && ...);
 }
 
 int launch_pairs(gpe_ctx* c, const PairArgs& a, int nblocks) {
@@ -478,17 +464,16 @@ int launch_pairs(gpe_ctx* c, const PairArgs& a, int nblocks) {
     HIPCHK(c, hipGetLastError());
     return GPE_OK;
   }
-  // the smallest padded width >= d (zero-padded dimensions cost one FMA each)
-  static constexpr int widths[] = {2, 4, 6, 8, 10, 12, 16, 20, 24, 32};
-  int dm = 32;
-  for (int w : widths)
-    if (a.d <= w) { dm = w; break; }
   // launches of few tiles (small n) split each tile's columns over up to 4 workgroups
   // (same values: every entry is computed as before, by another workgroup)
   PairArgs a2 = a;
   while (a2.csplit < 4 && nblocks * a2.csplit * 2 <= 512) a2.csplit *= 2;
   const dim3 g(nblocks * a2.csplit), b(256);
-  with_fam(a.fam, [&](auto F) { launch_pairs_fam<decltype(F)::value>(dm, g, b, c->stream, a2); });
+  with_fam(a.fam, [&](auto F) {
+    with_width(PairWidths(), a.d, [&](auto W) {
+      hipLaunchKernelGGL((k_pairs<decltype(W)::value, decltype(F)::value>), g, b, 0, c->stream, a2);
+    });
+  });
   HIPCHK(c, hipGetLastError());
   return GPE_OK;
 }
@@ -1516,8 +1501,9 @@ gpe_ctx* gpe_create(int32_t device) {
                              (int)(DB_LDS_DOUBLES * sizeof(double))) == hipSuccess;
     const int tl = (G_LDS_LAUNCH_DOUBLES + 2 * TILE * TINY_ZP) * (int)sizeof(double);
     // every family's instances, not one chosen at run time as with_fam does
-    ok = ok && onel_lds_attr<FAM_GAUSS>(tl, SNB_LDS_DOUBLES * 8) && onel_lds_attr<FAM_MATERN32>(tl, SNB_LDS_DOUBLES * 8) &&
-         onel_lds_attr<FAM_MATERN52>(tl, SNB_LDS_DOUBLES * 8);
+    const RegWidths w;
+    ok = ok && onel_lds_attr<FAM_GAUSS>(w, tl, SNB_LDS_DOUBLES * 8) && onel_lds_attr<FAM_MATERN32>(w, tl, SNB_LDS_DOUBLES * 8) &&
+         onel_lds_attr<FAM_MATERN52>(w, tl, SNB_LDS_DOUBLES * 8);
     if (!ok) c->err = "hipFuncSetAttribute(max dynamic LDS) failed";
   }
   if (!ok) {
@@ -2341,7 +2327,49 @@ namespace {
 // pipeline holds two chunks in flight
 constexpr long long POST_CHUNK_FULL = 16384, POST_CHUNK_DIAG = 8192;
 
-inline long long pad_tile(long long m) { return ((m + TILE - 1) / TILE) * TILE; }
+inline long long pad_to(long long v, long long unit) { return ((v + unit - 1) / unit) * unit; }
+
+// 1 / delta of the resident factor, through d doubles of the pinned buffer, into c->dinvdelta
+int upload_invdelta(gpe_ctx* c, double* pin) {
+  for (int k = 0; k < c->d; ++k) pin[k] = 1.0 / c->f_delta[k];
+  HIPCHK(c, hipMemcpyAsync(c->dinvdelta, pin, c->d * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  return GPE_OK;
+}
+
+// The chunk pipelines' events, one per pinned result slot (made at the first use), and
+// chunk_pipeline's wait and drain for them
+int pipe_events(gpe_ctx* c) {
+  if (!c->ev_pipe[0])
+    for (hipEvent_t& e : c->ev_pipe) HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  return GPE_OK;
+}
+int pipe_wait(gpe_ctx* c, int slot) {
+  HIPCHK(c, hipEventSynchronize(c->ev_pipe[slot]));
+  return GPE_OK;
+}
+template <class Dev, class Host>
+int run_chunks(gpe_ctx* c, long long m, long long chunk, Dev&& dev, Host&& host) {
+  return chunk_pipeline(m, chunk, dev, [&](int slot) { return pipe_wait(c, slot); }, host,
+                        [&] { (void)hipStreamSynchronize(c->stream); });
+}
+
+// The per-chunk profiling bracket: the device time of what is queued between the two calls is
+// added to phase_ms[0], and 1 to phase_ms[1].  Nothing unless c->prof (profiling only: one
+// synchronisation per chunk).
+int chunk_prof_begin(gpe_ctx* c) {
+  if (c->prof) HIPCHK(c, hipEventRecord(c->ev[4], c->stream));
+  return GPE_OK;
+}
+int chunk_prof_end(gpe_ctx* c) {
+  if (!c->prof) return GPE_OK;
+  float ms = 0.f;
+  HIPCHK(c, hipEventRecord(c->ev[5], c->stream));
+  HIPCHK(c, hipEventSynchronize(c->ev[5]));
+  (void)hipEventElapsedTime(&ms, c->ev[4], c->ev[5]);
+  c->phase_ms[0] += ms;
+  c->phase_ms[1] += 1.0;
+  return GPE_OK;
+}
 
 // where the variance goes (on the device: column-major, ld = m rounded up to TILE, identity
 // padding)
@@ -2383,11 +2411,10 @@ template <int FAM, bool WB>
 void launch_post_grad_fam(int d, dim3 g, hipStream_t st, const PostGradArgs& a) {
   const dim3 b(PG_PTS);
   if (d > 32) hipLaunchKernelGGL((k_post_grad<PG_WIDE, FAM, true, WB>), g, b, 0, st, a);
-  else if (d <= 4) hipLaunchKernelGGL((k_post_grad<4, FAM, false, WB>), g, b, 0, st, a);
-  else if (d <= 8) hipLaunchKernelGGL((k_post_grad<8, FAM, false, WB>), g, b, 0, st, a);
-  else if (d <= 12) hipLaunchKernelGGL((k_post_grad<12, FAM, false, WB>), g, b, 0, st, a);
-  else if (d <= 16) hipLaunchKernelGGL((k_post_grad<16, FAM, false, WB>), g, b, 0, st, a);
-  else hipLaunchKernelGGL((k_post_grad<32, FAM, false, WB>), g, b, 0, st, a);
+  else
+    with_width(RegWidths(), d, [&](auto W) {
+      hipLaunchKernelGGL((k_post_grad<decltype(W)::value, FAM, false, WB>), g, b, 0, st, a);
+    });
 }
 
 template <bool WB>
@@ -2432,8 +2459,8 @@ struct Posterior : PostReq {
         groups(var == PostVar::GROUPS), d(c->d), q(c->q), P(q + 1), kq(((q + 15) / 16) * 16), np(c->n_pad),
         // (whole groups per chunk: a group never straddles two)
         CHUNK(full ? POST_CHUNK_FULL : groups ? (POST_CHUNK_DIAG / group) * group : POST_CHUNK_DIAG),
-        big(full && m > CHUNK), mtot(pad_tile(m)),
-        mp0(pad_tile(std::min<long long>(CHUNK, m))), grad(r.dmean_out != nullptr) {}
+        big(full && m > CHUNK), mtot(pad_to(m, TILE)),
+        mp0(pad_to(std::min<long long>(CHUNK, m), TILE)), grad(r.dmean_out != nullptr) {}
 
   // Setup: the fp32 copy of L^-1 where the fp32 product needs it, [gamma, G] =
   // A^-1 [f - H beta, H] (in dWa; L^-1 [..] in dZ), Kq and its inverse, the kernel's constants.
@@ -2499,8 +2526,7 @@ struct Posterior : PostReq {
     pin_in[0] = c->hpin, pin_in[1] = pin_in[0] + (size_t)mp0 * d;
     pin_out[0] = pin_in[1] + (size_t)mp0 * d, pin_out[1] = pin_out[0] + rs;
     double* pin_dl = pin_out[1] + rs;   // 1 / delta
-    for (int k = 0; k < d; ++k) pin_dl[k] = 1.0 / c->f_delta[k];
-    HIPCHK(c, hipMemcpyAsync(c->dinvdelta, pin_dl, d * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    CHK(upload_invdelta(c, pin_dl));
     if (grad) {
       for (int i = 0; i < 2; ++i) {
         gpin_in[i] = pin_dl + d + i * gsl;
@@ -2508,15 +2534,13 @@ struct Posterior : PostReq {
       }
       CHK(grad_workspace());
     }
-    if (!c->ev_pipe[0])
-      for (hipEvent_t& e : c->ev_pipe) HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    return GPE_OK;
+    return pipe_events(c);
   }
 
   // One chunk's device work: its points from the pinned slot pin, K*, Y = K*^T [gamma, G]
   // into dY, V = L^-1 K* into vdst (fp32 path: into dK32).
   int dev_chunk(long long s0, double* pin, double* dY, double* vdst) {
-    const long long mc = std::min(CHUNK, m - s0), mp = pad_tile(mc);
+    const long long mc = std::min(CHUNK, m - s0), mp = pad_to(mc, TILE);
     const int mt = (int)(mp / TILE);
     std::memset(pin, 0, (size_t)mp * d * sizeof(double));
     std::memcpy(pin, Xs + s0 * d, (size_t)mc * d * sizeof(double));
@@ -2579,7 +2603,7 @@ struct Posterior : PostReq {
   // from chunk to chunk: Q^-1 = Kq^-T Kq^-1, beta, hdim, and G = dWa's columns 1..q copied
   // into kq zero-padded columns, the first operand of the rank-q update.
   int grad_workspace() {
-    const long long mpl = pad_tile(m - ((m - 1) / CHUNK) * CHUNK);   // the last chunk
+    const long long mpl = pad_to(m - ((m - 1) / CHUNK) * CHUNK, TILE);   // the last chunk
     const size_t nhd = (size_t)q / 2 + 1;
     // (a and b sums of every split; a short last chunk may split its rows further than the first)
     const size_t npart =
@@ -2623,7 +2647,7 @@ struct Posterior : PostReq {
   // L^-T V + G tau^T in dW3, the fused sums, the epilogue, and the copy of [dmean, dvar] into
   // the pinned slot.  L^-1 is read K-contiguous from its row tile on, as the LAUUM reads it.
   int grad_chunk(long long s0, int slot, const double* dY) {
-    const long long mc = std::min(CHUNK, m - s0), mp = pad_tile(mc);
+    const long long mc = std::min(CHUNK, m - s0), mp = pad_to(mc, TILE);
     const int mt = (int)(mp / TILE);
     const size_t hq = (size_t)mc * q, md = (size_t)mp * d;
     double* hin = gpin_in[slot];
@@ -2644,18 +2668,11 @@ struct Posterior : PostReq {
     a.xw = c->dXw; a.xsw = c->dXsw; a.gam = c->dWa; a.U = wb ? c->dW3 : nullptr; a.ldu = np;
     a.part = g.part; a.n = (int)c->n; a.np = (int)np; a.mp = (int)mp; a.d = d; a.nsplit = grad_nsplit(mp);
     const dim3 grid((unsigned)(mp / PG_PTS), (unsigned)a.nsplit, (unsigned)(d > 32 ? (d + PG_WIDE - 1) / PG_WIDE : 1));
-    if (c->prof) HIPCHK(c, hipEventRecord(c->ev[4], c->stream));
+    CHK(chunk_prof_begin(c));
     if (wb) launch_post_grad<true>(fam, d, grid, c->stream, a);
     else launch_post_grad<false>(fam, d, grid, c->stream, a);
     HIPCHK(c, hipGetLastError());
-    if (c->prof) {   // (profiling only: one synchronisation per chunk)
-      float ms = 0.f;
-      HIPCHK(c, hipEventRecord(c->ev[5], c->stream));
-      HIPCHK(c, hipEventSynchronize(c->ev[5]));
-      (void)hipEventElapsedTime(&ms, c->ev[4], c->ev[5]);
-      c->phase_ms[0] += ms;
-      c->phase_ms[1] += 1.0;
-    }
+    CHK(chunk_prof_end(c));
     PostGradFin f;
     f.part = g.part; f.invdelta = c->dinvdelta; f.dHs = g.dHs; f.hdim = g.hdim; f.beta = g.beta; f.tau = g.tau;
     f.dmean = g.dmean; f.dvar = wb ? g.dvar : nullptr; f.coff = coff; f.s2 = s2;
@@ -2690,7 +2707,7 @@ struct Posterior : PostReq {
   // into means and variances, so the GPU does not idle on the host between chunks.
   int diag() {
     auto host_chunk = [&](long long s0, const double* out) {
-      const long long mc = std::min(CHUNK, m - s0), mp = pad_tile(mc);
+      const long long mc = std::min(CHUNK, m - s0), mp = pad_to(mc, TILE);
       const double* nrm = out + (size_t)mp * P;
       for (long long s = 0; s < mc; ++s) {
         double tq = 0.0;   // |T Kq^-T|^2
@@ -2704,42 +2721,28 @@ struct Posterior : PostReq {
       std::memcpy(dmean_out + s0 * d, out, cnt * sizeof(double));
       if (dvar_out) std::memcpy(dvar_out + s0 * d, out + (size_t)mp0 * d, cnt * sizeof(double));
     };
-    int slot = 0;
-    long long prev = -1;
-    auto pipeline = [&]() -> int {
-      for (long long s0 = 0; s0 < m; s0 += CHUNK, slot ^= 1) {
-        const long long mp = pad_tile(std::min(CHUNK, m - s0));
-        double* dY = c->dsmall + slot * rs;
-        double* dn = dY + (size_t)mp * P;
-        CHK(dev_chunk(s0, pin_in[slot], dY, c->dW2));
-        if (f32 && !ozp)
-          hipLaunchKernelGGL(k_colnorm2_f32, dim3((unsigned)((mp + 3) / 4)), dim3(256), 0, c->stream,
-                             c->dK32 + (size_t)np * mp, np, (int)np, (int)mp, dn);
-        else
-          hipLaunchKernelGGL(k_colnorm2, dim3((unsigned)((mp + 3) / 4)), dim3(256), 0, c->stream, c->dW2, np,
-                             (int)np, (int)mp, dn);
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipMemcpyAsync(pin_out[slot], dY, ((size_t)mp * P + mp) * sizeof(double), hipMemcpyDeviceToHost,
-                                 c->stream));
-        if (grad) CHK(grad_chunk(s0, slot, dY));
-        HIPCHK(c, hipEventRecord(c->ev_pipe[slot], c->stream));
-        if (prev >= 0) {
-          HIPCHK(c, hipEventSynchronize(c->ev_pipe[slot ^ 1]));
-          host_chunk(prev, pin_out[slot ^ 1]);
-          if (grad) host_grad(prev, gpin_out[slot ^ 1]);
-        }
-        prev = s0;
-      }
-      HIPCHK(c, hipEventSynchronize(c->ev_pipe[slot ^ 1]));
-      host_chunk(prev, pin_out[slot ^ 1]);
-      if (grad) host_grad(prev, gpin_out[slot ^ 1]);
+    auto dev = [&](long long s0, int slot) -> int {
+      const long long mp = pad_to(std::min(CHUNK, m - s0), TILE);
+      double* dY = c->dsmall + slot * rs;
+      double* dn = dY + (size_t)mp * P;
+      CHK(dev_chunk(s0, pin_in[slot], dY, c->dW2));
+      if (f32 && !ozp)
+        hipLaunchKernelGGL(k_colnorm2_f32, dim3((unsigned)((mp + 3) / 4)), dim3(256), 0, c->stream,
+                           c->dK32 + (size_t)np * mp, np, (int)np, (int)mp, dn);
+      else
+        hipLaunchKernelGGL(k_colnorm2, dim3((unsigned)((mp + 3) / 4)), dim3(256), 0, c->stream, c->dW2, np,
+                           (int)np, (int)mp, dn);
+      HIPCHK(c, hipGetLastError());
+      HIPCHK(c, hipMemcpyAsync(pin_out[slot], dY, ((size_t)mp * P + mp) * sizeof(double), hipMemcpyDeviceToHost,
+                               c->stream));
+      if (grad) CHK(grad_chunk(s0, slot, dY));
+      HIPCHK(c, hipEventRecord(c->ev_pipe[slot], c->stream));
       return GPE_OK;
     };
-    const int rc = pipeline();
-    // (a failed step may leave copies into the pinned slots queued: drained before the
-    // staging buffer can be reused or regrown)
-    if (rc != GPE_OK) (void)hipStreamSynchronize(c->stream);
-    return rc;
+    return run_chunks(c, m, CHUNK, dev, [&](long long s0, int slot) {
+      host_chunk(s0, pin_out[slot]);
+      if (grad) host_grad(s0, gpin_out[slot]);
+    });
   }
 
   // k_post_groupgram<NT> for items of cw columns
@@ -2760,7 +2763,7 @@ struct Posterior : PostReq {
     const long long GG = (long long)G * G;
     std::vector<double> Tg((size_t)G * q);
     auto host_chunk = [&](long long s0, const double* out) {
-      const long long mc = std::min(CHUNK, m - s0), mp = pad_tile(mc);
+      const long long mc = std::min(CHUNK, m - s0), mp = pad_to(mc, TILE);
       const double* cv = out + (size_t)mp * P;
       for (long long g = 0; g < mc / G; ++g) {
         for (int a = 0; a < G; ++a)
@@ -2777,50 +2780,30 @@ struct Posterior : PostReq {
           }
       }
     };
-    int slot = 0;
-    long long prev = -1;
-    auto pipeline = [&]() -> int {
-      for (long long s0 = 0; s0 < m; s0 += CHUNK, slot ^= 1) {
-        const long long mc = std::min(CHUNK, m - s0), mp = pad_tile(mc);
-        double* dY = c->dsmall + slot * rs;
-        double* dcov = dY + (size_t)mp * P;
-        CHK(dev_chunk(s0, pin_in[slot], dY, c->dW2));
-        GroupGramArgs a;
-        a.V = c->dW2; a.ldv = np; a.part = c->dPgc; a.np = (int)np; a.G = G; a.gpi = pgc_gpi(G);
-        a.ngroups = (int)(mc / G);
-        GroupCovArgs f;
-        f.part = c->dPgc; f.xsw = c->dXsw; f.cov = dcov; f.coff = coff; f.cdiag = cdiag;
-        f.nseg = pgc_nseg(np); f.ngroups = a.ngroups; f.G = G; f.d = d;
-        if (c->prof) HIPCHK(c, hipEventRecord(c->ev[4], c->stream));
-        launch_groupgram(a.gpi * G, dim3((unsigned)((a.ngroups + a.gpi - 1) / a.gpi), (unsigned)f.nseg), a);
-        HIPCHK(c, hipGetLastError());
-        const dim3 fg((unsigned)((a.ngroups * GG + 255) / 256));
-        with_fam(fam, [&](auto F) { hipLaunchKernelGGL(k_post_groupcov<decltype(F)::value>, fg, dim3(256), 0, c->stream, f); });
-        HIPCHK(c, hipGetLastError());
-        if (c->prof) {   // (profiling only: one synchronisation per chunk)
-          float ms = 0.f;
-          HIPCHK(c, hipEventRecord(c->ev[5], c->stream));
-          HIPCHK(c, hipEventSynchronize(c->ev[5]));
-          (void)hipEventElapsedTime(&ms, c->ev[4], c->ev[5]);
-          c->phase_ms[0] += ms;
-          c->phase_ms[1] += 1.0;
-        }
-        HIPCHK(c, hipMemcpyAsync(pin_out[slot], dY, ((size_t)mp * P + (size_t)mc * G) * sizeof(double),
-                                 hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipEventRecord(c->ev_pipe[slot], c->stream));
-        if (prev >= 0) {
-          HIPCHK(c, hipEventSynchronize(c->ev_pipe[slot ^ 1]));
-          host_chunk(prev, pin_out[slot ^ 1]);
-        }
-        prev = s0;
-      }
-      HIPCHK(c, hipEventSynchronize(c->ev_pipe[slot ^ 1]));
-      host_chunk(prev, pin_out[slot ^ 1]);
+    auto dev = [&](long long s0, int slot) -> int {
+      const long long mc = std::min(CHUNK, m - s0), mp = pad_to(mc, TILE);
+      double* dY = c->dsmall + slot * rs;
+      double* dcov = dY + (size_t)mp * P;
+      CHK(dev_chunk(s0, pin_in[slot], dY, c->dW2));
+      GroupGramArgs a;
+      a.V = c->dW2; a.ldv = np; a.part = c->dPgc; a.np = (int)np; a.G = G; a.gpi = pgc_gpi(G);
+      a.ngroups = (int)(mc / G);
+      GroupCovArgs f;
+      f.part = c->dPgc; f.xsw = c->dXsw; f.cov = dcov; f.coff = coff; f.cdiag = cdiag;
+      f.nseg = pgc_nseg(np); f.ngroups = a.ngroups; f.G = G; f.d = d;
+      CHK(chunk_prof_begin(c));
+      launch_groupgram(a.gpi * G, dim3((unsigned)((a.ngroups + a.gpi - 1) / a.gpi), (unsigned)f.nseg), a);
+      HIPCHK(c, hipGetLastError());
+      const dim3 fg((unsigned)((a.ngroups * GG + 255) / 256));
+      with_fam(fam, [&](auto F) { hipLaunchKernelGGL(k_post_groupcov<decltype(F)::value>, fg, dim3(256), 0, c->stream, f); });
+      HIPCHK(c, hipGetLastError());
+      CHK(chunk_prof_end(c));
+      HIPCHK(c, hipMemcpyAsync(pin_out[slot], dY, ((size_t)mp * P + (size_t)mc * G) * sizeof(double),
+                               hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(c, hipEventRecord(c->ev_pipe[slot], c->stream));
       return GPE_OK;
     };
-    const int rc = pipeline();
-    if (rc != GPE_OK) (void)hipStreamSynchronize(c->stream);   // (as diag())
-    return rc;
+    return run_chunks(c, m, CHUNK, dev, [&](long long s0, int slot) { host_chunk(s0, pin_out[slot]); });
   }
 
   // One block of the covariance, dst (ld) = s2 (A** - V_R^T V_C + T_R T_C^T) for the points R
@@ -2856,7 +2839,7 @@ struct Posterior : PostReq {
     std::vector<double> Th;   // every point's T Kq^-T (mtot x kq column-major)
     if (big) Th.assign((size_t)mtot * kq, 0.0);
     for (long long s0 = 0; s0 < m; s0 += CHUNK) {
-      const long long mc = std::min(CHUNK, m - s0), mp = pad_tile(mc);
+      const long long mc = std::min(CHUNK, m - s0), mp = pad_to(mc, TILE);
       double* dY = c->dsmall;
       CHK(dev_chunk(s0, pin_in[0], dY, big ? c->dVall + s0 * np : c->dW2));
       std::vector<double> Yh((size_t)mp * P);
@@ -2905,7 +2888,7 @@ struct Posterior : PostReq {
     std::vector<double> hc;
     auto side = [&](long long s0) {
       const long long mc = std::min(CHUNK, m - s0);
-      return CovSide{c->dXall + s0 * d, c->dVall + s0 * np, c->dTall + s0, mtot, s0, mc, pad_tile(mc)};
+      return CovSide{c->dXall + s0 * d, c->dVall + s0 * np, c->dTall + s0, mtot, s0, mc, pad_to(mc, TILE)};
     };
     for (long long a0 = 0; a0 < m; a0 += CHUNK)
       for (long long b0 = a0; b0 < m; b0 += CHUNK) {
@@ -2970,107 +2953,10 @@ template <int FAM>
 void launch_post_mean_fam(int d, dim3 g, hipStream_t st, const PostMeanArgs& a) {
   const dim3 b(PM_LANES);
   if (d > 32) hipLaunchKernelGGL((k_post_mean<PM_WIDE, FAM, true>), g, b, 0, st, a);
-  else if (d <= 4) hipLaunchKernelGGL((k_post_mean<4, FAM, false>), g, b, 0, st, a);
-  else if (d <= 8) hipLaunchKernelGGL((k_post_mean<8, FAM, false>), g, b, 0, st, a);
-  else if (d <= 12) hipLaunchKernelGGL((k_post_mean<12, FAM, false>), g, b, 0, st, a);
-  else if (d <= 16) hipLaunchKernelGGL((k_post_mean<16, FAM, false>), g, b, 0, st, a);
-  else hipLaunchKernelGGL((k_post_mean<32, FAM, false>), g, b, 0, st, a);
-}
-
-// The posterior mean alone (gpe_posterior_mean): gamma from Posterior::setup(), then per chunk
-// the points' upload, k_scale_points, k_post_mean and k_post_mean_fin, and the copy of y into a
-// pinned slot; the host adds hs . beta as Posterior::point does.  Two pinned slots of points
-// and two of results: chunk i + 1's upload and kernels are queued before the host finishes
-// chunk i.  Device workspace: the chunk's points twice and its nseg + 1 sums per point.
-int posterior_mean_impl(gpe_ctx* c, int64_t m, const double* Xs, const double* Hs, const double* beta,
-                        double* mean_out) {
-  CHK(check_ready(c));
-  if (!c->factor_valid) return fail(c, GPE_ERR_STATE, "no resident factor (call gpe_factor)");
-  if (m <= 0 || !Xs || !Hs || !beta || !mean_out)
-    return fail(c, GPE_ERR_ARG, "bad posterior_mean args (m >= 1; Xs, Hs, beta and mean_out not NULL)");
-  if (c->prof)   // phase 0: k_post_mean's device time over the chunks, phase 1: the chunks
-    for (int i = 0; i < 8; ++i) c->phase_ms[i] = 0.0;
-  CHK(ensure_linv(c));
-  PostReq r{m, Xs, Hs, beta, 1.0, 64, mean_out, PostVar::DIAG, nullptr};
-  Posterior S(c, r);
-  CHK(S.setup());   // gamma in dWa's first column, coff, fam
-  const int d = c->d, q = c->q;
-  const long long np = c->n_pad, CH = c->mean_chunk;
-  auto pad_pts = [](long long v) { return ((v + PM_PTS - 1) / PM_PTS) * PM_PTS; };
-  const long long mp0 = pad_pts(std::min<long long>(CH, m));
-  const int nrt = (int)(np / PM_RI), nseg = (nrt + PM_SEG - 1) / PM_SEG;
-  CHK(grow_buf(c, &c->dXs, &c->xs_cap, (size_t)mp0 * d));
-  CHK(grow_buf(c, &c->dXsw, &c->xsw_cap, (size_t)mp0 * d));
-  CHK(grow_buf(c, &c->dPm, &c->pm_cap, (size_t)(nseg + 1) * mp0));
-  double* dY = c->dPm + (size_t)nseg * mp0;
-  CHK(ensure_pinned(c, 2 * (size_t)mp0 * d + 2 * (size_t)mp0 + d + 64));
-  double* pin_in[2] = {c->hpin, c->hpin + (size_t)mp0 * d};
-  double* pin_out[2] = {pin_in[1] + (size_t)mp0 * d, pin_in[1] + (size_t)mp0 * d + mp0};
-  double* pin_dl = pin_out[1] + mp0;   // 1 / delta
-  for (int k = 0; k < d; ++k) pin_dl[k] = 1.0 / c->f_delta[k];
-  HIPCHK(c, hipMemcpyAsync(c->dinvdelta, pin_dl, d * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  if (!c->ev_pipe[0])
-    for (hipEvent_t& e : c->ev_pipe) HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  auto dev_chunk = [&](long long s0, int slot) -> int {
-    const long long mc = std::min(CH, m - s0), mp = pad_pts(mc);
-    std::memcpy(pin_in[slot], Xs + s0 * d, (size_t)mc * d * sizeof(double));
-    // (k_scale_points reads the mc points only and writes zeros for the padded ones)
-    HIPCHK(c, hipMemcpyAsync(c->dXs, pin_in[slot], (size_t)mc * d * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(k_scale_points, dim3((unsigned)((mp * d + 255) / 256)), dim3(256), 0, c->stream, c->dXs,
-                       c->dinvdelta, d, (int)mc, (int)mp, c->dXsw);
-    HIPCHK(c, hipGetLastError());
-    // one workgroup per column of points and segment of rows
-    PostMeanArgs a;
-    a.xw = c->dXw; a.xsw = c->dXsw; a.gam = c->dWa; a.part = c->dPm; a.coff = S.coff;
-    a.n = (int)c->n; a.np = (int)np; a.mp = (int)mp; a.d = d;
-    const dim3 grid((unsigned)(mp / (d > 32 ? PM_LANES : PM_PTS)), (unsigned)nseg);
-    if (c->prof) HIPCHK(c, hipEventRecord(c->ev[4], c->stream));
-    with_fam(S.fam, [&](auto F) { launch_post_mean_fam<decltype(F)::value>(d, grid, c->stream, a); });
-    HIPCHK(c, hipGetLastError());
-    if (c->prof) {   // (profiling only: one synchronisation per chunk)
-      float ms = 0.f;
-      HIPCHK(c, hipEventRecord(c->ev[5], c->stream));
-      HIPCHK(c, hipEventSynchronize(c->ev[5]));
-      (void)hipEventElapsedTime(&ms, c->ev[4], c->ev[5]);
-      c->phase_ms[0] += ms;
-      c->phase_ms[1] += 1.0;
-    }
-    hipLaunchKernelGGL(k_post_mean_fin, dim3((unsigned)((mp + 255) / 256)), dim3(256), 0, c->stream, c->dPm, nseg,
-                       (int)mp, dY);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(pin_out[slot], dY, (size_t)mc * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipEventRecord(c->ev_pipe[slot], c->stream));
-    return GPE_OK;
-  };
-  auto host_chunk = [&](long long s0, const double* y) {
-    const long long mc = std::min(CH, m - s0);
-    for (long long s = 0; s < mc; ++s) {
-      const double* hs = Hs + (s0 + s) * q;
-      double mu = y[s];
-      for (int i = 0; i < q; ++i) mu += hs[i] * beta[i];
-      mean_out[s0 + s] = mu;
-    }
-  };
-  auto pipeline = [&]() -> int {
-    int slot = 0;
-    long long prev = -1;
-    for (long long s0 = 0; s0 < m; s0 += CH, slot ^= 1) {
-      CHK(dev_chunk(s0, slot));
-      if (prev >= 0) {
-        HIPCHK(c, hipEventSynchronize(c->ev_pipe[slot ^ 1]));
-        host_chunk(prev, pin_out[slot ^ 1]);
-      }
-      prev = s0;
-    }
-    HIPCHK(c, hipEventSynchronize(c->ev_pipe[slot ^ 1]));
-    host_chunk(prev, pin_out[slot ^ 1]);
-    return GPE_OK;
-  };
-  const int rc = pipeline();
-  // (a failed step may leave copies into the pinned slots queued: drained before the staging
-  // buffer can be reused or regrown)
-  if (rc != GPE_OK) (void)hipStreamSynchronize(c->stream);
-  return rc;
+  else
+    with_width(RegWidths(), d, [&](auto W) {
+      hipLaunchKernelGGL((k_post_mean<decltype(W)::value, FAM, false>), g, b, 0, st, a);
+    });
 }
 
 // k_post_mean_multi<DMAX, FAM, WIDE, NCB> for d inputs (launch_post_mean_fam's widths) and p
@@ -3079,11 +2965,10 @@ template <int FAM, int NCB>
 void launch_post_mean_multi_ncb(int d, dim3 g, hipStream_t st, const PostMeanMultiArgs& a) {
   const dim3 b(PM_LANES);
   if (d > 32) hipLaunchKernelGGL((k_post_mean_multi<PM_WIDE, FAM, true, NCB>), g, b, 0, st, a);
-  else if (d <= 4) hipLaunchKernelGGL((k_post_mean_multi<4, FAM, false, NCB>), g, b, 0, st, a);
-  else if (d <= 8) hipLaunchKernelGGL((k_post_mean_multi<8, FAM, false, NCB>), g, b, 0, st, a);
-  else if (d <= 12) hipLaunchKernelGGL((k_post_mean_multi<12, FAM, false, NCB>), g, b, 0, st, a);
-  else if (d <= 16) hipLaunchKernelGGL((k_post_mean_multi<16, FAM, false, NCB>), g, b, 0, st, a);
-  else hipLaunchKernelGGL((k_post_mean_multi<32, FAM, false, NCB>), g, b, 0, st, a);
+  else
+    with_width(RegWidths(), d, [&](auto W) {
+      hipLaunchKernelGGL((k_post_mean_multi<decltype(W)::value, FAM, false, NCB>), g, b, 0, st, a);
+    });
 }
 template <int FAM>
 void launch_post_mean_multi_fam(int d, dim3 g, hipStream_t st, const PostMeanMultiArgs& a) {
@@ -3095,10 +2980,109 @@ void launch_post_mean_multi_fam(int d, dim3 g, hipStream_t st, const PostMeanMul
   }
 }
 
+// What gpe_posterior_mean and gpe_posterior_mean_multi differ in, for posterior_means()
+struct MeanKind {
+  int p;                // values per point
+  double** part;        // the partial sums, (nseg + 1) p per point: c->dPm, c->dPmm
+  size_t* part_cap;
+  const double* coef;   // the host adds hs . coef: beta (q), B (q x p row-major)
+  size_t pin_route;     // pinned doubles behind 1 / delta for the route to gamma
+};
+
+// The posterior means of one kind at m points, with gamma resident or queued by route().  Per
+// chunk: the points' upload, k_scale_points, kernels(mp, nseg, part, dY, coff, fam) -- the
+// kind's fused kernel inside the profiling bracket and its finishing kernel -- and the copy of
+// y into a pinned slot; the host adds hs . coef as Posterior::point does.  Two pinned slots of
+// points and two of results: chunk i + 1's upload and kernels are queued before the host
+// finishes chunk i.  Device workspace: the chunk's points twice and its (nseg + 1) p sums per
+// point.  route(pin) runs behind the upload of 1 / delta, with pin_route pinned doubles.
+// P1: the kind's p where the compiler is to know it (1: the host's loop over 1e6 points is then
+// the single-output one, measurably faster than the general one at p = 1), 0 for any p.
+template <int P1, class Route, class Kernels>
+int posterior_means(gpe_ctx* c, const MeanKind& k, int64_t m, const double* Xs, const double* Hs, double* mean_out,
+                    Route&& route, Kernels&& kernels) {
+  const int d = c->d, q = c->q, p = P1 ? P1 : k.p;
+  const long long np = c->n_pad, CH = c->mean_chunk;
+  const long long mp0 = pad_to(std::min<long long>(CH, m), PM_PTS);
+  const int nrt = (int)(np / PM_RI), nseg = (nrt + PM_SEG - 1) / PM_SEG;
+  CHK(grow_buf(c, &c->dXs, &c->xs_cap, (size_t)mp0 * d));
+  CHK(grow_buf(c, &c->dXsw, &c->xsw_cap, (size_t)mp0 * d));
+  CHK(grow_buf(c, k.part, k.part_cap, (size_t)(nseg + 1) * p * mp0));
+  double* dY = *k.part + (size_t)nseg * p * mp0;
+  CHK(ensure_pinned(c, 2 * (size_t)mp0 * d + 2 * (size_t)mp0 * p + d + k.pin_route + 64));
+  double* pin_in[2] = {c->hpin, c->hpin + (size_t)mp0 * d};
+  double* pin_out[2] = {pin_in[1] + (size_t)mp0 * d, pin_in[1] + (size_t)mp0 * d + (size_t)mp0 * p};
+  double* pin_dl = pin_out[1] + (size_t)mp0 * p;   // 1 / delta
+  CHK(upload_invdelta(c, pin_dl));
+  CHK(route(pin_dl + d));
+  double coff, cdiag;
+  kernel_consts(c->f_kernel, c->f_nu, true, &coff, &cdiag);
+  const int fam = kernel_fam(c->f_kernel);
+  CHK(pipe_events(c));
+  auto dev_chunk = [&](long long s0, int slot) -> int {
+    const long long mc = std::min(CH, m - s0), mp = pad_to(mc, PM_PTS);
+    std::memcpy(pin_in[slot], Xs + s0 * d, (size_t)mc * d * sizeof(double));
+    // (k_scale_points reads the mc points only and writes zeros for the padded ones)
+    HIPCHK(c, hipMemcpyAsync(c->dXs, pin_in[slot], (size_t)mc * d * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_scale_points, dim3((unsigned)((mp * d + 255) / 256)), dim3(256), 0, c->stream, c->dXs,
+                       c->dinvdelta, d, (int)mc, (int)mp, c->dXsw);
+    HIPCHK(c, hipGetLastError());
+    CHK(kernels(mp, nseg, *k.part, dY, coff, fam));
+    HIPCHK(c, hipMemcpyAsync(pin_out[slot], dY, (size_t)mc * p * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipEventRecord(c->ev_pipe[slot], c->stream));
+    return GPE_OK;
+  };
+  return run_chunks(c, m, CH, dev_chunk, [&](long long s0, int slot) {
+    const long long mc = std::min(CH, m - s0);
+    const double* y = pin_out[slot];
+    for (long long s = 0; s < mc; ++s) {
+      const double* hs = Hs + (s0 + s) * q;
+      for (int a = 0; a < p; ++a) {
+        double mu = y[s * p + a];
+        for (int i = 0; i < q; ++i) mu += hs[i] * k.coef[i * p + a];
+        mean_out[(s0 + s) * p + a] = mu;
+      }
+    }
+  });
+}
+
+// The posterior mean alone (gpe_posterior_mean): gamma from Posterior::setup(), k_post_mean
+// with one workgroup per column of points and segment of rows.
+int posterior_mean_impl(gpe_ctx* c, int64_t m, const double* Xs, const double* Hs, const double* beta,
+                        double* mean_out) {
+  CHK(check_ready(c));
+  if (!c->factor_valid) return fail(c, GPE_ERR_STATE, "no resident factor (call gpe_factor)");
+  if (m <= 0 || !Xs || !Hs || !beta || !mean_out)
+    return fail(c, GPE_ERR_ARG, "bad posterior_mean args (m >= 1; Xs, Hs, beta and mean_out not NULL)");
+  if (c->prof)   // phase 0: k_post_mean's device time over the chunks, phase 1: the chunks
+    for (int i = 0; i < 8; ++i) c->phase_ms[i] = 0.0;
+  CHK(ensure_linv(c));
+  PostReq r{m, Xs, Hs, beta, 1.0, 64, mean_out, PostVar::DIAG, nullptr};
+  Posterior S(c, r);
+  CHK(S.setup());   // gamma in dWa's first column
+  const int d = c->d;
+  const MeanKind kind{1, &c->dPm, &c->pm_cap, beta, 0};
+  return posterior_means<1>(
+      c, kind, m, Xs, Hs, mean_out, [](double*) { return GPE_OK; },
+      [&](long long mp, int nseg, double* part, double* dY, double coff, int fam) -> int {
+        PostMeanArgs a;
+        a.xw = c->dXw; a.xsw = c->dXsw; a.gam = c->dWa; a.part = part; a.coff = coff;
+        a.n = (int)c->n; a.np = (int)c->n_pad; a.mp = (int)mp; a.d = d;
+        const dim3 grid((unsigned)(mp / (d > 32 ? PM_LANES : PM_PTS)), (unsigned)nseg);
+        CHK(chunk_prof_begin(c));
+        with_fam(fam, [&](auto F) { launch_post_mean_fam<decltype(F)::value>(d, grid, c->stream, a); });
+        HIPCHK(c, hipGetLastError());
+        CHK(chunk_prof_end(c));
+        hipLaunchKernelGGL(k_post_mean_fin, dim3((unsigned)((mp + 255) / 256)), dim3(256), 0, c->stream, part, nseg,
+                           (int)mp, dY);
+        HIPCHK(c, hipGetLastError());
+        return GPE_OK;
+      });
+}
+
 // The posterior means of the p outputs of gpe_set_outputs (gpe_posterior_mean_multi):
-// Gamma = A^-1 (F - H B) by posterior_mean_impl's route to gamma (L^-1, then L^-T, of the
-// columns) into dWm, then posterior_mean_impl's pipeline with k_post_mean_multi and p values
-// per point.  Device workspace: the chunk's points twice and its (nseg + 1) p sums per point.
+// Gamma = A^-1 (F - H B) by Posterior::setup()'s route to gamma (L^-1, then L^-T, of the
+// columns) into dWm, k_post_mean_multi with one workgroup per PMM_PTS points and segment of rows.
 int posterior_mean_multi_impl(gpe_ctx* c, int64_t m, const double* Xs, const double* Hs, const double* B,
                               double* mean_out) {
   CHK(check_ready(c));
@@ -3110,98 +3094,73 @@ int posterior_mean_multi_impl(gpe_ctx* c, int64_t m, const double* Xs, const dou
     for (int i = 0; i < 8; ++i) c->phase_ms[i] = 0.0;
   CHK(ensure_linv(c));
   const int d = c->d, q = c->q, p = c->mo_p, P = p + q;
-  const long long np = c->n_pad, CH = c->mean_chunk;
-  auto pad_pts = [](long long v) { return ((v + PM_PTS - 1) / PM_PTS) * PM_PTS; };
+  const long long np = c->n_pad;
   static_assert(PM_PTS % PMM_PTS == 0, "a padded chunk is whole workgroups of k_post_mean_multi");
-  const long long mp0 = pad_pts(std::min<long long>(CH, m));
-  const int nrt = (int)(np / PM_RI), nseg = (nrt + PM_SEG - 1) / PM_SEG;
-  CHK(grow_buf(c, &c->dXs, &c->xs_cap, (size_t)mp0 * d));
-  CHK(grow_buf(c, &c->dXsw, &c->xsw_cap, (size_t)mp0 * d));
-  CHK(grow_buf(c, &c->dPmm, &c->pmm_cap, (size_t)(nseg + 1) * p * mp0));
-  double* dY = c->dPmm + (size_t)nseg * p * mp0;
-  CHK(ensure_pinned(c, 2 * (size_t)mp0 * d + 2 * (size_t)mp0 * p + d + (size_t)P * p + 64));
-  double* pin_in[2] = {c->hpin, c->hpin + (size_t)mp0 * d};
-  double* pin_out[2] = {pin_in[1] + (size_t)mp0 * d, pin_in[1] + (size_t)mp0 * d + (size_t)mp0 * p};
-  double* pin_dl = pin_out[1] + (size_t)mp0 * p;   // 1 / delta
-  double* pin_t = pin_dl + d;                      // [I; -B] (P x p, column-major)
-  for (int k = 0; k < d; ++k) pin_dl[k] = 1.0 / c->f_delta[k];
-  HIPCHK(c, hipMemcpyAsync(c->dinvdelta, pin_dl, d * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  std::memset(pin_t, 0, (size_t)P * p * sizeof(double));
-  for (int a = 0; a < p; ++a) {
-    pin_t[a + (size_t)a * P] = 1.0;
-    for (int i = 0; i < q; ++i) pin_t[(p + i) + (size_t)a * P] = -B[i * p + a];
-  }
-  HIPCHK(c, hipMemcpyAsync(c->dT2, pin_t, (size_t)P * p * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  CHK(apply_small(c, c->dFm, np, P, c->dT2, p, c->dR2m, np, (int)np, nullptr));
-  CHK(skinny(c, false, c->tr.B, np, c->NB, c->NB, true, c->dR2m, np, p, c->dZm, np));   // L^-1 (F - H B)
-  CHK(skinny(c, true, c->tr.B, np, c->NB, c->NB, true, c->dZm, np, p, c->dWm, np));    // Gamma
-  double coff, cdiag;
-  kernel_consts(c->f_kernel, c->f_nu, true, &coff, &cdiag);
-  const int fam = kernel_fam(c->f_kernel);
-  if (!c->ev_pipe[0])
-    for (hipEvent_t& e : c->ev_pipe) HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  auto dev_chunk = [&](long long s0, int slot) -> int {
-    const long long mc = std::min(CH, m - s0), mp = pad_pts(mc);
-    std::memcpy(pin_in[slot], Xs + s0 * d, (size_t)mc * d * sizeof(double));
-    // (k_scale_points reads the mc points only and writes zeros for the padded ones)
-    HIPCHK(c, hipMemcpyAsync(c->dXs, pin_in[slot], (size_t)mc * d * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(k_scale_points, dim3((unsigned)((mp * d + 255) / 256)), dim3(256), 0, c->stream, c->dXs,
-                       c->dinvdelta, d, (int)mc, (int)mp, c->dXsw);
-    HIPCHK(c, hipGetLastError());
-    // one workgroup per PMM_PTS points and segment of rows
-    PostMeanMultiArgs a;
-    a.xw = c->dXw; a.xsw = c->dXsw; a.gam = c->dWm; a.part = c->dPmm; a.coff = coff;
-    a.n = (int)c->n; a.np = (int)np; a.mp = (int)mp; a.d = d; a.p = p;
-    const dim3 grid((unsigned)(mp / PMM_PTS), (unsigned)nseg);
-    if (c->prof) HIPCHK(c, hipEventRecord(c->ev[4], c->stream));
-    with_fam(fam, [&](auto F) { launch_post_mean_multi_fam<decltype(F)::value>(d, grid, c->stream, a); });
-    HIPCHK(c, hipGetLastError());
-    if (c->prof) {   // (profiling only: one synchronisation per chunk)
+  const MeanKind kind{p, &c->dPmm, &c->pmm_cap, B, (size_t)P * p};
+  return posterior_means<0>(
+      c, kind, m, Xs, Hs, mean_out,
+      [&](double* pin_t) -> int {   // [I; -B] (P x p, column-major)
+        std::memset(pin_t, 0, (size_t)P * p * sizeof(double));
+        for (int a = 0; a < p; ++a) {
+          pin_t[a + (size_t)a * P] = 1.0;
+          for (int i = 0; i < q; ++i) pin_t[(p + i) + (size_t)a * P] = -B[i * p + a];
+        }
+        HIPCHK(c, hipMemcpyAsync(c->dT2, pin_t, (size_t)P * p * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        CHK(apply_small(c, c->dFm, np, P, c->dT2, p, c->dR2m, np, (int)np, nullptr));
+        CHK(skinny(c, false, c->tr.B, np, c->NB, c->NB, true, c->dR2m, np, p, c->dZm, np));   // L^-1 (F - H B)
+        return skinny(c, true, c->tr.B, np, c->NB, c->NB, true, c->dZm, np, p, c->dWm, np);   // Gamma
+      },
+      [&](long long mp, int nseg, double* part, double* dY, double coff, int fam) -> int {
+        PostMeanMultiArgs a;
+        a.xw = c->dXw; a.xsw = c->dXsw; a.gam = c->dWm; a.part = part; a.coff = coff;
+        a.n = (int)c->n; a.np = (int)np; a.mp = (int)mp; a.d = d; a.p = p;
+        const dim3 grid((unsigned)(mp / PMM_PTS), (unsigned)nseg);
+        CHK(chunk_prof_begin(c));
+        with_fam(fam, [&](auto F) { launch_post_mean_multi_fam<decltype(F)::value>(d, grid, c->stream, a); });
+        HIPCHK(c, hipGetLastError());
+        CHK(chunk_prof_end(c));
+        hipLaunchKernelGGL(k_post_mean_multi_fin, dim3((unsigned)((mp * p + 255) / 256)), dim3(256), 0, c->stream,
+                           part, nseg, p, (int)mp, dY);
+        HIPCHK(c, hipGetLastError());
+        return GPE_OK;
+      });
+}
+
+// The greedy selections' profiling (gpe_posterior_pivchol, gpe_posterior_imse): what ran since
+// ev[0], the covariance and the set-up, into phase_ms[0]; ev[1] then opens the first panel.
+int panels_prof_begin(gpe_ctx* c) {
+  if (!c->prof) return GPE_OK;
+  float ms = 0.f;
+  HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
+  HIPCHK(c, hipEventSynchronize(c->ev[1]));
+  (void)hipEventElapsedTime(&ms, c->ev[0], c->ev[1]);
+  c->phase_ms[0] = ms;
+  return GPE_OK;
+}
+
+// Their k steps in panels of PC_PANEL columns: step(t0, j) for the panel's columns, the
+// trailing update Lt if steps remain, then tail(t0, cols).  Profiling adds the steps' device
+// time to phase_ms[1] and the update's and tail's to phase_ms[2] (one synchronisation per panel).
+template <class Step, class Tail>
+int run_panels(gpe_ctx* c, long long k, const GemmLaunch& Lt, Step&& step, Tail&& tail) {
+  for (long long t0 = 0; t0 < k; t0 += PC_PANEL) {
+    const int cols = (int)std::min<long long>(PC_PANEL, k - t0);
+    for (int j = 0; j < cols; ++j) CHK(step(t0, j));
+    if (c->prof) HIPCHK(c, hipEventRecord(c->ev[2], c->stream));
+    if (t0 + cols < k) CHK(launch_gemm_range(c, Lt));
+    CHK(tail(t0, cols));
+    if (c->prof) {
       float ms = 0.f;
-      HIPCHK(c, hipEventRecord(c->ev[5], c->stream));
-      HIPCHK(c, hipEventSynchronize(c->ev[5]));
-      (void)hipEventElapsedTime(&ms, c->ev[4], c->ev[5]);
-      c->phase_ms[0] += ms;
-      c->phase_ms[1] += 1.0;
+      HIPCHK(c, hipEventRecord(c->ev[3], c->stream));
+      HIPCHK(c, hipEventSynchronize(c->ev[3]));
+      (void)hipEventElapsedTime(&ms, c->ev[1], c->ev[2]);
+      c->phase_ms[1] += ms;
+      (void)hipEventElapsedTime(&ms, c->ev[2], c->ev[3]);
+      c->phase_ms[2] += ms;
+      HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
     }
-    hipLaunchKernelGGL(k_post_mean_multi_fin, dim3((unsigned)((mp * p + 255) / 256)), dim3(256), 0, c->stream,
-                       c->dPmm, nseg, p, (int)mp, dY);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(pin_out[slot], dY, (size_t)mc * p * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipEventRecord(c->ev_pipe[slot], c->stream));
-    return GPE_OK;
-  };
-  auto host_chunk = [&](long long s0, const double* y) {
-    const long long mc = std::min(CH, m - s0);
-    for (long long s = 0; s < mc; ++s) {
-      const double* hs = Hs + (s0 + s) * q;
-      for (int a = 0; a < p; ++a) {
-        double mu = y[s * p + a];
-        for (int i = 0; i < q; ++i) mu += hs[i] * B[i * p + a];
-        mean_out[(s0 + s) * p + a] = mu;
-      }
-    }
-  };
-  auto pipeline = [&]() -> int {
-    int slot = 0;
-    long long prev = -1;
-    for (long long s0 = 0; s0 < m; s0 += CH, slot ^= 1) {
-      CHK(dev_chunk(s0, slot));
-      if (prev >= 0) {
-        HIPCHK(c, hipEventSynchronize(c->ev_pipe[slot ^ 1]));
-        host_chunk(prev, pin_out[slot ^ 1]);
-      }
-      prev = s0;
-    }
-    HIPCHK(c, hipEventSynchronize(c->ev_pipe[slot ^ 1]));
-    host_chunk(prev, pin_out[slot ^ 1]);
-    return GPE_OK;
-  };
-  const int rc = pipeline();
-  // (a failed step may leave copies into the pinned slots queued: drained before the staging
-  // buffer can be reused or regrown)
-  if (rc != GPE_OK) (void)hipStreamSynchronize(c->stream);
-  return rc;
+  }
+  return GPE_OK;
 }
 
 }  // namespace
@@ -3365,36 +3324,22 @@ int gpe_posterior_pivchol(gpe_ctx* c, int64_t m, const double* Xs, const double*
   }
   hipLaunchKernelGGL(k_pc_init, dim3(G), dim3(PC_ROWS), 0, c->stream, a, (int)k);
   HIPCHK(c, hipGetLastError());
-  float ms = 0.f;
-  if (c->prof) {
-    HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
-    HIPCHK(c, hipEventSynchronize(c->ev[1]));
-    (void)hipEventElapsedTime(&ms, c->ev[0], c->ev[1]);
-    c->phase_ms[0] = ms;
-  }
-  for (long long t0 = 0; t0 < k; t0 += PC_PANEL) {
-    const int cols = (int)std::min<long long>(PC_PANEL, k - t0);
-    for (int j = 0; j < cols; ++j) {
-      hipLaunchKernelGGL(k_pc_step, dim3(G), dim3(256), 0, c->stream, a, W, (int)(t0 + j), j);
-      HIPCHK(c, hipGetLastError());
-    }
-    if (c->prof) HIPCHK(c, hipEventRecord(c->ev[2], c->stream));
-    if (t0 + cols < k) CHK(launch_gemm_range(c, Lt));
-    if (L_out) {   // the panel into the row-major device copy of L (zeros beyond the rank)
-      hipLaunchKernelGGL(k_pc_panel_out, dim3(G, (cols + 63) / 64), dim3(256), 0, c->stream, W, mp, (int)m, cols,
-                         a.st, Ld, (long long)k, t0);
-      HIPCHK(c, hipGetLastError());
-    }
-    if (c->prof) {   // (profiling only: one synchronisation per panel)
-      HIPCHK(c, hipEventRecord(c->ev[3], c->stream));
-      HIPCHK(c, hipEventSynchronize(c->ev[3]));
-      (void)hipEventElapsedTime(&ms, c->ev[1], c->ev[2]);
-      c->phase_ms[1] += ms;
-      (void)hipEventElapsedTime(&ms, c->ev[2], c->ev[3]);
-      c->phase_ms[2] += ms;
-      HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
-    }
-  }
+  CHK(panels_prof_begin(c));
+  CHK(run_panels(
+      c, k, Lt,
+      [&](long long t0, int j) -> int {
+        hipLaunchKernelGGL(k_pc_step, dim3(G), dim3(256), 0, c->stream, a, W, (int)(t0 + j), j);
+        HIPCHK(c, hipGetLastError());
+        return GPE_OK;
+      },
+      [&](long long t0, int cols) -> int {
+        if (!L_out) return GPE_OK;
+        // the panel into the row-major device copy of L (zeros beyond the rank)
+        hipLaunchKernelGGL(k_pc_panel_out, dim3(G, (cols + 63) / 64), dim3(256), 0, c->stream, W, mp, (int)m, cols,
+                           a.st, Ld, (long long)k, t0);
+        HIPCHK(c, hipGetLastError());
+        return GPE_OK;
+      }));
   CHK(ensure_pinned(c, head + 8));
   HIPCHK(c, hipMemcpyAsync(c->hpin, c->dPc, head * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -3489,39 +3434,23 @@ int gpe_posterior_imse(gpe_ctx* c, int64_t m, int64_t mc, const double* Xs, cons
   HIPCHK(c, hipGetLastError());
   hipLaunchKernelGGL(k_im_copy, dim3((unsigned)((ldc + 255) / 256), (unsigned)(Gs * IM_NC)), dim3(256), 0, c->stream, a);
   HIPCHK(c, hipGetLastError());
-  float ms = 0.f;
-  if (c->prof) {
-    HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
-    HIPCHK(c, hipEventSynchronize(c->ev[1]));
-    (void)hipEventElapsedTime(&ms, c->ev[0], c->ev[1]);
-    c->phase_ms[0] = ms;
-  }
+  CHK(panels_prof_begin(c));
   // step 0's scores: the sweep without a downdate
   hipLaunchKernelGGL(k_im_sweep<false>, dim3(Gs), dim3(256), 0, c->stream, a, (const double*)W, -1);
   HIPCHK(c, hipGetLastError());
-  for (long long t0 = 0; t0 < k; t0 += PC_PANEL) {
-    const int cols = (int)std::min<long long>(PC_PANEL, k - t0);
-    for (int j = 0; j < cols; ++j) {
-      hipLaunchKernelGGL(k_im_col, dim3(Gc), dim3(256), 0, c->stream, a, W, (int)(t0 + j), j);
-      HIPCHK(c, hipGetLastError());
-      if (t0 + j + 1 < k) {   // (the last pick's downdate would feed a step that is not taken)
-        hipLaunchKernelGGL(k_im_sweep<true>, dim3(Gs), dim3(256), 0, c->stream, a,
-                           (const double*)(W + (size_t)j * mp), (int)(t0 + j));
+  CHK(run_panels(
+      c, k, Lt,
+      [&](long long t0, int j) -> int {
+        hipLaunchKernelGGL(k_im_col, dim3(Gc), dim3(256), 0, c->stream, a, W, (int)(t0 + j), j);
         HIPCHK(c, hipGetLastError());
-      }
-    }
-    if (c->prof) HIPCHK(c, hipEventRecord(c->ev[2], c->stream));
-    if (t0 + cols < k) CHK(launch_gemm_range(c, Lt));
-    if (c->prof) {   // (profiling only: one synchronisation per panel)
-      HIPCHK(c, hipEventRecord(c->ev[3], c->stream));
-      HIPCHK(c, hipEventSynchronize(c->ev[3]));
-      (void)hipEventElapsedTime(&ms, c->ev[1], c->ev[2]);
-      c->phase_ms[1] += ms;
-      (void)hipEventElapsedTime(&ms, c->ev[2], c->ev[3]);
-      c->phase_ms[2] += ms;
-      HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
-    }
-  }
+        if (t0 + j + 1 < k) {   // (the last pick's downdate would feed a step that is not taken)
+          hipLaunchKernelGGL(k_im_sweep<true>, dim3(Gs), dim3(256), 0, c->stream, a,
+                             (const double*)(W + (size_t)j * mp), (int)(t0 + j));
+          HIPCHK(c, hipGetLastError());
+        }
+        return GPE_OK;
+      },
+      [](long long, int) { return GPE_OK; }));
   HIPCHK(c, hipMemcpyAsync(c->hpin, c->dIm, head * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   if (c->prof) c->phase_ms[6] = c->phase_ms[0] + c->phase_ms[1] + c->phase_ms[2];

@@ -344,6 +344,21 @@ def test_posterior_means_against_the_reference(ctx, case):
     assert np.max(np.abs(mean - cols)) <= tol
 
 
+@pytest.mark.parametrize("case", [c for c in MEAN_CASES if c[2] == 1], ids=lambda c: "-".join(str(v) for v in c))
+def test_one_output_returns_the_single_mean_bits(ctx, case):
+    """p = 1: gpe_posterior_mean_multi and gpe_posterior_mean share the route to gamma, the order
+    of the n-term sum and the host's hs . beta, so they return the same bits (the register
+    widths with d = 3, the wide instance with d = 40)."""
+    n, m, p, d, family, kind = case
+    X, F, H = problem(n, d, p)
+    Xs, Hs, _, _ = mean_reference(*case)
+    _resident(ctx, n, p, d, family, kind)
+    B = ctx.beta_multi()
+    multi = ctx.posterior_mean_multi(Xs, Hs, B)
+    single = ctx.posterior_mean(Xs, Hs, B[:, 0])
+    assert multi.shape == (m, 1) and np.array_equal(multi[:, 0], single)
+
+
 @pytest.mark.parametrize("m,p,d", [(1000, 17, 3), (257, 3, 40)])
 def test_chunks_return_the_same_bits(ctx, monkeypatch, m, p, d):
     """GPEMU_MEAN_CHUNK=256 in a context of its own: 4 chunks (m = 1000), and 2 with the last of

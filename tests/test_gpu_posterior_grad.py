@@ -104,6 +104,28 @@ def test_more_than_one_chunk(ctx, family):
     assert np.all(np.isfinite(dmean)) and np.all(np.isfinite(dvar))
 
 
+def test_profiling_counts_the_chunks(ctx):
+    """The same two chunks with profiling on: phase_times() slot [1] is the chunk count and
+    slot [0] k_post_grad's device time, and the outputs are the bits of the unprofiled call."""
+    n, d, m, kind, family = 129, 2, 8192 + 130, orc.ALT, "gaussian"
+    Xs = np.random.RandomState(11).uniform(size=(m, d))
+    Hs = orc.linear_basis(Xs)
+    dHs, hdim = pgr.linear_basis_deriv(Xs)
+    tm._factor(ctx, family, n, d, kind)
+    beta = ctx.beta()
+    plain = ctx.posterior_grad(Xs, Hs, dHs, hdim, beta, mr.SIGMA)
+    ctx.set_profiling(True)
+    try:
+        timed = ctx.posterior_grad(Xs, Hs, dHs, hdim, beta, mr.SIGMA)
+        times = ctx.phase_times()
+    finally:
+        ctx.set_profiling(False)
+    print("chunks", times["cholesky"], "k_post_grad ms", times["kbuild"])
+    assert times["cholesky"] == 2 and times["kbuild"] > 0.0      # slots [1] and [0]
+    for a, b in zip(timed, plain):
+        assert np.array_equal(a, b)
+
+
 @pytest.mark.parametrize("family", mr.FAMILIES)
 def test_with_r(ctx, family):
     """The alt kernel with r on the diagonal of the resident A (r_scale = 1)."""
