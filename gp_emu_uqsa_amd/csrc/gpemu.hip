@@ -39,6 +39,7 @@
 #include "gpemu_postmean.hpp"
 #include "gpemu_postmean_multi.hpp"
 #include "gpemu_postgroup.hpp"
+#include "gpemu_hm.hpp"
 #include "gpemu_host_alloc.hpp"
 
 using namespace gpe;
@@ -4203,3 +4204,292 @@ int gpe_bench_gemm(gpe_ctx* c, int32_t trans_a, int32_t trans_b, int32_t mt, int
 }  // extern "C"
 
 
+// ---------------------------------------------------------------- history matching
+// A set of emulators resident on one GPU (gpe_hm_*; kernels in gpemu_hm.hpp, layouts and sizes
+// in gpemu_hm_plan.hpp).  gpe_hm_add snapshots what the posterior of a context's resident factor
+// needs into buffers the set owns; gpe_hm_implausibility runs the candidates through every
+// emulator chunk by chunk on the set's own stream.
+
+namespace {
+
+// One emulator: its device buffer (dev, one allocation) and the arrays inside it
+struct HmEmul {
+  int n = 0, d = 0, q = 0, fam = 0, pt = 0, maxact = 0;
+  double s2 = 0.0, coff = 0.0, cdiag = 0.0;
+  double* dev = nullptr;
+  double *xw = nullptr, *invdelta = nullptr, *W = nullptr, *beta = nullptr, *kinv = nullptr, *hval = nullptr;
+  int *active = nullptr, *hdim = nullptr;
+};
+
+}  // namespace
+
+struct gpe_hm {
+  int device = 0;
+  hipStream_t stream = nullptr;
+  std::string err;
+  std::vector<HmEmul> em;
+  long long chunk = HM_CHUNK_DEFAULT;
+  hipEvent_t ev_ctx = nullptr, ev_set = nullptr;   // gpe_hm_add: the context's stream <-> the set's
+  hipEvent_t ev_pipe[2] = {nullptr, nullptr};      // the chunk pipeline's result slots
+  double* dwork = nullptr;   // one chunk: the points, I^2, the parts, the selection
+  size_t work_cap = 0;
+  double* hpin = nullptr;    // two slots of points, two of results
+  size_t hpin_cap = 0;
+};
+
+namespace {
+
+thread_local std::string g_hm_create_error;
+
+int hm_fail(gpe_hm* h, int code, const std::string& msg) {
+  h->err = msg;
+  return code;
+}
+
+#define HM_HIPCHK(h, expr)                                                  \
+  do {                                                                      \
+    hipError_t e_ = (expr);                                                 \
+    if (e_ != hipSuccess) {                                                 \
+      (h)->err = std::string(#expr) + ": " + hipGetErrorString(e_);         \
+      return GPE_ERR_HIP;                                                   \
+    }                                                                       \
+  } while (0)
+
+template <int FAM, int PT>
+bool hm_lds_attr_one() {
+  return hipFuncSetAttribute((const void*)k_hm_post<FAM, PT>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                             HM_LDS_BYTES) == hipSuccess;
+}
+template <int FAM>
+bool hm_lds_attr() {
+  return hm_lds_attr_one<FAM, HM_PT_WIDE>() && hm_lds_attr_one<FAM, HM_PT_NARROW>();
+}
+
+// k_hm_post<FAM, PT> for one emulator and one chunk
+void hm_launch_post(const HmEmul& e, dim3 g, size_t lds, hipStream_t st, const HmPostArgs& a) {
+  with_fam(e.fam, [&](auto F) {
+    constexpr int FAM = decltype(F)::value;
+    if (e.pt == HM_PT_WIDE) hipLaunchKernelGGL((k_hm_post<FAM, HM_PT_WIDE>), g, dim3(HM_LANES), lds, st, a);
+    else hipLaunchKernelGGL((k_hm_post<FAM, HM_PT_NARROW>), g, dim3(HM_LANES), lds, st, a);
+  });
+}
+
+// The snapshot of gpe_hm_add, behind the checks: [gamma, G], Kq^-1 and the kernel's constants
+// by Posterior::setup() on the context (scratch buffers only: what gpe_posterior itself
+// overwrites on every call), then the copies on the set's stream, ordered behind the context's
+// stream by ev_ctx; the context's stream waits for them (ev_set) before it goes on.
+int hm_snapshot(gpe_hm* h, gpe_ctx* c, const int32_t* active, const int32_t* hdim, const double* hval,
+                const double* beta, double sigma, HmEmul& e) {
+  const int n = (int)c->n, d = c->d, q = c->q;
+  const long long np = c->n_pad;
+  PostReq r{0, nullptr, nullptr, beta, sigma, 64, nullptr, PostVar::DIAG, nullptr};
+  Posterior S(c, r);
+  CHK(S.setup());
+  e.n = n; e.d = d; e.q = q; e.fam = S.fam; e.pt = hm_pt(n);
+  e.s2 = S.s2; e.coff = S.coff; e.cdiag = S.cdiag;
+  e.maxact = 0;
+  for (int k = 0; k < d; ++k) e.maxact = std::max(e.maxact, (int)active[k]);
+  const size_t nW = (size_t)hm_packed_size(n, q), nint = ((size_t)d + q + 1) / 2 + 1;
+  const size_t sz[] = {(size_t)n * d, (size_t)d, nW, (size_t)q, (size_t)q * q, (size_t)q, nint};
+  size_t tot = 0;
+  for (size_t s : sz) tot += s;
+  HM_HIPCHK(h, hipMalloc((void**)&e.dev, tot * sizeof(double)));
+  double* p = e.dev;
+  e.xw = p, p += sz[0];
+  e.invdelta = p, p += sz[1];
+  e.W = p, p += sz[2];
+  e.beta = p, p += sz[3];
+  e.kinv = p, p += sz[4];
+  e.hval = p, p += sz[5];
+  e.active = reinterpret_cast<int*>(p);
+  e.hdim = e.active + d;
+  // the small arrays lie together behind W: one blocking copy
+  std::vector<double> hs(sz[3] + sz[4] + sz[5] + sz[6], 0.0);
+  std::memcpy(hs.data(), beta, (size_t)q * sizeof(double));
+  std::memcpy(hs.data() + q, S.Kinv.data(), (size_t)q * q * sizeof(double));
+  std::memcpy(hs.data() + q + (size_t)q * q, hval, (size_t)q * sizeof(double));
+  int* hi = reinterpret_cast<int*>(hs.data() + 2 * (size_t)q + (size_t)q * q);
+  for (int k = 0; k < d; ++k) hi[k] = active[k];
+  for (int j = 0; j < q; ++j) hi[d + j] = hdim[j];
+  HM_HIPCHK(h, hipMemcpy(e.beta, hs.data(), hs.size() * sizeof(double), hipMemcpyHostToDevice));
+  std::vector<double> idl((size_t)d);
+  for (int k = 0; k < d; ++k) idl[k] = 1.0 / c->f_delta[k];   // (as upload_invdelta)
+  HM_HIPCHK(h, hipMemcpy(e.invdelta, idl.data(), (size_t)d * sizeof(double), hipMemcpyHostToDevice));
+  HM_HIPCHK(h, hipEventRecord(h->ev_ctx, c->stream));
+  HM_HIPCHK(h, hipStreamWaitEvent(h->stream, h->ev_ctx, 0));
+  HM_HIPCHK(h, hipMemcpyAsync(e.xw, c->dXw, (size_t)n * d * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+  hipLaunchKernelGGL(k_hm_pack, dim3((unsigned)hm_nblocks(n, q)), dim3(256), 0, h->stream, c->tr.B, c->dWa, np, n, q,
+                     e.W);
+  HM_HIPCHK(h, hipGetLastError());
+  HM_HIPCHK(h, hipEventRecord(h->ev_set, h->stream));
+  HM_HIPCHK(h, hipStreamWaitEvent(c->stream, h->ev_set, 0));
+  HM_HIPCHK(h, hipStreamSynchronize(h->stream));
+  return GPE_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+gpe_hm* gpe_hm_create(int32_t device) {
+  int ndev = 0;
+  hipError_t e = hipGetDeviceCount(&ndev);
+  if (e != hipSuccess || ndev <= 0) {
+    g_hm_create_error = std::string("no HIP device available: ") + hipGetErrorString(e);
+    return nullptr;
+  }
+  if (device < 0 || device >= ndev) {
+    g_hm_create_error = "device index out of range";
+    return nullptr;
+  }
+  gpe_hm* h = new gpe_hm();
+  h->device = device;
+  if (const char* ec = std::getenv("GPEMU_HM_CHUNK")) h->chunk = hm_chunk(std::atoll(ec));
+  bool ok = hipSetDevice(device) == hipSuccess &&
+            hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) == hipSuccess &&
+            hipEventCreateWithFlags(&h->ev_ctx, hipEventDisableTiming) == hipSuccess &&
+            hipEventCreateWithFlags(&h->ev_set, hipEventDisableTiming) == hipSuccess;
+  for (hipEvent_t& ev : h->ev_pipe) ok = ok && hipEventCreateWithFlags(&ev, hipEventDisableTiming) == hipSuccess;
+  ok = ok && hm_lds_attr<FAM_GAUSS>() && hm_lds_attr<FAM_MATERN32>() && hm_lds_attr<FAM_MATERN52>();
+  if (!ok) {
+    g_hm_create_error = "failed to initialise the set's stream, events or kernels";
+    gpe_hm_destroy(h);
+    return nullptr;
+  }
+  return h;
+}
+
+void gpe_hm_destroy(gpe_hm* h) {
+  if (!h) return;
+  (void)hipSetDevice(h->device);
+  if (h->stream) (void)hipStreamSynchronize(h->stream);
+  for (HmEmul& e : h->em)
+    if (e.dev) (void)hipFree(e.dev);
+  if (h->dwork) (void)hipFree(h->dwork);
+  if (h->hpin) (void)hipHostFree(h->hpin);
+  for (hipEvent_t ev : {h->ev_ctx, h->ev_set, h->ev_pipe[0], h->ev_pipe[1]})
+    if (ev) (void)hipEventDestroy(ev);
+  if (h->stream) (void)hipStreamDestroy(h->stream);
+  delete h;
+}
+
+const char* gpe_hm_last_error(const gpe_hm* h) {
+  if (!h) return g_hm_create_error.c_str();
+  return h->err.c_str();
+}
+
+int gpe_hm_count(const gpe_hm* h) { return h ? (int)h->em.size() : GPE_ERR_ARG; }
+
+int gpe_hm_add(gpe_hm* h, gpe_ctx* c, int32_t d, const int32_t* active, int32_t q, const int32_t* hdim,
+               const double* hval, const double* beta, double sigma) {
+  if (!h) return GPE_ERR_ARG;
+  h->err.clear();
+  if (!c || !active || !hdim || !hval || !beta) return hm_fail(h, GPE_ERR_ARG, "bad hm_add args (a NULL pointer)");
+  if (c->device != h->device) return hm_fail(h, GPE_ERR_ARG, "the context is on another device than the set");
+  if (c->n <= 0 || !c->factor_valid) return hm_fail(h, GPE_ERR_STATE, "no resident factor (call gpe_factor)");
+  if (d != c->d || q != c->q) return hm_fail(h, GPE_ERR_ARG, "d and q must be those of the context's data");
+  if (c->n > HM_MAX_N || d > HM_MAX_D || q > HM_MAX_Q || (int)h->em.size() >= HM_MAX_EMUL)
+    return hm_fail(h, GPE_ERR_UNSUPPORTED, "an emulator of a set has n <= 512, d <= 32, q <= 16; a set at most 32");
+  for (int k = 0; k < d; ++k)
+    if (active[k] < 0) return hm_fail(h, GPE_ERR_ARG, "active[" + std::to_string(k) + "] is negative");
+  for (int j = 0; j < q; ++j)
+    if (hdim[j] < -1 || hdim[j] >= d) return hm_fail(h, GPE_ERR_ARG, "hdim[" + std::to_string(j) + "] is outside [-1, d)");
+  HM_HIPCHK(h, hipSetDevice(h->device));
+  HmEmul e;
+  int rc = ensure_linv(c);
+  if (rc == GPE_OK) rc = hm_snapshot(h, c, active, hdim, hval, beta, sigma, e);
+  if (rc != GPE_OK) {
+    // (the copies may be queued: they end before the buffer goes)
+    (void)hipStreamSynchronize(h->stream);
+    if (e.dev) (void)hipFree(e.dev);
+    if (h->err.empty()) h->err = c->err;
+    return rc;
+  }
+  h->em.push_back(e);
+  return (int)h->em.size() - 1;
+}
+
+int gpe_hm_implausibility(gpe_hm* h, int64_t m, int32_t D, const double* Xs, const double* z, const double* var_extra,
+                          int32_t maxno, double* imax_out, double* mean_out, double* var_out) {
+  if (!h) return GPE_ERR_ARG;
+  const int p = (int)h->em.size();
+  if (p == 0) return hm_fail(h, GPE_ERR_STATE, "the set is empty (call gpe_hm_add)");
+  if (m <= 0 || !Xs || !z || !var_extra || !imax_out)
+    return hm_fail(h, GPE_ERR_ARG, "bad hm_implausibility args (m >= 1; Xs, z, var_extra and imax_out not NULL)");
+  if (maxno < 1 || maxno > p) return hm_fail(h, GPE_ERR_ARG, "maxno must be in [1, emulators of the set]");
+  for (const HmEmul& e : h->em)
+    if (D <= e.maxact) return hm_fail(h, GPE_ERR_ARG, "D is smaller than an emulator's largest active index + 1");
+  if ((mean_out == nullptr) != (var_out == nullptr))
+    return hm_fail(h, GPE_ERR_ARG, "mean_out and var_out go together (both or neither)");
+  HM_HIPCHK(h, hipSetDevice(h->device));
+  const bool parts = mean_out != nullptr;
+  const long long CH = h->chunk, cl = std::min<long long>(CH, m);
+  const HmWork w = hm_work(cl, D, p, maxno, parts);
+  if ((size_t)w.dev() > h->work_cap) {
+    if (h->dwork) (void)hipFree(h->dwork);
+    h->dwork = nullptr, h->work_cap = 0;
+    HM_HIPCHK(h, hipMalloc((void**)&h->dwork, (size_t)w.dev() * sizeof(double)));
+    h->work_cap = (size_t)w.dev();
+  }
+  const size_t pin = 2 * (size_t)(w.pin_in() + w.pin_out());
+  if (pin > h->hpin_cap) {
+    if (h->hpin) (void)hipHostFree(h->hpin);
+    h->hpin = nullptr, h->hpin_cap = 0;
+    HM_HIPCHK(h, hipHostMalloc((void**)&h->hpin, pin * sizeof(double), hipHostMallocDefault));
+    h->hpin_cap = pin;
+  }
+  double* dX = h->dwork;
+  double* dI2 = dX + w.pts;
+  double* dparts = dI2 + w.i2;       // mean (p x cl), then var (p x cl)
+  double* dsel = dparts + w.parts;
+  double* pin_in[2] = {h->hpin, h->hpin + w.pin_in()};
+  double* pin_out[2] = {pin_in[1] + w.pin_in(), pin_in[1] + w.pin_in() + w.pin_out()};
+  auto dev = [&](long long s0, int slot) -> int {
+    const long long mc = std::min(CH, m - s0);
+    std::memcpy(pin_in[slot], Xs + s0 * D, (size_t)mc * D * sizeof(double));
+    HM_HIPCHK(h, hipMemcpyAsync(dX, pin_in[slot], (size_t)mc * D * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    for (int o = 0; o < p; ++o) {
+      const HmEmul& e = h->em[o];
+      HmPostArgs a;
+      a.xw = e.xw; a.invdelta = e.invdelta; a.active = e.active; a.W = e.W; a.hdim = e.hdim; a.hval = e.hval;
+      a.beta = e.beta; a.kinv = e.kinv; a.Xs = dX; a.i2 = dI2 + o * cl;
+      a.mean = parts ? dparts + o * cl : nullptr;
+      a.var = parts ? dparts + (p + o) * cl : nullptr;
+      a.z = z[o]; a.ve = var_extra[o]; a.s2 = e.s2; a.coff = e.coff; a.cdiag = e.cdiag;
+      a.n = e.n; a.d = e.d; a.q = e.q; a.D = D; a.mc = (int)mc;
+      hm_launch_post(e, dim3((unsigned)hm_tiles(mc, e.pt)), (size_t)hm_lds_doubles(e.n, e.pt) * sizeof(double),
+                     h->stream, a);
+      HM_HIPCHK(h, hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_hm_select, dim3((unsigned)((mc + 255) / 256)), dim3(256), 0, h->stream, dI2, cl, p, (int)maxno,
+                       (int)mc, dsel);
+    HM_HIPCHK(h, hipGetLastError());
+    // (the parts keep the leading dimension cl on both sides: one copy whatever mc is)
+    HM_HIPCHK(h, hipMemcpyAsync(pin_out[slot], dsel, (size_t)mc * maxno * sizeof(double), hipMemcpyDeviceToHost,
+                                h->stream));
+    if (parts)
+      HM_HIPCHK(h, hipMemcpyAsync(pin_out[slot] + w.sel, dparts, (size_t)w.parts * sizeof(double), hipMemcpyDeviceToHost,
+                                  h->stream));
+    HM_HIPCHK(h, hipEventRecord(h->ev_pipe[slot], h->stream));
+    return GPE_OK;
+  };
+  auto host = [&](long long s0, int slot) {
+    const long long mc = std::min(CH, m - s0);
+    std::memcpy(imax_out + s0 * maxno, pin_out[slot], (size_t)mc * maxno * sizeof(double));
+    if (!parts) return;
+    const double* src = pin_out[slot] + w.sel;
+    for (int o = 0; o < p; ++o) {
+      std::memcpy(mean_out + (long long)o * m + s0, src + o * cl, (size_t)mc * sizeof(double));
+      std::memcpy(var_out + (long long)o * m + s0, src + (p + o) * cl, (size_t)mc * sizeof(double));
+    }
+  };
+  return chunk_pipeline(
+      m, CH, dev,
+      [&](int slot) -> int {
+        HM_HIPCHK(h, hipEventSynchronize(h->ev_pipe[slot]));
+        return GPE_OK;
+      },
+      host, [&] { (void)hipStreamSynchronize(h->stream); });
+}
+
+}  // extern "C"

@@ -27,6 +27,9 @@ import numpy as _np
 from . import design_inputs as _gd
 from . import model as _model
 
+__all__ = ["imp_plot", "imp_plot_recon", "nonimp_data", "new_wave_design", "EmulatorSet", "implausibility",
+           "nonimp_sample"]
+
 
 # ----------------------------------------------------------------- helpers (_hmutilfunctions.py)
 def make_sets(ai):
@@ -297,3 +300,140 @@ def new_wave_design(emuls, zs, cm, var_extra, datafiles, maxno=1, olhcmult=100, 
     _np.savetxt(nfileStr + datafiles[0], nimp_inputs)
     print("Generated", len(nimp_inputs), "new data points")
     return len(nimp_inputs)
+
+
+# ----------------------------------------------------------------- resident emulator set
+class EmulatorSet:
+    """The emulators of a wave resident on the GPU together (native.EmulatorSet, gpe_hm).
+
+    Each emulator's training set is uploaded and factored once, as ``Sensitivity._gpu`` does,
+    and snapshotted into the set; ``implausibility`` then runs any number of candidate points
+    through all of them, one fused kernel per emulator and chunk.  ``fused`` is False when an
+    emulator falls outside that path -- the library refuses it (n > 512, more than 32 inputs,
+    16 basis columns or 32 emulators), a basis expression is neither the constant nor ``x``,
+    or ``model.Posterior`` would add a host-side term to its variance -- and the whole set then
+    computes through the ``_posterior_diag`` loop, with that loop's results."""
+
+    def __init__(self, emuls):
+        self.emuls = list(emuls)
+        _, minmax, _ = emulsetup(self.emuls)
+        self.minmax = minmax
+        self.act_ref = ref_act(minmax)
+        self.D = len(minmax)
+        self._cols = [[self.act_ref[str(l)] for l in E.beliefs.active_index] for E in self.emuls]
+        self._set = None
+        self.fused = self._make_fused()
+
+    @staticmethod
+    def _basis_forms(E):
+        """(hdim, hval) of E's basis if every column is the constant or the identity on one
+        input (the reference's default mean functions), else None."""
+        exprs = [str(e).strip() for e in E.beliefs.basis_str]
+        if len(exprs) != len(E.basis.h) or any(e != "x" for e in exprs[1:]) \
+                or any(str(e).strip() != "x" for e in E.basis.exprs[1:]):
+            return None
+        try:
+            const = float(E.basis.h[0](1.0))
+        except Exception:
+            return None
+        hdim = [-1] + [int(E.basis.basis_inf[j - 1]) for j in range(1, len(exprs))]
+        return hdim, [const] + [0.0] * (len(exprs) - 1)
+
+    @staticmethod
+    def _host_var_term(E):
+        """True if model.Posterior adds a term to the variance of new points on the host."""
+        probe = _model.Data(_np.asarray(E.training.inputs)[:1], None, E.basis, E.par, E.beliefs, E.K)
+        return probe.r_scale() != 0.0
+
+    def _make_fused(self):
+        from . import native as _native
+        forms = [self._basis_forms(E) for E in self.emuls]
+        if any(f is None for f in forms) or any(self._host_var_term(E) for E in self.emuls):
+            return False
+        nset = None
+        try:
+            for E, cols, (hdim, hval) in zip(self.emuls, self._cols, forms):
+                ctx = _model.upload_training(E.training)
+                ctx.ensure_factor(E.K.kind, E.K.d, float(E.K.n), 1.0, E.training.r_scale())
+                if nset is None:
+                    nset = _native.EmulatorSet(ctx.device)
+                nset.add(ctx, cols, hdim, hval, E.par.beta, float(E.par.sigma))
+        except RuntimeError as err:
+            if nset is not None:
+                nset.close()
+            if getattr(err, "status", None) == -5:   # GPE_ERR_UNSUPPORTED: beyond the set's limits
+                return False
+            raise
+        self._set = nset
+        return True
+
+    def implausibility(self, zs, var_extra, x, maxno=1):
+        """m x maxno: per point of x (m x D, scaled) the maxno largest implausibilities over
+        the emulators, ascending."""
+        x = _np.ascontiguousarray(x, dtype=float)
+        if x.ndim == 1:
+            x = x.reshape(-1, 1)
+        maxno = int(maxno)
+        if self.fused:
+            return self._set.implausibility(x, zs, var_extra, maxno=maxno)
+        I2 = _np.zeros((x.shape[0], len(self.emuls)))
+        for o, (E, cols) in enumerate(zip(self.emuls, self._cols)):
+            mean, var = _posterior_diag(E, x[:, cols])
+            I2[:, o] = (mean - zs[o]) ** 2 / (var + var_extra[o])
+        return _imaxes(I2, maxno)
+
+    def close(self):
+        if self._set is not None:
+            self._set.close()
+            self._set = None
+            self.fused = False
+
+
+def _as_set(emuls_or_set):
+    if isinstance(emuls_or_set, EmulatorSet):
+        return emuls_or_set, False
+    return EmulatorSet(emuls_or_set), True
+
+
+def implausibility(emuls_or_set, zs, var_extra, x, maxno=1):
+    """The maxno largest implausibilities over the emulators at every point of x (m x D in the
+    scaled inputs, one column per active input in ascending order): m x maxno, ascending, so
+    column -maxno is what ``nonimp_data`` compares with the cut-off.  Takes a list of emulators
+    or an ``EmulatorSet`` (kept resident between calls)."""
+    S, mine = _as_set(emuls_or_set)
+    try:
+        return S.implausibility(zs, var_extra, x, maxno)
+    finally:
+        if mine:
+            S.close()
+
+
+def nonimp_sample(emuls_or_set, zs, cm, var_extra, count, maxno=1, seed=0, batch=2 ** 20, max_tried=None):
+    """Rejection sampling of the non-implausible region: uniform candidates in the scaled box,
+    ``np.random.default_rng(seed).random((batch, D))`` batch after batch, kept where the
+    maxno-th largest implausibility is below cm.  Returns (points, tried): the first ``count``
+    accepted candidates in stream order (fewer if ``max_tried`` candidates did not yield them)
+    and the number of candidates drawn up to and including the last one returned, or all that
+    were tried if fewer than ``count`` were found.  The result does not depend on ``batch``."""
+    S, mine = _as_set(emuls_or_set)
+    try:
+        rng = _np.random.default_rng(seed)
+        lo = _np.array([S.minmax[k][0] for k in sorted(S.minmax, key=int)], dtype=float)
+        hi = _np.array([S.minmax[k][1] for k in sorted(S.minmax, key=int)], dtype=float)
+        maxno, count, batch = int(maxno), int(count), int(batch)
+        kept, have, tried = [], 0, 0
+        while have < count and (max_tried is None or tried < max_tried):
+            k = batch if max_tried is None else min(batch, int(max_tried) - tried)
+            x = lo + rng.random((k, S.D)) * (hi - lo)
+            ok = _np.flatnonzero(S.implausibility(zs, var_extra, x, maxno)[:, -maxno] < cm)
+            if have + ok.size >= count:
+                ok = ok[:count - have]
+                kept.append(x[ok])
+                return _np.concatenate(kept), tried + int(ok[-1]) + 1
+            kept.append(x[ok])
+            have += ok.size
+            tried += k
+        return (_np.concatenate(kept) if kept else _np.zeros((0, S.D))), tried
+    finally:
+        if mine:
+            S.close()

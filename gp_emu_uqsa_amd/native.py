@@ -101,6 +101,12 @@ SIGNATURES = {
     "gpe_posterior_imse": (_ct.c_int, [_VP, _ct.c_int64, _ct.c_int64, _D, _D, _D, _ct.c_double, _D, _ct.c_double,
                                        _D, _ct.c_int64, _ct.c_double, _D, _ct.POINTER(_ct.c_int64), _D, _D, _D,
                                        _ct.POINTER(_ct.c_int64)]),
+    "gpe_hm_destroy": (None, [_VP]),
+    "gpe_hm_last_error": (_ct.c_char_p, [_VP]),
+    "gpe_hm_add": (_ct.c_int, [_VP, _VP, _ct.c_int32, _ct.POINTER(_ct.c_int32), _ct.c_int32,
+                               _ct.POINTER(_ct.c_int32), _D, _D, _ct.c_double]),
+    "gpe_hm_count": (_ct.c_int, [_VP]),
+    "gpe_hm_implausibility": (_ct.c_int, [_VP, _ct.c_int64, _ct.c_int32, _D, _D, _D, _ct.c_int32, _D, _D, _D]),
     "gpe_solve": (_ct.c_int, [_VP, _ct.c_int32, _D, _D]),
     "gpe_sense_pairs": (_ct.c_int, [_VP, _ct.c_int32, _D, _D, _ct.c_int32, _D, _D, _D]),
     "gpe_gauss_transform": (_ct.c_int, [_VP, _ct.c_int64, _ct.c_int32, _ct.POINTER(_ct.c_int32), _D, _D, _D,
@@ -137,6 +143,12 @@ SIGNATURES = {
     "gpe_dist_rank_bytes": (_ct.c_int, [_VP, _ct.c_int32, _ct.POINTER(_ct.c_int64)]),
 }
 
+# constructors that return a handle type of their own (SIGNATURES lists the entries whose
+# return type is int, void, const char* or one of the two context handles)
+HANDLE_SIGNATURES = {
+    "gpe_hm_create": (_VP, [_ct.c_int32]),
+}
+
 UNIQUE_ID_BYTES = 128
 
 
@@ -163,7 +175,7 @@ def load_library(path: str | None = None):
             raise NativeUnavailable(
                 f"{p} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'`")
         lib = _ct.CDLL(p)
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in list(SIGNATURES.items()) + list(HANDLE_SIGNATURES.items()):
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args
@@ -795,6 +807,88 @@ _ctx_lock = _threading.Lock()
 
 _tls = _threading.local()
 _extra_ctxs: list = []
+
+
+class EmulatorSet:
+    """Emulators resident on one GPU together for history matching (gpe_hm).  ``add`` snapshots
+    a context's resident factor; ``implausibility`` runs candidates through every emulator of
+    the set, one fused kernel per emulator and chunk, without forming K* or L^-1 K*."""
+
+    MAX_N, MAX_D, MAX_Q, MAX_EMUL = 512, 32, 16, 32
+
+    def __init__(self, device: int = 0):
+        self.lib = load_library()
+        if self.lib.gpe_device_count() <= 0:
+            raise NativeUnavailable("no HIP device visible to libgpemu.so")
+        h = self.lib.gpe_hm_create(int(device))
+        if not h:
+            raise NativeUnavailable("gpe_hm_create failed: " + self.lib.gpe_hm_last_error(None).decode())
+        self._h = h
+        self.device = device
+        self._maxact = -1
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self.lib.gpe_hm_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __len__(self):
+        return int(self.lib.gpe_hm_count(self._h))
+
+    def _check(self, rc, what):
+        if rc == GPE_OK:
+            return
+        msg = self.lib.gpe_hm_last_error(self._h).decode()
+        if rc == GPE_NOT_PD:
+            raise NotPositiveDefinite(f"{what}: {msg}")
+        err = RuntimeError(f"{what} failed ({rc}): {msg}")
+        err.status = rc
+        raise err
+
+    def add(self, ctx, active, hdim, hval, beta, sigma):
+        """Snapshot ctx's resident factor as the next emulator; returns its number.  active:
+        the columns of the candidate rows it reads, in the order of its inputs; basis column j
+        is the constant hval[j] where hdim[j] == -1, else the emulator's input hdim[j]."""
+        i32 = _ct.POINTER(_ct.c_int32)
+        active = _np.ascontiguousarray(active, dtype=_np.int32).ravel()
+        hdim = _np.ascontiguousarray(hdim, dtype=_np.int32).ravel()
+        hval = _f64(hval).ravel()
+        beta = _f64(beta).ravel()
+        if not (hdim.size == hval.size == beta.size):
+            raise ValueError("hdim, hval and beta have one entry per basis column")
+        rc = self.lib.gpe_hm_add(self._h, ctx._h, active.size, active.ctypes.data_as(i32), hdim.size,
+                                 hdim.ctypes.data_as(i32), _ptr(hval), _ptr(beta), float(sigma))
+        # (the return value 1 is emulator number 1 unless the set left an error text: GPE_NOT_PD)
+        if rc < 0 or (rc == GPE_NOT_PD and self.lib.gpe_hm_last_error(self._h)):
+            self._check(rc, "gpe_hm_add")
+        return rc
+
+    def implausibility(self, Xs, z, var_extra, maxno=1, parts=False):
+        """imax (m x maxno): per candidate the maxno largest implausibilities over the
+        emulators, ascending, NaN last.  parts=True: (imax, mean, var) with mean and var
+        p x m.  Xs is m x D in the scaled coordinates posterior() takes."""
+        Xs = _f64(Xs)
+        if Xs.ndim == 1:
+            Xs = Xs.reshape(-1, 1)
+        m, D = Xs.shape
+        p = len(self)
+        z = _f64(z).ravel()
+        ve = _f64(var_extra).ravel()
+        if z.size != p or ve.size != p:
+            raise ValueError("z and var_extra have one entry per emulator of the set")
+        maxno = int(maxno)
+        imax = _np.zeros((m, max(maxno, 1)))
+        mean = _np.zeros((p, m)) if parts else None
+        var = _np.zeros((p, m)) if parts else None
+        self._check(self.lib.gpe_hm_implausibility(self._h, m, D, _ptr(Xs), _ptr(z), _ptr(ve), maxno, _ptr(imax),
+                                                   _ptr(mean), _ptr(var)), "gpe_hm_implausibility")
+        return (imax, mean, var) if parts else imax
 
 
 def default_context() -> Context:

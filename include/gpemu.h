@@ -37,7 +37,7 @@ extern "C" {
                                 9: gpe_dist_local_rows takes the basis width q;
                                 10: gpe_ozaki_stats (gpe_loo, gpe_posterior_pivchol,
                                 gpe_posterior_imse, gpe_posterior_grad, gpe_posterior_mean, gpe_posterior_groups,
-                                gpe_set_outputs, gpe_objective_multi, gpe_beta_multi, gpe_posterior_mean_multi and the test
+                                gpe_set_outputs, gpe_objective_multi, gpe_beta_multi, gpe_posterior_mean_multi, the gpe_hm_* set and the test
                                 hooks gpe_test_oz_product, gpe_test_oz_planes and gpe_test_gemm_group were
                                 added within 10: additions, nothing existing changed) */
 
@@ -296,6 +296,65 @@ int gpe_posterior_mean_multi(gpe_ctx* ctx, int64_t m, const double* Xs, const do
  * multiple of G or a NULL pointer; GPE_NOT_PD as gpe_posterior. */
 int gpe_posterior_groups(gpe_ctx* ctx, int64_t m, int32_t G, const double* Xs, const double* Hs,
                          const double* beta, double sigma, double* mean_out, double* cov_out);
+
+/* ---- History matching over a resident set of emulators (additions within ABI 10; the
+ * reference forms one Posterior per emulator and grid cell, history_match.py:91-121).  A wave
+ * has p emulators of a few hundred design points each and rules out input space at 10^6 and
+ * more candidates.  A set keeps p emulators on one GPU together; per emulator one fused kernel
+ * (gpemu_hm.hpp) goes from the candidates to I^2 without K* or L^-1 K* in memory (L^-1 of
+ * n <= 512 rows is at most 1 MB and stays in L2), and one selection kernel follows.  One set
+ * per host thread; its calls are synchronous on a stream of its own. */
+typedef struct gpe_hm gpe_hm;
+
+/* A set on one GPU.  NULL on failure; the reason is then in gpe_hm_last_error(NULL).
+ * GPEMU_HM_CHUNK (read here; default 65536, rounded down to a multiple of 64, at least 64) is
+ * the number of candidates per chunk. */
+gpe_hm* gpe_hm_create(int32_t device);
+void gpe_hm_destroy(gpe_hm* set);
+const char* gpe_hm_last_error(const gpe_hm* set);
+
+/* Snapshot ctx's resident factor (gpe_factor) as the next emulator of the set; returns its
+ * number (>= 0), or a negative status.  The triangular inverse runs on demand, as for
+ * gpe_solve.  Copied into buffers the set owns: the scaled training rows, 1 / delta, L^-1 and
+ * [gamma, G] = A^-1 [f - H beta, H] in MFMA operand order (lower 16 x 16 blocks only), Kq^-1
+ * with Kq Kq^T = H^T A^-1 H, beta, sigma^2 and the kernel's family, coff and cdiag: exactly what
+ * gpe_posterior(beta, sigma) would use.  The copies are ordered behind the context's stream,
+ * and the context's stream behind them, by events; the context keeps its factor and everything
+ * other entries keep of it, and is free for the next emulator on return.
+ * d and q are those of ctx's data.  active[d]: the columns of the D-wide candidate rows this
+ * emulator reads, in the order of its inputs.  Basis column j of a candidate is the constant
+ * hval[j] when hdim[j] == -1, else the value of the emulator's input hdim[j] (0 <= hdim[j] < d):
+ * the reference's default forms.
+ * Limits: n <= 512, d <= 32, q <= 16, 32 emulators per set; beyond, GPE_ERR_UNSUPPORTED and the
+ * set is unchanged.  GPE_ERR_STATE without a resident factor; GPE_ERR_ARG for a NULL pointer, a
+ * d or q other than the context's, a negative active index, hdim[j] outside [-1, d) or a
+ * context on another device; GPE_NOT_PD if H^T A^-1 H is not positive definite. */
+int gpe_hm_add(gpe_hm* set, gpe_ctx* ctx, int32_t d, const int32_t* active, int32_t q,
+               const int32_t* hdim, const double* hval, const double* beta, double sigma);
+int gpe_hm_count(const gpe_hm* set);
+
+/* Implausibilities of m candidates.  Xs m x D row-major in the scaled coordinates
+ * gpe_posterior takes, uploaded once per chunk for all emulators; z and var_extra p values
+ * (p = gpe_hm_count).  For emulator o and candidate s, with K* and h of the candidate,
+ *   mean = h . beta + sum_i gamma_i K*_i,
+ *   var  = sigma^2 (cdiag - |L^-1 K*|^2 + |(h - G^T K*) Kq^-T|^2)
+ * (gpe_posterior(full_var = 0, precision = 64)'s formulas) and
+ *   I^2 = (mean - z_o)^2 / (var + var_extra_o),
+ * IEEE arithmetic with no clamping.  imax_out (m x maxno): per candidate the maxno largest
+ * sqrt(I^2) over the emulators in ascending order, a NaN counted above every number (numpy's
+ * sort order); 1 <= maxno <= p.  mean_out and var_out (p x m each, row o emulator o; both or
+ * neither): the parts.
+ * Any m: chunks of GPEMU_HM_CHUNK candidates through two pinned slots, the next chunk's work
+ * queued before the host copies the previous one's results.  The sums over the training rows
+ * run in an order that depends on n alone and there are no floating-point atomics: the result
+ * of a candidate does not depend on m, on the chunk length or on the other candidates, and
+ * repeated calls return the same bits.
+ * GPE_ERR_STATE for an empty set; GPE_ERR_ARG for m <= 0, a NULL among Xs, z, var_extra and
+ * imax_out, one of mean_out / var_out without the other, D smaller than an emulator's largest
+ * active index + 1, or maxno outside [1, p]. */
+int gpe_hm_implausibility(gpe_hm* set, int64_t m, int32_t D, const double* Xs, const double* z,
+                          const double* var_extra, int32_t maxno, double* imax_out,
+                          double* mean_out, double* var_out);
 
 /* ---- Sensitivity / UQ building blocks, resident factor --------
  * Replace the O(n^2) parts of sensitivity/_sensitivityclasses.py (case2): the
