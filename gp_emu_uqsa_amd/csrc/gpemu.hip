@@ -73,6 +73,12 @@ enum AdhocSlot {
 // rows of the Schur complement from which the objective's Cholesky is split and S runs on the
 // int8 cores (GPEMU_OZAKI_CHOL_MIN)
 constexpr int OZ_CHOL_MIN = 8192;
+// n_pad from which the objective's int8 products carry a 15-moduli certificate
+// (GPEMU_OZAKI_CERT_MIN_NP).  Below 6144 the int8 path runs only with its own thresholds lowered;
+// measured there with all of them at their floors, one evaluation gains 1%
+// at n_pad 4096 and 5120 and nothing at 2944 (3.58 against 3.60 ms), where the k_oz_cert launches
+// and the sums cost what the sixteenth modulus saves
+constexpr int OZ_CERT_MIN_NP = 4096;
 // rows of the trapezoid (those from the inner split column q on) from which the split sweep's
 // first phase is split once more (GPEMU_OZAKI_CHOL_NEST_MIN)
 constexpr int OZ_CHOL_NEST_MIN = 12288;
@@ -176,6 +182,17 @@ struct gpe_ctx {
   int8_t* dozp = nullptr;         // the N int8 planes of X (lower 256-column panels)
   int8_t* dozr = nullptr;         // the N residue bytes of every lower 256-tile entry
   int* dozx = nullptr;            // per-column exponents
+  // the 15-moduli certificate of the objective's products (gpemu_ozaki.hpp; GPEMU_OZAKI_CERT=0:
+  // 16 moduli everywhere; only where the context runs 16): the operands' row sums beside dozx
+  // (same indices, same lifetime), one flag per product of an evaluation, the 15-moduli constants.
+  // From n_pad oz_cert_min_np (GPEMU_OZAKI_CERT_MIN_NP, default OZ_CERT_MIN_NP; tests lower it to 512)
+  int oz_cert_on = 1, oz_cert_min_np = OZ_CERT_MIN_NP;
+  unsigned long long* dozs = nullptr;
+  int* dozf = nullptr;
+  unsigned long long* dozm = nullptr;   // per flag: A = max s_a, B = max s_b (gpe_oz_cert_sums)
+  int oz_flag_cap = 0, oz_cert_used = 0;   // flags: allocated, taken by the last evaluation's products
+  OzConst oz_c15{};
+  std::vector<std::pair<int, double>> oz_cert_ops;   // profiling: a product's flag and its int8 ops
   unsigned* dozl = nullptr;       // k_oz_gemm's tile lists (the LAUUM's, then every TRTRI pair's)
   double* dozt = nullptr;         // the TRTRI pairs' T = L21 X11
   hipEvent_t ev_oz = nullptr;     // the first int8 TRTRI pair's L21 planes are ready (stream2)
@@ -1002,6 +1019,8 @@ int factor_and_invert(gpe_ctx* c, int kernel, const double* delta, double nu, do
                       double rscale, bool invert = true, bool objective = false, const Cols* cols = nullptr) {
   c->linv_valid = false;
   c->oz_l21_valid = false;
+  c->oz_cert_used = 0;   // (every int8 product with a certificate follows from here: its flags from the first)
+  c->oz_cert_ops.clear();
   // a call that failed inside the sweep may have left Cholesky launches on the
   // high-priority stream (the join is recorded only after the last one): drain them
   // before this call's memsets and K-build touch the same buffers
@@ -1203,6 +1222,21 @@ int oz_prepare(gpe_ctx* c, Fact& F) {
   CHK(dalloc(c, &c->dozp, planes));
   CHK(dalloc(c, &c->dozr, resid));
   CHK(dalloc(c, &c->dozx, nex));
+  // a flag per product an evaluation can launch: S, the trapezoid, two per TRTRI pair (the top
+  // pair's own when its level stays fp64), the LAUUM
+  c->oz_flag_cap = 0;
+  c->oz_cert_used = 0;
+  if (c->oz_cert_on && N == OZ_MAXMOD && c->n_pad >= c->oz_cert_min_np) {
+    const size_t nflag = 2 * c->oz_tri.size() + 8;
+    CHK(dalloc(c, &c->dozs, nex));
+    CHK(dalloc(c, &c->dozf, nflag));
+    CHK(dalloc(c, &c->dozm, 2 * nflag));
+    HIPCHK(c, hipMemset(c->dozm, 0, 2 * nflag * sizeof(unsigned long long)));
+    HIPCHK(c, hipMemset(c->dozs, 0, nex * sizeof(unsigned long long)));
+    HIPCHK(c, hipMemset(c->dozf, 0, nflag * sizeof(int)));
+    c->oz_flag_cap = (int)nflag;
+    c->oz_c15 = oz_consts_cert(np2);
+  }
   CHK(dalloc(c, &c->dozt, scratch));
   CHK(dalloc(c, &c->dozl, all.size()));
   HIPCHK(c, hipMemcpy(c->dozl, all.data(), all.size() * sizeof(unsigned), hipMemcpyHostToDevice));
@@ -1211,6 +1245,16 @@ int oz_prepare(gpe_ctx* c, Fact& F) {
   c->oz_npad = c->n_pad;
   return GPE_OK;
 }
+
+// the certificate of the evaluation's next product (row sums sa[0, na), sb[0, nb) in dozs), or
+// none: switched off, fewer than 16 moduli, or no flag left
+OzCert oz_cert(gpe_ctx* c, const unsigned long long* sa, int na, const unsigned long long* sb, int nb) {
+  if (!c->oz_flag_cap || c->oz_cert_used >= c->oz_flag_cap) return OzCert{};
+  const int slot = c->oz_cert_used++;
+  return OzCert{sa, na, sb, nb, c->dozf + slot, &c->oz_c15, c->dozm + 2 * slot};
+}
+// the row sums beside dozx (null: no certificates)
+unsigned long long* oz_sums(gpe_ctx* c) { return c->oz_flag_cap ? c->dozs : nullptr; }
 
 // one product (oz_product_launch) on stream st (null: the context's); while profiling, between
 // two events of the pool, and counted in gpe_ozaki_stats
@@ -1233,6 +1277,8 @@ int oz_gemm_crt(gpe_ctx* c, const OzConst& k, const OzProduct& p, double ops, do
     c->oz_launches += 1.0;
     c->oz_ops += ops;
     c->oz_flops64 += flops64;
+    // (the moduli that ran are known once the flag is read back: objective_phase_times)
+    if (p.cert.flag && k.nmod == OZ_MAXMOD) c->oz_cert_ops.emplace_back((int)(p.cert.flag - c->dozf), ops);
   }
   return GPE_OK;
 }
@@ -1257,26 +1303,28 @@ int chol_schur(gpe_ctx* c, Fact& F, hipStream_t st, bool with_aug, int at) {
     if (with_aug) CHK(launch_gemm_range(c, pl.launches[pl.aug_q], st));
     const long long ld = F.n_pad;
     c->oz_l21_valid = false;
-    oz_operand(st, c->oz_c, n.src(F.A + (long long)n.q * TILE, ld), n.Pb, n.K, c->dozx, c->dozp);
+    oz_operand(st, c->oz_c, n.src(F.A + (long long)n.q * TILE, ld), n.Pb, n.K, c->dozx, c->dozp, oz_sums(c));
     HIPCHK(c, hipGetLastError());
     const OzShape s = n.shape();
     const OzOpnd l{c->dozp, (long long)n.Pb * n.K, n.K, 0};
     return oz_gemm_crt(c, c->oz_c,
                        OzProduct{s, l, l, c->dozl + c->oz_nest_loff, c->oz_nest_llen, c->dozr, s.res_bytes(),
-                                 OzOut{c->dozx, c->dozx, F.A + (long long)n.q * TILE * (ld + 1), ld, n.Rb, n.cols, 1, -1.0, 1}},
+                                 OzOut{c->dozx, c->dozx, F.A + (long long)n.q * TILE * (ld + 1), ld, n.Rb, n.cols, 1, -1.0, 1},
+                                 oz_cert(c, c->dozs, n.Pb, c->dozs, n.Pb)},
                        c->oz_nest_ops, (double)n.cols * (2.0 * n.Rb - n.cols) * n.K, st);
   }
   const OzTriPair& q = c->oz_chol_q;
   if (!c->oz_chol_ready || q.h != pl.split_h) return fail(c, GPE_ERR_STATE, "internal error: split Cholesky without an int8 plan");
   if (with_aug) CHK(launch_gemm_range(c, pl.launches[pl.aug_mid], st));
   const long long ld = F.n_pad;
-  oz_operand(st, c->oz_c, q.l21(F.A + (long long)q.h * TILE, ld), q.Pb, q.Pa, c->dozx, c->dozp);
+  oz_operand(st, c->oz_c, q.l21(F.A + (long long)q.h * TILE, ld), q.Pb, q.Pa, c->dozx, c->dozp, oz_sums(c));
   HIPCHK(c, hipGetLastError());
   const OzShape s = q.shape_schur();
   const OzOpnd l21{c->dozp, (long long)q.Pb * q.Pa, q.Pa, 0};
   CHK(oz_gemm_crt(c, c->oz_c,
                   OzProduct{s, l21, l21, c->dozl + c->oz_chol_loff, c->oz_chol_llen, c->dozr, s.res_bytes(),
-                            OzOut{c->dozx, c->dozx, F.A + (long long)q.h * TILE * (ld + 1), ld, q.Rb, q.Rb, 1, -1.0, 1}},
+                            OzOut{c->dozx, c->dozx, F.A + (long long)q.h * TILE * (ld + 1), ld, q.Rb, q.Rb, 1, -1.0, 1},
+                            oz_cert(c, c->dozs, q.Pb, c->dozs, q.Pb)},
                   c->oz_chol_ops, (double)q.Rb * q.Rb * q.Ra, st));
   c->oz_l21_valid = true;
   return GPE_OK;
@@ -1287,12 +1335,13 @@ int lauum_ozaki(gpe_ctx* c, Fact& F) {
   CHK(oz_prepare(c, F));
   const int np = (int)F.n_pad, np2 = c->oz_np2;
   c->oz_l21_valid = false;
-  oz_operand_packed(c->stream, c->oz_c, F.B, (long long)F.n_pad, np, np2, c->dozx, c->dozp);
+  oz_operand_packed(c->stream, c->oz_c, F.B, (long long)F.n_pad, np, np2, c->dozx, c->dozp, oz_sums(c));
   const OzShape s = oz_lauum_shape(np2);
   const OzOpnd x{c->dozp, oz_plane_bytes(np2), 0, np2};
   return oz_gemm_crt(c, c->oz_c,
                      OzProduct{s, x, x, c->dozl, c->oz_list_len, c->dozr, s.res_bytes(),
-                               OzOut{c->dozx, c->dozx, F.A, (long long)F.n_pad, np, np, 1, 1.0}},
+                               OzOut{c->dozx, c->dozx, F.A, (long long)F.n_pad, np, np, 1, 1.0},
+                               oz_cert(c, c->dozs, np2, c->dozs, np2)},
                      c->oz_lauum_ops, (double)np * np * np / 3.0);
 }
 
@@ -1307,7 +1356,7 @@ const OzTriPair* oz_pair(const gpe_ctx* c, int t0, int h, int t1) {
 int oz_l21(gpe_ctx* c, Fact& F, const OzTriPair& q, hipStream_t st) {
   c->oz_l21_valid = false;
   oz_operand(st, c->oz_c, q.l21(F.A + (long long)q.h * TILE + (long long)q.t0 * TILE * F.n_pad, F.n_pad), q.Pb, q.Pa,
-             c->dozx, c->dozp);
+             c->dozx, c->dozp, oz_sums(c));
   HIPCHK(c, hipGetLastError());
   return GPE_OK;
 }
@@ -1342,7 +1391,10 @@ int trtri_pair_ozaki(gpe_ctx* c, Fact& F, int t0, int h, int t1, int l21, int pa
                        tile(F.B, h, t0), ld, c->dozt, c->dozp, c->dozr, c->dozx, l21 != 0,
                        [&](const OzProduct& p, double ops, double fl) {
                          if (rc == GPE_OK) rc = oz_gemm_crt(c, c->oz_c, p, ops, fl);
-                       }, part);
+                       }, part, oz_sums(c),
+                       [&](const unsigned long long* sa, int na, const unsigned long long* sb, int nb) {
+                         return oz_cert(c, sa, na, sb, nb);
+                       });
   CHK(rc);
   HIPCHK(c, hipGetLastError());
   return GPE_OK;
@@ -1451,6 +1503,8 @@ gpe_ctx* gpe_create(int32_t device) {
     if (const char* ec = std::getenv("GPEMU_OZAKI_CHOL_MIN")) c->oz_chol_min = std::max(256, std::atoi(ec));
     if (const char* ec = std::getenv("GPEMU_OZAKI_CHOL_NEST")) c->oz_nest = std::atoi(ec) != 0;
     if (const char* ec = std::getenv("GPEMU_OZAKI_CHOL_NEST_MIN")) c->oz_nest_min = std::max(256, std::atoi(ec));
+    if (const char* ec = std::getenv("GPEMU_OZAKI_CERT")) c->oz_cert_on = std::atoi(ec) != 0;
+    if (const char* ec = std::getenv("GPEMU_OZAKI_CERT_MIN_NP")) c->oz_cert_min_np = std::max(512, std::atoi(ec));
     if (const char* ea = std::getenv("GPEMU_TRTRI_AHEAD")) c->tri_ahead_on = std::atoi(ea) != 0;
     if (const char* es = std::getenv("GPEMU_POTRF_SB")) {
       c->sched.sb = std::max(1, std::min(8, std::atoi(es)));
@@ -1543,6 +1597,9 @@ void gpe_destroy(gpe_ctx* c) {
   if (c->dozp) hipFree(c->dozp);
   if (c->dozr) hipFree(c->dozr);
   if (c->dozx) hipFree(c->dozx);
+  if (c->dozs) hipFree(c->dozs);
+  if (c->dozf) hipFree(c->dozf);
+  if (c->dozm) hipFree(c->dozm);
   if (c->dozl) hipFree(c->dozl);
   if (c->dozt) hipFree(c->dozt);
   if (c->ev_oz) hipEventDestroy(c->ev_oz);
@@ -1645,6 +1702,40 @@ int gpe_ozaki_stats(gpe_ctx* c, double* ms_out, double* launches_out, double* in
   if (launches_out) *launches_out = c->oz_launches;
   if (int8_ops_out) *int8_ops_out = c->oz_ops;
   if (fp64_flops_out) *fp64_flops_out = c->oz_flops64;
+  return GPE_OK;
+}
+
+int gpe_oz_cert_stats(gpe_ctx* c, int32_t* products_out, int32_t* certified_out) {
+  if (!c) return GPE_ERR_ARG;
+  HIPCHK(c, hipSetDevice(c->device));
+  int cert = 0;
+  if (c->oz_cert_used > 0) {
+    std::vector<int> fl((size_t)c->oz_cert_used);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream2));
+    HIPCHK(c, hipMemcpy(fl.data(), c->dozf, fl.size() * sizeof(int), hipMemcpyDeviceToHost));
+    for (const int f : fl) cert += f != 0;
+  }
+  if (products_out) *products_out = c->oz_cert_used;
+  if (certified_out) *certified_out = cert;
+  return GPE_OK;
+}
+
+int gpe_oz_cert_sums(gpe_ctx* c, int32_t cap, uint64_t* a_out, uint64_t* b_out) {
+  if (!c) return GPE_ERR_ARG;
+  if (cap < 0 || (cap > 0 && (!a_out || !b_out))) return fail(c, GPE_ERR_ARG, "gpe_oz_cert_sums: NULL output");
+  HIPCHK(c, hipSetDevice(c->device));
+  const int n = std::min((int)cap, c->oz_cert_used);
+  if (n > 0) {
+    std::vector<unsigned long long> m(2 * (size_t)n);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream2));
+    HIPCHK(c, hipMemcpy(m.data(), c->dozm, m.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    for (int i = 0; i < n; ++i) {
+      a_out[i] = m[2 * (size_t)i];
+      b_out[i] = m[2 * (size_t)i + 1];
+    }
+  }
   return GPE_OK;
 }
 
@@ -1820,6 +1911,14 @@ int objective_phase_times(gpe_ctx* c) {
     g += ms;
   }
   c->oz_ms = g;
+  // the int8 operations that ran: a certified product's sixteenth modulus did not
+  if (!c->oz_cert_ops.empty()) {
+    std::vector<int> fl((size_t)c->oz_flag_cap);
+    HIPCHK(c, hipMemcpy(fl.data(), c->dozf, fl.size() * sizeof(int), hipMemcpyDeviceToHost));
+    for (const auto& po : c->oz_cert_ops)
+      if (fl[(size_t)po.first]) c->oz_ops -= po.second / OZ_MAXMOD;
+    c->oz_cert_ops.clear();
+  }
   return GPE_OK;
 }
 
@@ -1847,6 +1946,7 @@ int gpe_objective(gpe_ctx* c, int32_t variant, int32_t kernel, const double* hp,
     c->gemm_launches = c->gemm_flops = c->gemm_ms = 0.0;
     c->oev_used = 0;
     c->oz_ms = c->oz_launches = c->oz_ops = c->oz_flops64 = 0.0;
+    c->oz_cert_ops.clear();
   }
   const bool one_launch = c->tiny;
   if (one_launch && c->NB == 1 && d <= TINY_DM && q + 1 <= TINY_DM)
@@ -1966,6 +2066,7 @@ int gpe_objective_multi(gpe_ctx* c, int32_t kernel, const double* hp, int32_t n_
     c->gemm_launches = c->gemm_flops = c->gemm_ms = 0.0;
     c->oev_used = 0;
     c->oz_ms = c->oz_launches = c->oz_ops = c->oz_flops64 = 0.0;
+    c->oz_cert_ops.clear();
   }
   // the general path of gpe_objective at every n, on the p + q columns of [F H]
   const Cols cols{c->dFm, P, c->dZm};
@@ -3820,8 +3921,11 @@ struct OzTestBufs {   // (freed on every way out)
   int *exa = nullptr, *exb = nullptr;
   int8_t *pa = nullptr, *pb = nullptr, *res = nullptr;
   unsigned* list = nullptr;
+  unsigned long long *suma = nullptr, *sumb = nullptr;   // (gpe_test_oz_product_cert: the row sums and the flag)
+  int* flag = nullptr;
   ~OzTestBufs() {
-    for (void* p : {(void*)sa, (void*)sb, (void*)C, (void*)exa, (void*)exb, (void*)pa, (void*)pb, (void*)res, (void*)list})
+    for (void* p : {(void*)sa, (void*)sb, (void*)C, (void*)exa, (void*)exb, (void*)pa, (void*)pb, (void*)res, (void*)list,
+                    (void*)suma, (void*)sumb, (void*)flag})
       if (p) (void)hipFree(p);
   }
 };
@@ -3835,21 +3939,27 @@ static long long oz_test_extent(const gpe_oz_operand& o, int R, int Kv) {
 
 // a rectangular operand: source to the device, row exponents, planes (P rows of Kp bytes per
 // modulus) by oz_operand, the call every production site converts its operands with
+// (dsum: null, or where the certificate's row sums go, P of them)
 static int oz_test_operand(gpe_ctx* c, const gpe_oz_operand& o, const OzConst& k, int P, int Kp, double** dsrc, int** dex,
-                           int8_t** dpl) {
+                           int8_t** dpl, unsigned long long** dsum = nullptr) {
+  if (dsum) CHK(dalloc(c, dsum, (size_t)P));
   CHK(dalloc(c, dsrc, (size_t)o.len));
   CHK(dalloc(c, dex, (size_t)P));
   CHK(dalloc(c, dpl, (size_t)k.nmod * P * Kp));
   HIPCHK(c, hipMemcpy(*dsrc, o.src, (size_t)o.len * sizeof(double), hipMemcpyHostToDevice));
-  oz_operand(c->stream, k, OzSrc{*dsrc + o.offset, (long long)o.ld, o.R, o.Kv, o.mask, o.trans != 0}, P, Kp, *dex, *dpl);
+  oz_operand(c->stream, k, OzSrc{*dsrc + o.offset, (long long)o.ld, o.R, o.Kv, o.mask, o.trans != 0}, P, Kp, *dex, *dpl,
+             dsum ? *dsum : nullptr);
   HIPCHK(c, hipGetLastError());
   return GPE_OK;
 }
 
+// (nmod_used_out: null, or the product runs with a certificate and the moduli it used go there)
 static int oz_test_product(gpe_ctx* c, const gpe_oz_operand& a, const gpe_oz_operand* b, gpe_oz_params p, double* C,
-                           int32_t* exa_out, int32_t* exb_out, int8_t* res_out) {
+                           int32_t* exa_out, int32_t* exb_out, int8_t* res_out, int32_t* nmod_used_out = nullptr) {
   const auto bad = [&](const char* what) { return fail(c, GPE_ERR_ARG, std::string("gpe_test_oz_product: ") + what); };
   if (p.nmod < 6 || p.nmod > OZ_MAXMOD) return bad("nmod outside [6, 16]");
+  const bool cert = nmod_used_out != nullptr;
+  if (cert && p.nmod != OZ_MAXMOD) return bad("a certificate needs nmod = 16");
   if (res_out && (p.res_mod < 0 || p.res_mod >= p.nmod)) return bad("res_mod is not a modulus number");
   if (a.R < 1 || a.R > (1 << 20)) return bad("bad operand rows");
   const int Pa = (a.R + OZ_T - 1) / OZ_T * OZ_T;
@@ -3880,6 +3990,7 @@ static int oz_test_product(gpe_ctx* c, const gpe_oz_operand& a, const gpe_oz_ope
     return bad("C too small for rows x cols at ldc");
   const int K = p.K, ti0 = p.ti0, nti = Pa / OZ_T - ti0, ntj = Pb / OZ_T;
   const OzConst k = oz_consts(p.nmod, K);
+  const OzConst k15 = oz_consts_cert(K);
   const OzShape s{nti, p.tri ? (Pb < Pa ? ntj : 0) : ntj, ti0, p.tri ? 1 : 0, K, p.kbeg, p.kend, p.kdiv};
   OzTestBufs d;
   hipStream_t st = c->stream;
@@ -3888,15 +3999,16 @@ static int oz_test_product(gpe_ctx* c, const gpe_oz_operand& a, const gpe_oz_ope
     CHK(dalloc(c, &d.sa, (size_t)a.len));
     CHK(dalloc(c, &d.exa, (size_t)Pa));
     CHK(dalloc(c, &d.pa, (size_t)k.nmod * oz_plane_bytes(Pa)));
+    if (cert) CHK(dalloc(c, &d.suma, (size_t)Pa));
     HIPCHK(c, hipMemcpy(d.sa, a.src, (size_t)a.len * sizeof(double), hipMemcpyHostToDevice));
-    oz_operand_packed(st, k, d.sa + a.offset, (long long)a.ld, a.R, Pa, d.exa, d.pa);
+    oz_operand_packed(st, k, d.sa + a.offset, (long long)a.ld, a.R, Pa, d.exa, d.pa, d.suma);
     HIPCHK(c, hipGetLastError());
     oa = ob = OzOpnd{d.pa, oz_plane_bytes(Pa), 0, Pa};
   } else {
-    CHK(oz_test_operand(c, a, k, Pa, K, &d.sa, &d.exa, &d.pa));
+    CHK(oz_test_operand(c, a, k, Pa, K, &d.sa, &d.exa, &d.pa, cert ? &d.suma : nullptr));
     oa = ob = OzOpnd{d.pa, (long long)Pa * K, K, 0};
     if (b) {
-      CHK(oz_test_operand(c, *b, k, Pb, K, &d.sb, &d.exb, &d.pb));
+      CHK(oz_test_operand(c, *b, k, Pb, K, &d.sb, &d.exb, &d.pb, cert ? &d.sumb : nullptr));
       ob = OzOpnd{d.pb, (long long)Pb * K, K, 0};
     }
   }
@@ -3909,8 +4021,19 @@ static int oz_test_product(gpe_ctx* c, const gpe_oz_operand& a, const gpe_oz_ope
   HIPCHK(c, hipMemcpy(d.C, C, (size_t)p.c_len * sizeof(double), hipMemcpyHostToDevice));
   HIPCHK(c, hipMemsetAsync(d.res, 0, (size_t)k.nmod * rb, st));
   const OzOut out{d.exa, b ? d.exb : d.exa, d.C, (long long)p.ldc, p.rows, p.cols, p.lower128 ? 1 : 0, p.alpha, p.acc ? 1 : 0};
-  CHK(oz_gemm_crt(c, k, OzProduct{s, oa, ob, d.list, (int)list.size(), d.res, rb, out}, 0.0, 0.0));
+  OzCert ct{};
+  if (cert) {
+    CHK(dalloc(c, &d.flag, (size_t)1));
+    HIPCHK(c, hipMemsetAsync(d.flag, 0, sizeof(int), st));
+    ct = OzCert{d.suma, Pa, b ? d.sumb : d.suma, Pb, d.flag, &k15};
+  }
+  CHK(oz_gemm_crt(c, k, OzProduct{s, oa, ob, d.list, (int)list.size(), d.res, rb, out, ct}, 0.0, 0.0));
   HIPCHK(c, hipStreamSynchronize(st));
+  if (cert) {
+    int fl = 0;
+    HIPCHK(c, hipMemcpy(&fl, d.flag, sizeof(int), hipMemcpyDeviceToHost));
+    *nmod_used_out = fl ? OZ_CERT_NMOD : OZ_MAXMOD;
+  }
   HIPCHK(c, hipMemcpy(C, d.C, (size_t)p.c_len * sizeof(double), hipMemcpyDeviceToHost));
   if (exa_out) HIPCHK(c, hipMemcpy(exa_out, d.exa, (size_t)Pa * sizeof(int), hipMemcpyDeviceToHost));
   if (exb_out) HIPCHK(c, hipMemcpy(exb_out, b ? d.exb : d.exa, (size_t)Pb * sizeof(int), hipMemcpyDeviceToHost));
@@ -3942,6 +4065,18 @@ int gpe_test_oz_product(gpe_ctx* c, const gpe_oz_operand* a, const gpe_oz_operan
   const bool prof = c->prof;   // (not a product of the objective: kept out of gpe_ozaki_stats)
   c->prof = false;
   const int rc = oz_test_product(c, *a, b, *p, C, exa_out, exb_out, res_out);
+  c->prof = prof;
+  return rc;
+}
+
+int gpe_test_oz_product_cert(gpe_ctx* c, const gpe_oz_operand* a, const gpe_oz_operand* b, const gpe_oz_params* p, double* C,
+                             int32_t* exa_out, int32_t* exb_out, int8_t* res_out, int32_t* nmod_used_out) {
+  if (!c) return GPE_ERR_ARG;
+  if (!a || !p || !nmod_used_out) return fail(c, GPE_ERR_ARG, "gpe_test_oz_product_cert: NULL operand, parameters or nmod_used_out");
+  HIPCHK(c, hipSetDevice(c->device));
+  const bool prof = c->prof;
+  c->prof = false;
+  const int rc = oz_test_product(c, *a, b, *p, C, exa_out, exb_out, res_out, nmod_used_out);
   c->prof = prof;
   return rc;
 }

@@ -55,6 +55,7 @@ struct OzConst {
   double rhi[OZ_MAXMOD];   // y / m rounded to a multiple of 2^-41 (y = (M / m)^-1 mod m)
   double rlo[OZ_MAXMOD];   // y / m - rhi
   double Md;               // M = prod m (rounded)
+  double Mlo;              // 0, or (oz_consts_cert) what Md lacks: the scale is Md + Mlo
   int nmod;
   int beta;                // operand bits
 };
@@ -163,16 +164,95 @@ __host__ __device__ __forceinline__ uint2 oz_residues8(const OzDigits (&d)[8], c
   return make_uint2(oz_pack4(v[0], v[1], v[2], v[3]), oz_pack4(v[4], v[5], v[6], v[7]));
 }
 
-// e_j for every column j < np2 (one wave per column, rows k >= j; columns past np: 0)
+// ---- the certificate: a product whose operands' rows are short in the 2-norm is exact on the
+// first 15 moduli (191 dropped), with the operands still at 53 bits.  The data-independent bound
+// |C'| <= K 2^(2 beta) puts every entry of both rows at the row maximum; Cauchy-Schwarz needs
+// the rows' 2-norms only.  Per operand row r the split kernels sum, in integers,
+//   s_r = sum_k y_k^2,  y = (|x'| >> 32) + 1  (x' = rint(ldexp(x, e)), |x'| <= 2^53),
+// so |x'| <= 2^32 y and ||a'_r||_2 <= 2^32 sqrt(s_r); s_r < 2^17 (2^21 + 1)^2 < 2^60 for
+// K <= OZ_MAX_K: no overflow.  With A = max_r s_a, B = max_r s_b and any k range,
+//   |C'_ij| <= ||a'_i|| ||b'_j|| <= 2^64 sqrt(A B) < M15 / 2  iff  A B < M15^2 / 2^130,
+// M15 the product of the first 15 moduli of oz_consts: A B < T15 = floor(M15^2 / 2^130) =
+// 34409203667017820043519436844158 ~ 2^104.76 (A B is an integer).  Then C' is its own centred
+// residue modulo M15 and k_oz_crt reconstructs it from 15 residues (oz_consts_cert).  Integer
+// sums are the same in any order, so the decision is the same from run to run.  Zero, masked
+// and padded entries may add their y = 1 or nothing: the bound holds either way.  Checked on the
+// host against 128-bit integers: tests/host/oz_cert_check.cpp.
+constexpr int OZ_CERT_NMOD = OZ_MAXMOD - 1;
+constexpr unsigned long long OZ_T15_HI = 0x1b24e222aafull, OZ_T15_LO = 0xd866408f6fe8ec7eull;   // T15 = HI 2^64 + LO
+// y^2 of an integer-valued x', |x'| <= 2^53 (the scaling is exact and the conversion truncates)
+__host__ __device__ __forceinline__ unsigned long long oz_cert_term(double xr) {
+  const unsigned y = (unsigned)(fabs(xr) * 0x1p-32) + 1u;
+  return (unsigned long long)y * y;
+}
+// A B < T15, the 128-bit product from 32-bit halves
+__host__ __device__ inline bool oz_cert_ok(unsigned long long A, unsigned long long B) {
+  const unsigned long long a0 = A & 0xffffffffull, a1 = A >> 32, b0 = B & 0xffffffffull, b1 = B >> 32;
+  const unsigned long long p00 = a0 * b0, p01 = a0 * b1, p10 = a1 * b0, p11 = a1 * b1;
+  const unsigned long long mid = (p00 >> 32) + (p01 & 0xffffffffull) + (p10 & 0xffffffffull);
+  const unsigned long long lo = (p00 & 0xffffffffull) | (mid << 32);
+  const unsigned long long hi = p11 + (p01 >> 32) + (p10 >> 32) + (mid >> 32);
+  return hi < OZ_T15_HI || (hi == OZ_T15_HI && lo < OZ_T15_LO);
+}
+// a workgroup's partial row sum into sum[r]: v summed over the workgroup's 256 threads (every
+// thread of the workgroup calls this), one atomic if anything was added
+__device__ __forceinline__ void oz_cert_block_add(unsigned long long v, unsigned long long* __restrict__ sum, int r) {
+  __shared__ unsigned long long part[4];
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    v = part[0] + part[1] + part[2] + part[3];
+    if (v) atomicAdd(sum + r, v);
+  }
+}
+// One workgroup: the flag of a product from its operands' row sums (na rows of sa, nb of sb);
+// mx (or null): the two maxima A and B for a read-back (gpe_oz_cert_sums)
+static __global__ void __launch_bounds__(256) k_oz_cert(const unsigned long long* __restrict__ sa, int na,
+                                                        const unsigned long long* __restrict__ sb, int nb,
+                                                        int* __restrict__ flag, unsigned long long* __restrict__ mx) {
+  __shared__ unsigned long long pa[4], pb[4];
+  unsigned long long A = 0, B = 0;
+  for (int r = threadIdx.x; r < na; r += 256) A = sa[r] > A ? sa[r] : A;
+  for (int r = threadIdx.x; r < nb; r += 256) B = sb[r] > B ? sb[r] : B;
+  for (int off = 32; off > 0; off >>= 1) {
+    const unsigned long long oa = __shfl_xor(A, off, 64), ob = __shfl_xor(B, off, 64);
+    A = oa > A ? oa : A;
+    B = ob > B ? ob : B;
+  }
+  if ((threadIdx.x & 63) == 0) {
+    pa[threadIdx.x >> 6] = A;
+    pb[threadIdx.x >> 6] = B;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < 4; ++w) {
+      A = pa[w] > A ? pa[w] : A;
+      B = pb[w] > B ? pb[w] : B;
+    }
+    *flag = oz_cert_ok(A, B) ? 1 : 0;
+    if (mx) {
+      mx[0] = A;
+      mx[1] = B;
+    }
+  }
+}
+
+// e_j for every column j < np2 (one wave per column, rows k >= j; columns past np: 0); sum (the
+// certificate's row sums, or null): zeroed where the exponent is written
 static __global__ void __launch_bounds__(256) k_oz_colexp(const double* __restrict__ X, long long ldx, int np,
-                                                          int np2, int beta, int* __restrict__ ex) {
+                                                          int np2, int beta, int* __restrict__ ex,
+                                                          unsigned long long* __restrict__ sum) {
   const int lane = threadIdx.x & 63, j = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (j >= np2) return;
   double mx = 0.0;
   if (j < np)
     for (int k = j + lane; k < np; k += 64) mx = oz_pmax(mx, fabs(X[k + (long long)j * ldx]));
   for (int off = 32; off > 0; off >>= 1) mx = oz_pmax(mx, __shfl_xor(mx, off, 64));
-  if (lane == 0) ex[j] = oz_ex_of(mx, beta);
+  if (lane == 0) {
+    ex[j] = oz_ex_of(mx, beta);
+    if (sum) sum[j] = 0ull;
+  }
 }
 
 // X -> the N int8 planes: thread = 8 consecutive rows of one column (a wave reads 4 KB of
@@ -180,21 +260,23 @@ static __global__ void __launch_bounds__(256) k_oz_colexp(const double* __restri
 // np) are zero, and a thread whose 8 rows are all such writes its zeros and nothing else; the
 // residues by oz_residues8.  Precondition: X is 16-byte aligned and ldx even (every column starts on a
 // 16-byte boundary: the double2 loads below; the callers' ldx is n_pad, a multiple of 128).
-// Entries above the diagonal are never read.
+// Entries above the diagonal are never read.  oz_split_thread: one thread's 8 rows of column j;
+// with CERT it returns their share of the column's certificate sum (0 where it stored zeros
+// alone).  sum (or null): the workgroup's share goes to sum[j], one atomic per workgroup.
 constexpr int OZ_SPLIT_ROWS = 8;
-static __global__ void __launch_bounds__(256) k_oz_split(const double* __restrict__ X, long long ldx, int np,
-                                                         int np2, const int* __restrict__ ex, int8_t* __restrict__ planes,
-                                                         long long plane_bytes, OzConst cst) {
-  const int j = blockIdx.x;
+template <bool CERT>
+__device__ __forceinline__ unsigned long long oz_split_thread(const double* __restrict__ X, long long ldx, int np, int np2,
+                                                              const int* __restrict__ ex, int8_t* __restrict__ planes,
+                                                              long long plane_bytes, const OzConst& cst, int j) {
   const int cb = j / OZ_T, r0 = cb * OZ_T;
   const int k0 = r0 + OZ_SPLIT_ROWS * ((int)blockIdx.y * 256 + (int)threadIdx.x);
-  if (k0 >= np2) return;
+  if (k0 >= np2) return 0ull;
   const int e = ex[j];
   const long long ld = np2 - r0;
   int8_t* dst = planes + oz_panel_off(cb, np2) + (long long)(j - r0) * ld + (k0 - r0);
   if (j >= np || k0 >= np || k0 + OZ_SPLIT_ROWS <= j || e == OZ_EX_NAN) {   // all 8 zero: the stores alone
     for (int l = 0; l < cst.nmod; ++l) *reinterpret_cast<uint2*>(dst + (long long)l * plane_bytes) = make_uint2(0u, 0u);
-    return;
+    return 0ull;
   }
   double xs[OZ_SPLIT_ROWS];
   if (k0 + OZ_SPLIT_ROWS <= np && k0 >= j) {   // (16-byte loads: k0 is a multiple of 8)
@@ -212,9 +294,23 @@ static __global__ void __launch_bounds__(256) k_oz_split(const double* __restric
     }
   }
   OzDigits d[OZ_SPLIT_ROWS];
+  unsigned long long s = 0ull;
 #pragma unroll
-  for (int u = 0; u < OZ_SPLIT_ROWS; ++u) d[u] = oz_digits(rint(ldexp(xs[u], e)));   // |.| <= 2^beta
+  for (int u = 0; u < OZ_SPLIT_ROWS; ++u) {
+    const double xr = rint(ldexp(xs[u], e));   // |.| <= 2^beta
+    d[u] = oz_digits(xr);
+    if constexpr (CERT) s += oz_cert_term(xr);
+  }
   for (int l = 0; l < cst.nmod; ++l) *reinterpret_cast<uint2*>(dst + (long long)l * plane_bytes) = oz_residues8(d, cst, l);
+  return s;
+}
+static __global__ void __launch_bounds__(256) k_oz_split(const double* __restrict__ X, long long ldx, int np,
+                                                         int np2, const int* __restrict__ ex, int8_t* __restrict__ planes,
+                                                         long long plane_bytes, OzConst cst,
+                                                         unsigned long long* __restrict__ sum) {
+  const int j = blockIdx.x;
+  if (sum) oz_cert_block_add(oz_split_thread<true>(X, ldx, np, np2, ex, planes, plane_bytes, cst, j), sum, j);
+  else oz_split_thread<false>(X, ldx, np, np2, ex, planes, plane_bytes, cst, j);
 }
 
 __device__ __forceinline__ void oz_glds16(const int8_t* src, int8_t* dst) {
@@ -270,6 +366,9 @@ struct OzGemm {
   long long res_bytes;
   int kdiv = 1;
   int ti0 = 0;
+  // the certificate's flag (k_oz_cert), or null: where it is set, modulus OZ_CERT_NMOD's
+  // workgroups (the grid's last list_len) have nothing to do
+  const int* flag = nullptr;
 };
 // residue tile of (ti, tj): ti ntj + tj, or (tri) ti (ti + 1) / 2 + tj over the lower triangle;
 // tri with ntj > 0: the lower triangle capped at ntj tile columns (tj <= min(ti, ntj - 1)), the
@@ -365,6 +464,7 @@ static __global__ void __launch_bounds__(256, 1) k_oz_gemm(OzGemm g, OzConst cst
   extern __shared__ __attribute__((aligned(16))) double lds_d[];
   int8_t* lds = reinterpret_cast<int8_t*>(lds_d);
   const int l = (int)blockIdx.x / g.list_len;
+  if (l == OZ_CERT_NMOD && g.flag && *g.flag) return;   // certified: 15 moduli carry the product
   const unsigned ent = g.list[(int)blockIdx.x - l * g.list_len];
   if (ent == 0xffffffffu) return;
   const int ti = (int)(ent >> 16), tj = (int)(ent & 0xffffu);
@@ -531,8 +631,9 @@ struct OzCrt {
 // one: the sums wait for memory once.  NM: the number of moduli at compile time (16, the default's), or 0: cst.nmod
 // (6 .. 15), the same code with the moduli past nmod skipped.  The sums themselves run over
 // l = 0 .. nmod - 1 in that order for every entry.
-template <int NM>
-static __global__ void __launch_bounds__(256) k_oz_crt(OzCrt g, OzConst cst) {
+// M2: the scale is Md + Mlo (oz_consts_cert), the low part entering by one more fma.
+template <int NM, bool M2 = false>
+__device__ __forceinline__ void oz_crt_entries(const OzCrt& g, const OzConst& cst) {
   const int nmod = NM ? NM : cst.nmod;
   const int t = (int)blockIdx.x >> 4;
   const int u = ((int)blockIdx.x & 15) * 256 + (int)threadIdx.x;
@@ -588,7 +689,7 @@ static __global__ void __launch_bounds__(256) k_oz_crt(OzCrt g, OzConst cst) {
         slo[r] = fma(cv, rl, slo[r]);
       }
     }
-  const double sc = g.alpha * cst.Md;
+  const double sc = g.alpha * cst.Md, scl = g.alpha * cst.Mlo;
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
     const int gn = gn0 + (r & 3) + 8 * (r >> 2);
@@ -597,9 +698,39 @@ static __global__ void __launch_bounds__(256) k_oz_crt(OzCrt g, OzConst cst) {
     const int en = ec[r >> 2][r & 3];
     double* dst = g.C + (gm - OZ_T * g.ti0 + (long long)gn * g.ldc);
     const double s = ldexp(sc, -(em + en));
-    if (em == OZ_EX_NAN || en == OZ_EX_NAN) *dst = __builtin_nan("");
-    else *dst = g.acc ? fma(v, s, *dst) : v * s;
+    if (em == OZ_EX_NAN || en == OZ_EX_NAN) {
+      *dst = __builtin_nan("");
+    } else if constexpr (M2) {   // v (s + sl): sl below half an ulp of s, its term rounded into the result
+      const double sl = ldexp(scl, -(em + en));
+      if (g.acc) {
+        // C + v (s + sl) to one rounding (and a second-order term): p + pe = v (s + sl), t + err = C + p,
+        // both error-free.  A plain fma(v, sl, fma(v, s, C)) loses v sl wherever |C| is not far below
+        // |v s|, which leaves every entry with the scale s alone: the common factor that oz_consts_cert
+        // exists to remove
+        const double c0 = *dst;
+        const double p = __dmul_rn(v, s), pe = fma(v, sl, fma(v, s, -p));
+        const double t = __dadd_rn(c0, p), bb = __dsub_rn(t, c0);
+        const double err = __dadd_rn(__dsub_rn(c0, __dsub_rn(t, bb)), __dsub_rn(p, bb));
+        *dst = __dadd_rn(t, __dadd_rn(err, pe));
+      } else {
+        *dst = fma(v, s, v * sl);
+      }
+    } else {
+      *dst = g.acc ? fma(v, s, *dst) : v * s;
+    }
   }
+}
+template <int NM>
+static __global__ void __launch_bounds__(256) k_oz_crt(OzCrt g, OzConst cst) {
+  oz_crt_entries<NM>(g, cst);
+}
+// A product with a certificate (N = 16): where the flag is set, the same sums over l = 0 .. 14
+// with the 15-moduli constants c15 (oz_consts_cert: rhi, rlo and the scale Md + Mlo = M15 as
+// the 16-moduli Md rounds it; the sixteenth residue is not read); where it is not,
+// k_oz_crt<16>'s arithmetic
+static __global__ void __launch_bounds__(256) k_oz_crt_cert(OzCrt g, OzConst cst, OzConst c15, const int* __restrict__ flag) {
+  if (*flag) oz_crt_entries<OZ_CERT_NMOD, true>(g, c15);
+  else oz_crt_entries<OZ_MAXMOD>(g, cst);
 }
 
 // ---- rectangular operands (the TRTRI's products): op(r, k) of an fp64 block src (ld) is
@@ -616,7 +747,8 @@ __device__ __forceinline__ bool oz_keep(int mask, int r, int k) {
 // before), then k_oz_il_to_ex.
 template <bool TRANS>
 static __global__ void __launch_bounds__(256) k_oz_rowexp(const double* __restrict__ src, long long ld, int R, int Rp,
-                                                          int Kv, int mask, int beta, int* __restrict__ ex) {
+                                                          int Kv, int mask, int beta, int* __restrict__ ex,
+                                                          unsigned long long* __restrict__ sum) {
   if constexpr (!TRANS) {
     const int lane = threadIdx.x & 63, r = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (r >= Rp) return;
@@ -625,7 +757,10 @@ static __global__ void __launch_bounds__(256) k_oz_rowexp(const double* __restri
       for (int k = lane; k < Kv; k += 64)
         if (oz_keep(mask, r, k)) mx = oz_pmax(mx, fabs(src[k + (long long)r * ld]));
     for (int off = 32; off > 0; off >>= 1) mx = oz_pmax(mx, __shfl_xor(mx, off, 64));
-    if (lane == 0) ex[r] = oz_ex_of(mx, beta);
+    if (lane == 0) {
+      ex[r] = oz_ex_of(mx, beta);
+      if (sum) sum[r] = 0ull;   // (the certificate's row sums: zeroed where the exponent is written)
+    }
   } else {
     __shared__ double red[4][64];
     const int rl = threadIdx.x & 63, q = threadIdx.x >> 6, r = blockIdx.x * 64 + rl;
@@ -646,9 +781,13 @@ static __global__ void __launch_bounds__(256) k_oz_rowexp(const double* __restri
     }
   }
 }
-static __global__ void __launch_bounds__(256) k_oz_il_to_ex(int* __restrict__ ex, int Rp, int beta) {
+static __global__ void __launch_bounds__(256) k_oz_il_to_ex(int* __restrict__ ex, int Rp, int beta,
+                                                            unsigned long long* __restrict__ sum) {
   const int r = blockIdx.x * 256 + threadIdx.x;
-  if (r < Rp) ex[r] = ex[r] >= OZ_IL_BAD ? OZ_EX_NAN : (ex[r] > 0 ? (beta - 1) - (ex[r] - 2048) : 0);
+  if (r < Rp) {
+    ex[r] = ex[r] >= OZ_IL_BAD ? OZ_EX_NAN : (ex[r] > 0 ? (beta - 1) - (ex[r] - 2048) : 0);
+    if (sum) sum[r] = 0ull;
+  }
 }
 
 // op -> the N int8 planes, rectangular (row r at r ldp + k, k < Kp; zero past R / Kv and
@@ -664,11 +803,14 @@ template <bool TRANS>
 static __global__ void __launch_bounds__(256) k_oz_split_rect(const double* __restrict__ src, long long ld, int R,
                                                               int Kv, int mask, const int* __restrict__ ex,
                                                               int8_t* __restrict__ planes, long long plane_bytes,
-                                                              long long ldp, int Kp, OzConst cst) {
+                                                              long long ldp, int Kp, OzConst cst,
+                                                              unsigned long long* __restrict__ sum) {
   if constexpr (!TRANS) {
     const int r = blockIdx.x;
+    // this thread's 8 entries; its share of the row's certificate sum (0 where it stores zeros alone)
+    const auto thread8 = [&]() -> unsigned long long {
     const int k0 = ((int)blockIdx.y * 256 + (int)threadIdx.x) * 8;
-    if (k0 >= Kp) return;
+    if (k0 >= Kp) return 0ull;
     const int e = ex[r];
     const double* p = src + k0 + (long long)r * ld;
     // the mask's diagonal k = r: all 8 kept (1), all dropped (0), or mixed (2)
@@ -677,7 +819,7 @@ static __global__ void __launch_bounds__(256) k_oz_split_rect(const double* __re
     int8_t* dst = planes + (long long)r * ldp + k0;
     if (side == 0 || r >= R || k0 >= Kv || e == OZ_EX_NAN) {   // all 8 zero: the stores alone
       for (int l = 0; l < cst.nmod; ++l) *reinterpret_cast<uint2*>(dst + (long long)l * plane_bytes) = make_uint2(0u, 0u);
-      return;
+      return 0ull;
     }
     double xs[8];
     if (k0 + 8 <= Kv && side == 1 && ((reinterpret_cast<uintptr_t>(p) & 15) == 0)) {
@@ -695,9 +837,18 @@ static __global__ void __launch_bounds__(256) k_oz_split_rect(const double* __re
       }
     }
     OzDigits d[8];
+    unsigned long long s = 0ull;
 #pragma unroll
-    for (int u = 0; u < 8; ++u) d[u] = oz_digits(rint(ldexp(xs[u], e)));
+    for (int u = 0; u < 8; ++u) {
+      const double xr = rint(ldexp(xs[u], e));
+      d[u] = oz_digits(xr);
+      if (sum) s += oz_cert_term(xr);
+    }
     for (int l = 0; l < cst.nmod; ++l) *reinterpret_cast<uint2*>(dst + (long long)l * plane_bytes) = oz_residues8(d, cst, l);
+    return s;
+    };
+    const unsigned long long s = thread8();
+    if (sum) oz_cert_block_add(s, sum, r);   // (sum: the same for the whole workgroup) one atomic per workgroup
   } else {
     constexpr int PL = 4;   // planes per LDS round
     __shared__ __attribute__((aligned(16))) unsigned tr[PL][64 * 20];   // [plane][row][16 words + 4 pad]
@@ -735,10 +886,29 @@ static __global__ void __launch_bounds__(256) k_oz_split_rect(const double* __re
       x1[u] = oz_keep(mask, r + 1, k) ? b : 0.0;
     }
     OzDigits d0[8], d1[8];
+    unsigned long long s0 = 0ull, s1 = 0ull;
 #pragma unroll
     for (int u = 0; u < 8; ++u) {
-      d0[u] = oz_digits(e0 == OZ_EX_NAN ? 0.0 : rint(ldexp(x0[u], e0)));
-      d1[u] = oz_digits(e1 == OZ_EX_NAN ? 0.0 : rint(ldexp(x1[u], e1)));
+      const double xr0 = e0 == OZ_EX_NAN ? 0.0 : rint(ldexp(x0[u], e0));
+      const double xr1 = e1 == OZ_EX_NAN ? 0.0 : rint(ldexp(x1[u], e1));
+      d0[u] = oz_digits(xr0);
+      d1[u] = oz_digits(xr1);
+      if (sum) {
+        s0 += oz_cert_term(xr0);
+        s1 += oz_cert_term(xr1);
+      }
+    }
+    if (sum) {   // (the same for the whole workgroup) the 64 rows' certificate sums: one atomic per row
+      __shared__ unsigned long long rs[8][64];
+      rs[kg][2 * rp] = s0;
+      rs[kg][2 * rp + 1] = s1;
+      __syncthreads();
+      if (threadIdx.x < 64) {
+        unsigned long long t = 0ull;
+#pragma unroll
+        for (int q = 0; q < 8; ++q) t += rs[q][threadIdx.x];
+        atomicAdd(sum + (long long)blockIdx.x * 64 + threadIdx.x, t);
+      }
     }
     for (int l0 = 0; l0 < cst.nmod; l0 += PL) {
       if (l0 > 0) __syncthreads();   // (the previous round's reads done)
@@ -796,6 +966,29 @@ inline OzConst oz_consts(int nmod, int np2) {
     k.rhi[l] = std::ldexp((double)Q, -41);
     k.rlo[l] = std::ldexp((double)R / (double)m, -41);
   }
+  return k;
+}
+
+// The reconstruction constants of a certified product: the first 15 moduli with the operands
+// still at 53 bits.  oz_consts(15, .) alone would lower beta to what 15 moduli carry without a
+// certificate (|C'| <= np2 2^(2 beta) < M15 / 2: 51 bits at np2 = 16384); here the certificate
+// bounds |C'|, beta stays the 16-moduli context's, and only rhi, rlo and the scale are used
+// (k_oz_crt_cert) -- the moduli, weights and reciprocals are the first 15 of the 16.
+// The scale: Md is one rounding of M, the same relative error e in every entry of a product (of
+// 16 moduli: 1.13 2^-53; of 15 alone: -0.66 2^-53 or so), and the objective's gradient, a
+// difference of large terms, magnifies what is common to all entries (measured at n = 1100:
+// 15-moduli products scaled by fl(M15) moved the gradient 2.1e-13 of its scale from the
+// 16-moduli result, three times the 16-moduli result's own distance from the fp64 path).  So a
+// certified product is scaled by Md16 / 191 carried in two doubles (Md + Mlo, exact to 2^-105):
+// M15 with the 16-moduli constant's own e, and a product's value does not depend on whether it
+// was certified beyond the reconstruction's last roundings.
+inline OzConst oz_consts_cert(int np2) {
+  OzConst k = oz_consts(OZ_CERT_NMOD, np2);
+  const OzConst k16 = oz_consts(OZ_MAXMOD, np2);
+  const double last = (double)k16.m[OZ_CERT_NMOD];
+  k.beta = k16.beta;
+  k.Md = k16.Md / last;
+  k.Mlo = std::fma(-k.Md, last, k16.Md) / last;   // (the division's remainder is exact)
   return k;
 }
 
@@ -858,36 +1051,41 @@ struct OzSrc {
   bool trans;
 };
 // its row exponents into ex[0, P) (P = R padded to 256) ...
-inline void oz_operand_exp(hipStream_t st, const OzConst& k, const OzSrc& o, int P, int* ex) {
+// (sum, here and below: the certificate's row sums beside ex, or null)
+inline void oz_operand_exp(hipStream_t st, const OzConst& k, const OzSrc& o, int P, int* ex,
+                           unsigned long long* sum = nullptr) {
   if (o.trans) {
     (void)hipMemsetAsync(ex, 0, (size_t)P * sizeof(int), st);
     hipLaunchKernelGGL(k_oz_rowexp<true>, dim3(P / 64, (o.Kv + 255) / 256), dim3(256), 0, st, o.src, o.ld, o.R, P, o.Kv,
-                       o.mask, k.beta, ex);
-    hipLaunchKernelGGL(k_oz_il_to_ex, dim3((P + 255) / 256), dim3(256), 0, st, ex, P, k.beta);
+                       o.mask, k.beta, ex, sum);
+    hipLaunchKernelGGL(k_oz_il_to_ex, dim3((P + 255) / 256), dim3(256), 0, st, ex, P, k.beta, sum);
   } else {
-    hipLaunchKernelGGL(k_oz_rowexp<false>, dim3(P / 4), dim3(256), 0, st, o.src, o.ld, o.R, P, o.Kv, o.mask, k.beta, ex);
+    hipLaunchKernelGGL(k_oz_rowexp<false>, dim3(P / 4), dim3(256), 0, st, o.src, o.ld, o.R, P, o.Kv, o.mask, k.beta, ex,
+                       sum);
   }
 }
 // ... and its planes: P rows of Kp bytes (a multiple of 64) per modulus, P Kp bytes apart
-inline void oz_operand_split(hipStream_t st, const OzConst& k, const OzSrc& o, int P, int Kp, const int* ex, int8_t* planes) {
+inline void oz_operand_split(hipStream_t st, const OzConst& k, const OzSrc& o, int P, int Kp, const int* ex, int8_t* planes,
+                             unsigned long long* sum = nullptr) {
   if (o.trans)
     hipLaunchKernelGGL(k_oz_split_rect<true>, dim3(P / 64, Kp / 64), dim3(256), 0, st, o.src, o.ld, o.R, o.Kv, o.mask, ex,
-                       planes, (long long)P * Kp, (long long)Kp, Kp, k);
+                       planes, (long long)P * Kp, (long long)Kp, Kp, k, sum);
   else
     hipLaunchKernelGGL(k_oz_split_rect<false>, dim3(P, (Kp + 2047) / 2048), dim3(256), 0, st, o.src, o.ld, o.R, o.Kv,
-                       o.mask, ex, planes, (long long)P * Kp, (long long)Kp, Kp, k);
+                       o.mask, ex, planes, (long long)P * Kp, (long long)Kp, Kp, k, sum);
 }
-inline void oz_operand(hipStream_t st, const OzConst& k, const OzSrc& o, int P, int Kp, int* ex, int8_t* planes) {
-  oz_operand_exp(st, k, o, P, ex);
-  oz_operand_split(st, k, o, P, Kp, ex, planes);
+inline void oz_operand(hipStream_t st, const OzConst& k, const OzSrc& o, int P, int Kp, int* ex, int8_t* planes,
+                       unsigned long long* sum = nullptr) {
+  oz_operand_exp(st, k, o, P, ex, sum);
+  oz_operand_split(st, k, o, P, Kp, ex, planes, sum);
 }
 // the packed operand (the LAUUM's): column exponents and the lower column panels of X (np x np
 // of the padded order np2, ld ldx), oz_plane_bytes(np2) per modulus
 inline void oz_operand_packed(hipStream_t st, const OzConst& k, const double* X, long long ldx, int np, int np2, int* ex,
-                              int8_t* planes) {
-  hipLaunchKernelGGL(k_oz_colexp, dim3((np2 + 3) / 4), dim3(256), 0, st, X, ldx, np, np2, k.beta, ex);
+                              int8_t* planes, unsigned long long* sum = nullptr) {
+  hipLaunchKernelGGL(k_oz_colexp, dim3((np2 + 3) / 4), dim3(256), 0, st, X, ldx, np, np2, k.beta, ex, sum);
   hipLaunchKernelGGL(k_oz_split, dim3(np2, (np2 + 256 * OZ_SPLIT_ROWS - 1) / (256 * OZ_SPLIT_ROWS)), dim3(256), 0, st, X,
-                     ldx, np, np2, ex, planes, oz_plane_bytes(np2), k);
+                     ldx, np, np2, ex, planes, oz_plane_bytes(np2), k, sum);
 }
 
 // A product's shape, stated once: tile rows [ti0, ti0 + nti) against ntj tile columns, or (tri)
@@ -942,6 +1140,19 @@ struct OzOut {
   double alpha;
   int acc = 0;
 };
+// A product's certificate (optional; flag null: none, the product runs on every modulus of the
+// context): the operands' row sums (na rows of a's, nb of b's: every row the product may read),
+// a device int for its flag and the 15-moduli constants (oz_consts_cert).  Used only where the
+// context runs 16 moduli.
+struct OzCert {
+  const unsigned long long* sa = nullptr;
+  int na = 0;
+  const unsigned long long* sb = nullptr;
+  int nb = 0;
+  int* flag = nullptr;
+  const OzConst* c15 = nullptr;
+  unsigned long long* maxima = nullptr;   // (optional) A = max s_a and B = max s_b go here
+};
 // One product: its shape, the operands' planes, the shape's list on the device, the residue
 // buffer (res_bytes per modulus, at least s.res_bytes()) and the output
 struct OzProduct {
@@ -952,22 +1163,32 @@ struct OzProduct {
   int8_t* res;
   long long res_bytes;
   OzOut out;
+  OzCert cert{};
 };
 // The one launch of k_oz_gemm (a workgroup per modulus and list position, the whole ring as
 // dynamic LDS: one workgroup per CU) and of k_oz_crt (16 workgroups per residue tile) behind
 // it.  e0, e1: events recorded just before and after k_oz_gemm (gpe_ozaki_stats times it alone).
+// With a certificate, k_oz_cert first (after the conversions, in stream order): the flag stays on
+// the device, where k_oz_gemm's last list_len workgroups and k_oz_crt_cert read it; the host
+// never waits for it.
 inline hipError_t oz_product_launch(hipStream_t st, const OzConst& k, const OzProduct& p, hipEvent_t e0 = nullptr,
                                     hipEvent_t e1 = nullptr) {
   const OzShape& s = p.s;
   const int ntj = s.ntj;   // (tri: 0, or the cap)
-  const OzGemm g{p.a, p.b, p.list, p.list_len, s.K, s.kbeg, s.kend, s.tri, ntj, p.res, p.res_bytes, s.kdiv, s.ti0};
+  const OzCert& ct = p.cert;
+  const bool cert = ct.flag && ct.c15 && k.nmod == OZ_MAXMOD;
+  const OzGemm g{p.a, p.b, p.list, p.list_len, s.K, s.kbeg, s.kend, s.tri, ntj, p.res, p.res_bytes, s.kdiv, s.ti0,
+                 cert ? ct.flag : nullptr};
   const OzOut& o = p.out;
   const OzCrt r{p.res, p.res_bytes, s.tri, ntj, o.exr, o.exc, o.C, o.ldc, o.rows, o.cols, o.lower128, o.alpha, s.ti0, o.acc};
   hipError_t e;
+  if (cert) hipLaunchKernelGGL(k_oz_cert, dim3(1), dim3(256), 0, st, ct.sa, ct.na, ct.sb, ct.nb, ct.flag,
+                             ct.maxima);
   if (e0 && (e = hipEventRecord(e0, st)) != hipSuccess) return e;
   hipLaunchKernelGGL(k_oz_gemm, dim3((unsigned)(k.nmod * g.list_len)), dim3(256), OZ_LDS, st, g, k);
   if (e1 && (e = hipEventRecord(e1, st)) != hipSuccess) return e;
-  if (k.nmod == OZ_MAXMOD) hipLaunchKernelGGL(k_oz_crt<OZ_MAXMOD>, dim3((unsigned)(s.tiles() * 16)), dim3(256), 0, st, r, k);
+  if (cert) hipLaunchKernelGGL(k_oz_crt_cert, dim3((unsigned)(s.tiles() * 16)), dim3(256), 0, st, r, k, *ct.c15, ct.flag);
+  else if (k.nmod == OZ_MAXMOD) hipLaunchKernelGGL(k_oz_crt<OZ_MAXMOD>, dim3((unsigned)(s.tiles() * 16)), dim3(256), 0, st, r, k);
   else hipLaunchKernelGGL(k_oz_crt<0>, dim3((unsigned)(s.tiles() * 16)), dim3(256), 0, st, r, k);
   return hipGetLastError();
 }
@@ -1066,35 +1287,48 @@ inline OzCholNest oz_chol_nest_plan(int q, int h, int NB) {
 // (q.l21: planes at planes, exponents at ex) is already there (ordered before st's work by the
 // caller).  gc(p, ops, flops64) launches one product (oz_product_launch).  part: 0 both
 // products, 1 the first alone (T, which needs X11 and not X22), 2 the second alone (T is there).
-template <class GC>
+// sum (or null): the certificate's row sums beside ex (Pa + Pb; with l21_done L21's are there as
+// its exponents are); cert(sa, na, sb, nb) then makes each product's certificate.
+template <class GC, class CT>
 void oz_tri_pair_launches(hipStream_t st, const OzConst& k, const OzTriPair& q, const unsigned* lists, const double* L21,
                           const double* X11, const double* X22, double* X21, long long ld, double* T, int8_t* planes,
-                          int8_t* res, int* ex, bool l21_done, GC gc, int part = 0) {
+                          int8_t* res, int* ex, bool l21_done, GC gc, int part, unsigned long long* sum, CT cert) {
   int* exA = ex;
   int* exB = ex + q.Pb;
+  unsigned long long* sA = sum;
+  unsigned long long* sB = sum ? sum + q.Pb : nullptr;
   int8_t* PA = planes;
   const long long rb = q.shape_a().res_bytes();
   if (part != 2) {   // T = L21 X11
     const long long pA = (long long)q.Pb * q.Pa, pB = (long long)q.Pa * q.Pa;
     int8_t* PB = planes + (size_t)k.nmod * pA;
-    if (!l21_done) oz_operand(st, k, q.l21(L21, ld), q.Pb, q.Pa, exA, PA);
-    oz_operand(st, k, OzSrc{X11, ld, q.Ra, q.Ra, 1, false}, q.Pa, q.Pa, exB, PB);
+    if (!l21_done) oz_operand(st, k, q.l21(L21, ld), q.Pb, q.Pa, exA, PA, sA);
+    oz_operand(st, k, OzSrc{X11, ld, q.Ra, q.Ra, 1, false}, q.Pa, q.Pa, exB, PB, sB);
     gc(OzProduct{q.shape_a(), OzOpnd{PA, pA, q.Pa, 0}, OzOpnd{PB, pB, q.Pa, 0}, lists + q.la_off, q.la_len, res, rb,
-                 OzOut{exA, exB, T, (long long)q.Pb, q.Rb, q.Ra, 0, 1.0}},
+                 OzOut{exA, exB, T, (long long)q.Pb, q.Rb, q.Ra, 0, 1.0}, sum ? cert(sA, q.Pb, sB, q.Pa) : OzCert{}},
        q.ops_a, (double)q.Ra * q.Ra * q.Rb);
   }
   if (part != 1) {   // X21 = -X22 T (both operands' exponents, then both operands' planes)
     const long long pA = (long long)q.Pb * q.Pb, pB = (long long)q.Pa * q.Pb;
     int8_t* PB = planes + (size_t)k.nmod * pA;
     const OzSrc x22{X22, ld, q.Rb, q.Rb, 2, true}, t{T, (long long)q.Pb, q.Ra, q.Rb, 0, false};
-    oz_operand_exp(st, k, x22, q.Pb, exA);
-    oz_operand_exp(st, k, t, q.Pa, exB);
-    oz_operand_split(st, k, x22, q.Pb, q.Pb, exA, PA);
-    oz_operand_split(st, k, t, q.Pa, q.Pb, exB, PB);
+    oz_operand_exp(st, k, x22, q.Pb, exA, sA);
+    oz_operand_exp(st, k, t, q.Pa, exB, sB);
+    oz_operand_split(st, k, x22, q.Pb, q.Pb, exA, PA, sA);
+    oz_operand_split(st, k, t, q.Pa, q.Pb, exB, PB, sB);
     gc(OzProduct{q.shape_b(), OzOpnd{PA, pA, q.Pb, 0}, OzOpnd{PB, pB, q.Pb, 0}, lists + q.lb_off, q.lb_len, res, rb,
-                 OzOut{exA, exB, X21, ld, q.Rb, q.Ra, 0, -1.0}},
+                 OzOut{exA, exB, X21, ld, q.Rb, q.Ra, 0, -1.0}, sum ? cert(sA, q.Pb, sB, q.Pa) : OzCert{}},
        q.ops_b, (double)q.Rb * q.Rb * q.Ra);
   }
+}
+
+// (without certificates: the row-block path)
+template <class GC>
+void oz_tri_pair_launches(hipStream_t st, const OzConst& k, const OzTriPair& q, const unsigned* lists, const double* L21,
+                          const double* X11, const double* X22, double* X21, long long ld, double* T, int8_t* planes,
+                          int8_t* res, int* ex, bool l21_done, GC gc, int part = 0) {
+  oz_tri_pair_launches(st, k, q, lists, L21, X11, X22, X21, ld, T, planes, res, ex, l21_done, gc, part, nullptr,
+                       [](const unsigned long long*, int, const unsigned long long*, int) { return OzCert{}; });
 }
 
 }  // namespace gpe

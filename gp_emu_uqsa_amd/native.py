@@ -67,6 +67,10 @@ SIGNATURES = {
     "gpe_test_oz_product": (_ct.c_int, [_VP, _ct.POINTER(OzOperand), _ct.POINTER(OzOperand),
                                         _ct.POINTER(OzParams), _D, _ct.POINTER(_ct.c_int32),
                                         _ct.POINTER(_ct.c_int32), _ct.POINTER(_ct.c_int8)]),
+    "gpe_test_oz_product_cert": (_ct.c_int, [_VP, _ct.POINTER(OzOperand), _ct.POINTER(OzOperand),
+                                             _ct.POINTER(OzParams), _D, _ct.POINTER(_ct.c_int32),
+                                             _ct.POINTER(_ct.c_int32), _ct.POINTER(_ct.c_int8),
+                                             _ct.POINTER(_ct.c_int32)]),
     "gpe_test_oz_planes": (_ct.c_int, [_VP, _ct.POINTER(OzOperand), _ct.c_int32, _ct.c_int32, _ct.c_int32,
                                        _ct.POINTER(_ct.c_int32), _ct.POINTER(_ct.c_int8)]),
     "gpe_abi_version": (_ct.c_int, []),
@@ -129,6 +133,8 @@ SIGNATURES = {
     "gpe_phase_times": (_ct.c_int, [_VP, _D, _ct.c_int32]),
     "gpe_gemm_stats": (_ct.c_int, [_VP, _D, _D, _D]),
     "gpe_ozaki_stats": (_ct.c_int, [_VP, _D, _D, _D, _D]),
+    "gpe_oz_cert_stats": (_ct.c_int, [_VP, _ct.POINTER(_ct.c_int32), _ct.POINTER(_ct.c_int32)]),
+    "gpe_oz_cert_sums": (_ct.c_int, [_VP, _ct.c_int32, _ct.POINTER(_ct.c_uint64), _ct.POINTER(_ct.c_uint64)]),
     # include/gpemu_dist.h: row-block distributed value objective (RCCL / loopback)
     "gpe_dist_unique_id": (_ct.c_int, [_ct.c_char_p, _ct.c_int32]),
     "gpe_dist_create": (_VP, [_ct.c_int32, _ct.c_int32, _ct.c_int32, _ct.c_char_p]),
@@ -686,14 +692,15 @@ class Context:
 
     def test_oz_product(self, a, b=None, *, C, ldc, packed=False, K=0, kbeg=0, kend=0, kdiv=1, ti0=0,
                         tri=False, lower128=False, alpha=1.0, acc=False, nmod=16, rows=0, cols=0,
-                        res_mod=None):
+                        res_mod=None, cert=False):
         """One exact int8 product through the production kernels (gpe_test_oz_product, a test
         hook).  a, b: dicts with src (1-d fp64 array, sent as it is), ld and optionally offset,
         trans, R, Kv, mask; b None: B is A.  C: 1-d fp64 array, the column-major output with
         leading dimension ldc (copied, read when acc).  Returns dict(C, exa, exb, res): the
         new C, the row exponents of both operands (padded to 256) and, with res_mod, the
         centred residues of that modulus as int8 (padded rows from tile row ti0 x padded
-        columns)."""
+        columns).  cert: through gpe_test_oz_product_cert, the same product with a 15-moduli
+        certificate; the dict then also holds nmod_used (15 certified, 16 refused)."""
         keep = []
 
         def opnd(o):
@@ -715,10 +722,14 @@ class Context:
         exb = _np.zeros(max(Pb, 1), dtype=_np.int32)
         res = None if res_mod is None else _np.zeros((max(Pa - 256 * int(ti0), 1), max(Pb, 1)), dtype=_np.int8)
         i32 = _ct.POINTER(_ct.c_int32)
-        self._check(self.lib.gpe_test_oz_product(
-            self._h, _ct.byref(oa), _ct.byref(ob) if ob is not None else None, _ct.byref(p), _ptr(Cc),
-            exa.ctypes.data_as(i32), exb.ctypes.data_as(i32),
-            None if res is None else res.ctypes.data_as(_ct.POINTER(_ct.c_int8))), "gpe_test_oz_product")
+        args = (self._h, _ct.byref(oa), _ct.byref(ob) if ob is not None else None, _ct.byref(p), _ptr(Cc),
+                exa.ctypes.data_as(i32), exb.ctypes.data_as(i32),
+                None if res is None else res.ctypes.data_as(_ct.POINTER(_ct.c_int8)))
+        if cert:
+            used = _ct.c_int32(0)
+            self._check(self.lib.gpe_test_oz_product_cert(*args, _ct.byref(used)), "gpe_test_oz_product_cert")
+            return {"C": Cc, "exa": exa, "exb": exb, "res": res, "nmod_used": used.value}
+        self._check(self.lib.gpe_test_oz_product(*args), "gpe_test_oz_product")
         return {"C": Cc, "exa": exa, "exb": exb, "res": res}
 
     def test_oz_planes(self, a, *, packed=False, K=0, nmod=16):
@@ -799,6 +810,23 @@ class Context:
         self._check(self.lib.gpe_ozaki_stats(self._h, _ct.byref(ms), _ct.byref(nl), _ct.byref(ops), _ct.byref(fl)),
                     "gpe_ozaki_stats")
         return {"ms": ms.value, "launches": nl.value, "int8_ops": ops.value, "fp64_flops": fl.value}
+
+    def oz_cert_stats(self):
+        """The 15-moduli certificates of the most recent objective's int8 products: how many
+        products carried one and how many were certified (gpe_oz_cert_stats)."""
+        n, k = _ct.c_int32(0), _ct.c_int32(0)
+        self._check(self.lib.gpe_oz_cert_stats(self._h, _ct.byref(n), _ct.byref(k)), "gpe_oz_cert_stats")
+        return {"products": n.value, "certified": k.value}
+
+    def oz_cert_sums(self):
+        """(A, B) = (max s_a, max s_b) of each of those products, in launch order, as Python ints
+        (gpe_oz_cert_sums, a debug read-back); certified iff A B < T15."""
+        n = self.oz_cert_stats()["products"]
+        a, b = _np.zeros(max(n, 1), dtype=_np.uint64), _np.zeros(max(n, 1), dtype=_np.uint64)
+        u64 = _ct.POINTER(_ct.c_uint64)
+        self._check(self.lib.gpe_oz_cert_sums(self._h, n, a.ctypes.data_as(u64), b.ctypes.data_as(u64)),
+                    "gpe_oz_cert_sums")
+        return [(int(a[i]), int(b[i])) for i in range(n)]
 
 
 _default_ctx = None

@@ -485,6 +485,14 @@ int gpe_test_oz_product(gpe_ctx* ctx, const gpe_oz_operand* a, const gpe_oz_oper
                         const gpe_oz_params* p, double* C, int32_t* exa_out, int32_t* exb_out,
                         int8_t* res_out);
 
+/* The same product with a 15-moduli certificate (gpemu_ozaki.hpp: OzCert), an addition within
+ * ABI 10: the operand conversions also form the row sums, k_oz_cert decides, and k_oz_gemm and
+ * k_oz_crt_cert run as the objective's products do.  nmod must be 16.  nmod_used_out (required):
+ * 15 where the certificate held, 16 where it was refused. */
+int gpe_test_oz_product_cert(gpe_ctx* ctx, const gpe_oz_operand* a, const gpe_oz_operand* b,
+                             const gpe_oz_params* p, double* C, int32_t* exa_out, int32_t* exb_out,
+                             int8_t* res_out, int32_t* nmod_used_out);
+
 /* Test hook for one operand's conversion (gpemu_ozaki.hpp), an addition within ABI 10; the
  * reference has no counterpart.  The operand a (as gpe_test_oz_product's: a window of a host
  * array, R rows padded to P, a multiple of 256) goes through the production oz_operand
@@ -670,11 +678,22 @@ int gpe_gemm_stats(gpe_ctx* ctx, double* ms_out, double* launches_out,
 
 /* The same for the int8 products of the objective's A^-1 and of the top TRTRI level
  * (gpemu_ozaki.hpp: the fp64 products emulated exactly on the i8 MFMA, N moduli): their
- * device time (ms), launch count, int8 multiply-add ops (2 per multiply-add, every modulus)
+ * device time (ms), launch count, int8 multiply-add ops (2 per multiply-add, every modulus that ran: 15 for a certified product)
  * and the fp64 flops of the products they replace.  Internal instrumentation for bench.py;
  * the reference has no counterpart. */
 int gpe_ozaki_stats(gpe_ctx* ctx, double* ms_out, double* launches_out, double* int8_ops_out,
                     double* fp64_flops_out);
+
+/* The 15-moduli certificates of the int8 products of the most recent factorisation or
+ * objective (an addition within ABI 10; no profiling needed): how many products carried a
+ * certificate (0 with GPEMU_OZAKI_CERT=0, fewer than 16 moduli or no int8 product) and how
+ * many of those were certified and ran on 15 moduli.  Waits for the context's streams. */
+int gpe_oz_cert_stats(gpe_ctx* ctx, int32_t* products_out, int32_t* certified_out);
+
+/* The same products' row-sum maxima, in launch order (an addition within ABI 10; a debug
+ * read-back, outside timed runs): A = max_r s_a and B = max_r s_b of the first min(cap,
+ * products) products; a product is certified iff A B < T15 (gpemu_ozaki.hpp). */
+int gpe_oz_cert_sums(gpe_ctx* ctx, int32_t cap, uint64_t* a_out, uint64_t* b_out);
 
 #ifdef __cplusplus
 }
