@@ -40,6 +40,7 @@
 #include "gpemu_postmean_multi.hpp"
 #include "gpemu_postgroup.hpp"
 #include "gpemu_hm.hpp"
+#include "gpemu_hm_mv.hpp"
 #include "gpemu_host_alloc.hpp"
 
 using namespace gpe;
@@ -3182,9 +3183,26 @@ int posterior_mean_impl(gpe_ctx* c, int64_t m, const double* Xs, const double* H
       });
 }
 
-// The posterior means of the p outputs of gpe_set_outputs (gpe_posterior_mean_multi):
-// Gamma = A^-1 (F - H B) by Posterior::setup()'s route to gamma (L^-1, then L^-T, of the
-// columns) into dWm, k_post_mean_multi with one workgroup per PMM_PTS points and segment of rows.
+// Gamma = A^-1 (F - H B) of the p outputs of gpe_set_outputs into the first p columns of dWm, by
+// Posterior::setup()'s route to gamma (L^-1, then L^-T, of the columns); queued on the
+// context's stream.  pin_t: (p + q) p pinned doubles for [I; -B].  L^-1 must be resident
+// (ensure_linv).  For gpe_posterior_mean_multi and gpe_hm_add_multi.
+int multi_gamma(gpe_ctx* c, const double* B, double* pin_t) {
+  const int q = c->q, p = c->mo_p, P = p + q;
+  const long long np = c->n_pad;
+  std::memset(pin_t, 0, (size_t)P * p * sizeof(double));   // [I; -B] (P x p, column-major)
+  for (int a = 0; a < p; ++a) {
+    pin_t[a + (size_t)a * P] = 1.0;
+    for (int i = 0; i < q; ++i) pin_t[(p + i) + (size_t)a * P] = -B[i * p + a];
+  }
+  HIPCHK(c, hipMemcpyAsync(c->dT2, pin_t, (size_t)P * p * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  CHK(apply_small(c, c->dFm, np, P, c->dT2, p, c->dR2m, np, (int)np, nullptr));
+  CHK(skinny(c, false, c->tr.B, np, c->NB, c->NB, true, c->dR2m, np, p, c->dZm, np));   // L^-1 (F - H B)
+  return skinny(c, true, c->tr.B, np, c->NB, c->NB, true, c->dZm, np, p, c->dWm, np);   // Gamma
+}
+
+// The posterior means of the p outputs of gpe_set_outputs (gpe_posterior_mean_multi): Gamma by
+// multi_gamma, k_post_mean_multi with one workgroup per PMM_PTS points and segment of rows.
 int posterior_mean_multi_impl(gpe_ctx* c, int64_t m, const double* Xs, const double* Hs, const double* B,
                               double* mean_out) {
   CHK(check_ready(c));
@@ -3195,23 +3213,13 @@ int posterior_mean_multi_impl(gpe_ctx* c, int64_t m, const double* Xs, const dou
   if (c->prof)   // phase 0: k_post_mean_multi's device time over the chunks, phase 1: the chunks
     for (int i = 0; i < 8; ++i) c->phase_ms[i] = 0.0;
   CHK(ensure_linv(c));
-  const int d = c->d, q = c->q, p = c->mo_p, P = p + q;
+  const int d = c->d, p = c->mo_p, P = p + c->q;
   const long long np = c->n_pad;
   static_assert(PM_PTS % PMM_PTS == 0, "a padded chunk is whole workgroups of k_post_mean_multi");
   const MeanKind kind{p, &c->dPmm, &c->pmm_cap, B, (size_t)P * p};
   return posterior_means<0>(
       c, kind, m, Xs, Hs, mean_out,
-      [&](double* pin_t) -> int {   // [I; -B] (P x p, column-major)
-        std::memset(pin_t, 0, (size_t)P * p * sizeof(double));
-        for (int a = 0; a < p; ++a) {
-          pin_t[a + (size_t)a * P] = 1.0;
-          for (int i = 0; i < q; ++i) pin_t[(p + i) + (size_t)a * P] = -B[i * p + a];
-        }
-        HIPCHK(c, hipMemcpyAsync(c->dT2, pin_t, (size_t)P * p * sizeof(double), hipMemcpyHostToDevice, c->stream));
-        CHK(apply_small(c, c->dFm, np, P, c->dT2, p, c->dR2m, np, (int)np, nullptr));
-        CHK(skinny(c, false, c->tr.B, np, c->NB, c->NB, true, c->dR2m, np, p, c->dZm, np));   // L^-1 (F - H B)
-        return skinny(c, true, c->tr.B, np, c->NB, c->NB, true, c->dZm, np, p, c->dWm, np);   // Gamma
-      },
+      [&](double* pin_t) -> int { return multi_gamma(c, B, pin_t); },
       [&](long long mp, int nseg, double* part, double* dY, double coff, int fam) -> int {
         PostMeanMultiArgs a;
         a.xw = c->dXw; a.xsw = c->dXsw; a.gam = c->dWm; a.part = part; a.coff = coff;
@@ -4348,12 +4356,18 @@ int gpe_bench_gemm(gpe_ctx* c, int32_t trans_a, int32_t trans_b, int32_t mt, int
 namespace {
 
 // One emulator: its device buffer (dev, one allocation) and the arrays inside it
+// (a member): p = 0 an emulator of gpe_hm_add, p >= 1 the p outputs of gpe_hm_add_multi, whose
+// beta holds B (q x p row-major) and whose sdiag Sigma's diagonal; first: its first output's
+// place among the set's outputs
 struct HmEmul {
-  int n = 0, d = 0, q = 0, fam = 0, pt = 0, maxact = 0;
+  int n = 0, d = 0, q = 0, fam = 0, pt = 0, maxact = 0, p = 0, first = 0;
   double s2 = 0.0, coff = 0.0, cdiag = 0.0;
   double* dev = nullptr;
-  double *xw = nullptr, *invdelta = nullptr, *W = nullptr, *beta = nullptr, *kinv = nullptr, *hval = nullptr;
+  double *xw = nullptr, *invdelta = nullptr, *W = nullptr, *beta = nullptr, *kinv = nullptr, *hval = nullptr,
+         *sdiag = nullptr;
   int *active = nullptr, *hdim = nullptr;
+  std::vector<double> Sigma;   // p x p (host: the joint measure's diagonalisation, once per call)
+  int outputs() const { return p ? p : 1; }
 };
 
 }  // namespace
@@ -4363,6 +4377,7 @@ struct gpe_hm {
   hipStream_t stream = nullptr;
   std::string err;
   std::vector<HmEmul> em;
+  int outputs = 0;           // the members' outputs together: at most HM_MAX_EMUL
   long long chunk = HM_CHUNK_DEFAULT;
   hipEvent_t ev_ctx = nullptr, ev_set = nullptr;   // gpe_hm_add: the context's stream <-> the set's
   hipEvent_t ev_pipe[2] = {nullptr, nullptr};      // the chunk pipeline's result slots
@@ -4393,39 +4408,80 @@ int hm_fail(gpe_hm* h, int code, const std::string& msg) {
 template <int FAM, int PT>
 bool hm_lds_attr_one() {
   return hipFuncSetAttribute((const void*)k_hm_post<FAM, PT>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                             HM_LDS_BYTES) == hipSuccess;
+                             HM_LDS_BYTES) == hipSuccess &&
+         hipFuncSetAttribute((const void*)k_hm_post<FAM, PT, HmPostMultiArgs>,
+                             hipFuncAttributeMaxDynamicSharedMemorySize, HM_LDS_BYTES) == hipSuccess;
 }
 template <int FAM>
 bool hm_lds_attr() {
   return hm_lds_attr_one<FAM, HM_PT_WIDE>() && hm_lds_attr_one<FAM, HM_PT_NARROW>();
 }
 
-// k_hm_post<FAM, PT> for one emulator and one chunk
-void hm_launch_post(const HmEmul& e, dim3 g, size_t lds, hipStream_t st, const HmPostArgs& a) {
+// k_hm_post<FAM, PT, Args> for one member and one chunk (Args: HmPostArgs, HmPostMultiArgs)
+template <class Args>
+void hm_launch_post(const HmEmul& e, dim3 g, size_t lds, hipStream_t st, const Args& a) {
   with_fam(e.fam, [&](auto F) {
     constexpr int FAM = decltype(F)::value;
-    if (e.pt == HM_PT_WIDE) hipLaunchKernelGGL((k_hm_post<FAM, HM_PT_WIDE>), g, dim3(HM_LANES), lds, st, a);
-    else hipLaunchKernelGGL((k_hm_post<FAM, HM_PT_NARROW>), g, dim3(HM_LANES), lds, st, a);
+    if (e.pt == HM_PT_WIDE) hipLaunchKernelGGL((k_hm_post<FAM, HM_PT_WIDE, Args>), g, dim3(HM_LANES), lds, st, a);
+    else hipLaunchKernelGGL((k_hm_post<FAM, HM_PT_NARROW, Args>), g, dim3(HM_LANES), lds, st, a);
   });
+}
+
+// What every k_hm_post instance reads of a member, for a chunk of mc candidates at dX
+void hm_post_args(const HmEmul& e, const double* dX, int D, long long mc, HmPostArgs& a) {
+  a.xw = e.xw; a.invdelta = e.invdelta; a.active = e.active; a.W = e.W; a.hdim = e.hdim; a.hval = e.hval;
+  a.beta = e.beta; a.kinv = e.kinv; a.Xs = dX;
+  a.s2 = e.s2; a.coff = e.coff; a.cdiag = e.cdiag;
+  a.n = e.n; a.d = e.d; a.q = e.q; a.D = D; a.mc = (int)mc;
+}
+void hm_multi_args(const HmEmul& e, HmPostMultiArgs& a) {
+  a.B = e.beta; a.sdiag = e.sdiag; a.Wj = nullptr; a.lam = nullptr; a.p = e.p;
+}
+
+// The set's chunk buffers: dev doubles on the device, pin pinned doubles, grown when too small
+int hm_workspace(gpe_hm* h, size_t dev, size_t pin) {
+  if (dev > h->work_cap) {
+    if (h->dwork) (void)hipFree(h->dwork);
+    h->dwork = nullptr, h->work_cap = 0;
+    HM_HIPCHK(h, hipMalloc((void**)&h->dwork, dev * sizeof(double)));
+    h->work_cap = dev;
+  }
+  if (pin > h->hpin_cap) {
+    if (h->hpin) (void)hipHostFree(h->hpin);
+    h->hpin = nullptr, h->hpin_cap = 0;
+    HM_HIPCHK(h, hipHostMalloc((void**)&h->hpin, pin * sizeof(double), hipHostMallocDefault));
+    h->hpin_cap = pin;
+  }
+  return GPE_OK;
 }
 
 // The snapshot of gpe_hm_add, behind the checks: [gamma, G], Kq^-1 and the kernel's constants
 // by Posterior::setup() on the context (scratch buffers only: what gpe_posterior itself
 // overwrites on every call), then the copies on the set's stream, ordered behind the context's
 // stream by ev_ctx; the context's stream waits for them (ev_set) before it goes on.
+// pm = 0: an emulator of gpe_hm_add (beta, sigma).  pm >= 1: the pm outputs of gpe_hm_add_multi:
+// beta is B (q x pm), Sigma pm x pm; G and Kq^-1 come from setup() at sigma = 1 (they do not
+// depend on its beta, taken as zero), Gamma from multi_gamma() into dWm.
 int hm_snapshot(gpe_hm* h, gpe_ctx* c, const int32_t* active, const int32_t* hdim, const double* hval,
-                const double* beta, double sigma, HmEmul& e) {
+                const double* beta, double sigma, int pm, const double* Sigma, HmEmul& e) {
   const int n = (int)c->n, d = c->d, q = c->q;
   const long long np = c->n_pad;
-  PostReq r{0, nullptr, nullptr, beta, sigma, 64, nullptr, PostVar::DIAG, nullptr};
+  const std::vector<double> zero((size_t)q, 0.0);
+  PostReq r{0, nullptr, nullptr, pm ? zero.data() : beta, sigma, 64, nullptr, PostVar::DIAG, nullptr};
   Posterior S(c, r);
   CHK(S.setup());
-  e.n = n; e.d = d; e.q = q; e.fam = S.fam; e.pt = hm_pt(n);
+  if (pm) {   // (setup() has waited for the stream: the pinned buffer is free)
+    CHK(ensure_pinned(c, (size_t)(pm + q) * pm + 64));
+    CHK(multi_gamma(c, beta, c->hpin));
+  }
+  e.n = n; e.d = d; e.q = q; e.fam = S.fam; e.pt = hm_pt(n); e.p = pm;
   e.s2 = S.s2; e.coff = S.coff; e.cdiag = S.cdiag;
   e.maxact = 0;
   for (int k = 0; k < d; ++k) e.maxact = std::max(e.maxact, (int)active[k]);
-  const size_t nW = (size_t)hm_packed_size(n, q), nint = ((size_t)d + q + 1) / 2 + 1;
-  const size_t sz[] = {(size_t)n * d, (size_t)d, nW, (size_t)q, (size_t)q * q, (size_t)q, nint};
+  const int rows = pm ? pm + q : 1 + q;
+  const size_t nW = (size_t)hm_packed_size_rows(n, rows), nint = ((size_t)d + q + 1) / 2 + 1;
+  const size_t nbeta = pm ? (size_t)q * pm : (size_t)q;
+  const size_t sz[] = {(size_t)n * d, (size_t)d, nW, nbeta, (size_t)q * q, (size_t)q, (size_t)pm, nint};
   size_t tot = 0;
   for (size_t s : sz) tot += s;
   HM_HIPCHK(h, hipMalloc((void**)&e.dev, tot * sizeof(double)));
@@ -4436,14 +4492,18 @@ int hm_snapshot(gpe_hm* h, gpe_ctx* c, const int32_t* active, const int32_t* hdi
   e.beta = p, p += sz[3];
   e.kinv = p, p += sz[4];
   e.hval = p, p += sz[5];
+  e.sdiag = p, p += sz[6];
   e.active = reinterpret_cast<int*>(p);
   e.hdim = e.active + d;
   // the small arrays lie together behind W: one blocking copy
-  std::vector<double> hs(sz[3] + sz[4] + sz[5] + sz[6], 0.0);
-  std::memcpy(hs.data(), beta, (size_t)q * sizeof(double));
-  std::memcpy(hs.data() + q, S.Kinv.data(), (size_t)q * q * sizeof(double));
-  std::memcpy(hs.data() + q + (size_t)q * q, hval, (size_t)q * sizeof(double));
-  int* hi = reinterpret_cast<int*>(hs.data() + 2 * (size_t)q + (size_t)q * q);
+  std::vector<double> hs(sz[3] + sz[4] + sz[5] + sz[6] + sz[7], 0.0);
+  double* hp = hs.data();
+  std::memcpy(hp, beta, nbeta * sizeof(double)), hp += nbeta;
+  std::memcpy(hp, S.Kinv.data(), (size_t)q * q * sizeof(double)), hp += (size_t)q * q;
+  std::memcpy(hp, hval, (size_t)q * sizeof(double)), hp += q;
+  for (int a = 0; a < pm; ++a) *hp++ = Sigma[(size_t)a * pm + a];
+  if (pm) e.Sigma.assign(Sigma, Sigma + (size_t)pm * pm);
+  int* hi = reinterpret_cast<int*>(hp);
   for (int k = 0; k < d; ++k) hi[k] = active[k];
   for (int j = 0; j < q; ++j) hi[d + j] = hdim[j];
   HM_HIPCHK(h, hipMemcpy(e.beta, hs.data(), hs.size() * sizeof(double), hipMemcpyHostToDevice));
@@ -4453,13 +4513,39 @@ int hm_snapshot(gpe_hm* h, gpe_ctx* c, const int32_t* active, const int32_t* hdi
   HM_HIPCHK(h, hipEventRecord(h->ev_ctx, c->stream));
   HM_HIPCHK(h, hipStreamWaitEvent(h->stream, h->ev_ctx, 0));
   HM_HIPCHK(h, hipMemcpyAsync(e.xw, c->dXw, (size_t)n * d * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-  hipLaunchKernelGGL(k_hm_pack, dim3((unsigned)hm_nblocks(n, q)), dim3(256), 0, h->stream, c->tr.B, c->dWa, np, n, q,
-                     e.W);
+  // [gamma, G] is dWa; [Gamma, G] is dWm's first pm columns and dWa's columns 1 .. q
+  hipLaunchKernelGGL(k_hm_pack, dim3((unsigned)hm_nblocks_rows(n, rows)), dim3(256), 0, h->stream, c->tr.B,
+                     pm ? c->dWm : c->dWa, c->dWa + np, np, n, pm ? pm : 1, q, e.W);
   HM_HIPCHK(h, hipGetLastError());
   HM_HIPCHK(h, hipEventRecord(h->ev_set, h->stream));
   HM_HIPCHK(h, hipStreamWaitEvent(c->stream, h->ev_set, 0));
   HM_HIPCHK(h, hipStreamSynchronize(h->stream));
   return GPE_OK;
+}
+
+// gpe_hm_add and gpe_hm_add_multi behind their own checks: active and hdim, the triangular
+// inverse, the snapshot; the member joins the set only when all of it succeeded.
+int hm_add_member(gpe_hm* h, gpe_ctx* c, int d, const int32_t* active, int q, const int32_t* hdim,
+                  const double* hval, const double* beta, double sigma, int pm, const double* Sigma) {
+  for (int k = 0; k < d; ++k)
+    if (active[k] < 0) return hm_fail(h, GPE_ERR_ARG, "active[" + std::to_string(k) + "] is negative");
+  for (int j = 0; j < q; ++j)
+    if (hdim[j] < -1 || hdim[j] >= d) return hm_fail(h, GPE_ERR_ARG, "hdim[" + std::to_string(j) + "] is outside [-1, d)");
+  HM_HIPCHK(h, hipSetDevice(h->device));
+  HmEmul e;
+  int rc = ensure_linv(c);
+  if (rc == GPE_OK) rc = hm_snapshot(h, c, active, hdim, hval, beta, sigma, pm, Sigma, e);
+  if (rc != GPE_OK) {
+    // (the copies may be queued: they end before the buffer goes)
+    (void)hipStreamSynchronize(h->stream);
+    if (e.dev) (void)hipFree(e.dev);
+    if (h->err.empty()) h->err = c->err;
+    return rc;
+  }
+  e.first = h->outputs;
+  h->outputs += e.outputs();
+  h->em.push_back(e);
+  return (int)h->em.size() - 1;
 }
 
 }  // namespace
@@ -4523,31 +4609,39 @@ int gpe_hm_add(gpe_hm* h, gpe_ctx* c, int32_t d, const int32_t* active, int32_t 
   if (c->device != h->device) return hm_fail(h, GPE_ERR_ARG, "the context is on another device than the set");
   if (c->n <= 0 || !c->factor_valid) return hm_fail(h, GPE_ERR_STATE, "no resident factor (call gpe_factor)");
   if (d != c->d || q != c->q) return hm_fail(h, GPE_ERR_ARG, "d and q must be those of the context's data");
-  if (c->n > HM_MAX_N || d > HM_MAX_D || q > HM_MAX_Q || (int)h->em.size() >= HM_MAX_EMUL)
+  if (c->n > HM_MAX_N || d > HM_MAX_D || q > HM_MAX_Q || h->outputs >= HM_MAX_EMUL)
     return hm_fail(h, GPE_ERR_UNSUPPORTED, "an emulator of a set has n <= 512, d <= 32, q <= 16; a set at most 32");
-  for (int k = 0; k < d; ++k)
-    if (active[k] < 0) return hm_fail(h, GPE_ERR_ARG, "active[" + std::to_string(k) + "] is negative");
-  for (int j = 0; j < q; ++j)
-    if (hdim[j] < -1 || hdim[j] >= d) return hm_fail(h, GPE_ERR_ARG, "hdim[" + std::to_string(j) + "] is outside [-1, d)");
-  HM_HIPCHK(h, hipSetDevice(h->device));
-  HmEmul e;
-  int rc = ensure_linv(c);
-  if (rc == GPE_OK) rc = hm_snapshot(h, c, active, hdim, hval, beta, sigma, e);
-  if (rc != GPE_OK) {
-    // (the copies may be queued: they end before the buffer goes)
-    (void)hipStreamSynchronize(h->stream);
-    if (e.dev) (void)hipFree(e.dev);
-    if (h->err.empty()) h->err = c->err;
-    return rc;
-  }
-  h->em.push_back(e);
-  return (int)h->em.size() - 1;
+  return hm_add_member(h, c, d, active, q, hdim, hval, beta, sigma, 0, nullptr);
+}
+
+int gpe_hm_add_multi(gpe_hm* h, gpe_ctx* c, int32_t d, const int32_t* active, int32_t q, const int32_t* hdim,
+                     const double* hval, int32_t p, const double* B, const double* Sigma) {
+  if (!h) return GPE_ERR_ARG;
+  h->err.clear();
+  if (!c || !active || !hdim || !hval || !B || !Sigma)
+    return hm_fail(h, GPE_ERR_ARG, "bad hm_add_multi args (a NULL pointer)");
+  if (c->device != h->device) return hm_fail(h, GPE_ERR_ARG, "the context is on another device than the set");
+  if (c->n <= 0 || !c->factor_valid) return hm_fail(h, GPE_ERR_STATE, "no resident factor (call gpe_factor)");
+  if (!c->mo_p) return hm_fail(h, GPE_ERR_STATE, "gpe_set_outputs has not been called for this data");
+  if (d != c->d || q != c->q) return hm_fail(h, GPE_ERR_ARG, "d and q must be those of the context's data");
+  if (p != c->mo_p) return hm_fail(h, GPE_ERR_ARG, "p must be the number of outputs of gpe_set_outputs");
+  if (c->n > HM_MAX_N || d > HM_MAX_D || q > HM_MAX_Q || p + q > HM_MAX_ROWS || h->outputs + p > HM_MAX_EMUL)
+    return hm_fail(h, GPE_ERR_UNSUPPORTED,
+                   "a multi-output member of a set has n <= 512, d <= 32, q <= 16, p + q <= 32; a set at most 32 outputs");
+  return hm_add_member(h, c, d, active, q, hdim, hval, B, 1.0, p, Sigma);
+}
+
+int gpe_hm_outputs(const gpe_hm* h) { return h ? h->outputs : GPE_ERR_ARG; }
+
+int gpe_hm_member_outputs(const gpe_hm* h, int32_t member) {
+  if (!h || member < 0 || member >= (int)h->em.size()) return GPE_ERR_ARG;
+  return h->em[member].outputs();
 }
 
 int gpe_hm_implausibility(gpe_hm* h, int64_t m, int32_t D, const double* Xs, const double* z, const double* var_extra,
                           int32_t maxno, double* imax_out, double* mean_out, double* var_out) {
   if (!h) return GPE_ERR_ARG;
-  const int p = (int)h->em.size();
+  const int p = h->outputs;   // (the members' outputs: the emulators of a set of gpe_hm_add members)
   if (p == 0) return hm_fail(h, GPE_ERR_STATE, "the set is empty (call gpe_hm_add)");
   if (m <= 0 || !Xs || !z || !var_extra || !imax_out)
     return hm_fail(h, GPE_ERR_ARG, "bad hm_implausibility args (m >= 1; Xs, z, var_extra and imax_out not NULL)");
@@ -4560,19 +4654,7 @@ int gpe_hm_implausibility(gpe_hm* h, int64_t m, int32_t D, const double* Xs, con
   const bool parts = mean_out != nullptr;
   const long long CH = h->chunk, cl = std::min<long long>(CH, m);
   const HmWork w = hm_work(cl, D, p, maxno, parts);
-  if ((size_t)w.dev() > h->work_cap) {
-    if (h->dwork) (void)hipFree(h->dwork);
-    h->dwork = nullptr, h->work_cap = 0;
-    HM_HIPCHK(h, hipMalloc((void**)&h->dwork, (size_t)w.dev() * sizeof(double)));
-    h->work_cap = (size_t)w.dev();
-  }
-  const size_t pin = 2 * (size_t)(w.pin_in() + w.pin_out());
-  if (pin > h->hpin_cap) {
-    if (h->hpin) (void)hipHostFree(h->hpin);
-    h->hpin = nullptr, h->hpin_cap = 0;
-    HM_HIPCHK(h, hipHostMalloc((void**)&h->hpin, pin * sizeof(double), hipHostMallocDefault));
-    h->hpin_cap = pin;
-  }
+  if (int rc = hm_workspace(h, (size_t)w.dev(), 2 * (size_t)(w.pin_in() + w.pin_out()))) return rc;
   double* dX = h->dwork;
   double* dI2 = dX + w.pts;
   double* dparts = dI2 + w.i2;       // mean (p x cl), then var (p x cl)
@@ -4583,17 +4665,28 @@ int gpe_hm_implausibility(gpe_hm* h, int64_t m, int32_t D, const double* Xs, con
     const long long mc = std::min(CH, m - s0);
     std::memcpy(pin_in[slot], Xs + s0 * D, (size_t)mc * D * sizeof(double));
     HM_HIPCHK(h, hipMemcpyAsync(dX, pin_in[slot], (size_t)mc * D * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    for (int o = 0; o < p; ++o) {
-      const HmEmul& e = h->em[o];
-      HmPostArgs a;
-      a.xw = e.xw; a.invdelta = e.invdelta; a.active = e.active; a.W = e.W; a.hdim = e.hdim; a.hval = e.hval;
-      a.beta = e.beta; a.kinv = e.kinv; a.Xs = dX; a.i2 = dI2 + o * cl;
-      a.mean = parts ? dparts + o * cl : nullptr;
-      a.var = parts ? dparts + (p + o) * cl : nullptr;
-      a.z = z[o]; a.ve = var_extra[o]; a.s2 = e.s2; a.coff = e.coff; a.cdiag = e.cdiag;
-      a.n = e.n; a.d = e.d; a.q = e.q; a.D = D; a.mc = (int)mc;
-      hm_launch_post(e, dim3((unsigned)hm_tiles(mc, e.pt)), (size_t)hm_lds_doubles(e.n, e.pt) * sizeof(double),
-                     h->stream, a);
+    for (const HmEmul& e : h->em) {
+      const int o = e.first;
+      const dim3 grid((unsigned)hm_tiles(mc, e.pt));
+      const size_t lds = (size_t)hm_lds_doubles(e.n, e.pt) * sizeof(double);
+      if (e.p) {
+        HmPostMultiArgs a = {};
+        hm_post_args(e, dX, D, mc, a);
+        hm_multi_args(e, a);
+        a.i2 = dI2 + o * cl; a.ldo = cl; a.joint = 0;
+        a.mean = parts ? dparts + o * cl : nullptr;
+        a.var = parts ? dparts + (p + o) * cl : nullptr;
+        for (int j = 0; j < e.p; ++j) a.zs[j] = z[o + j], a.ves[j] = var_extra[o + j];
+        hm_launch_post(e, grid, lds, h->stream, a);
+      } else {
+        HmPostArgs a;
+        hm_post_args(e, dX, D, mc, a);
+        a.i2 = dI2 + o * cl;
+        a.mean = parts ? dparts + o * cl : nullptr;
+        a.var = parts ? dparts + (p + o) * cl : nullptr;
+        a.z = z[o]; a.ve = var_extra[o];
+        hm_launch_post(e, grid, lds, h->stream, a);
+      }
       HM_HIPCHK(h, hipGetLastError());
     }
     hipLaunchKernelGGL(k_hm_select, dim3((unsigned)((mc + 255) / 256)), dim3(256), 0, h->stream, dI2, cl, p, (int)maxno,
@@ -4617,6 +4710,75 @@ int gpe_hm_implausibility(gpe_hm* h, int64_t m, int32_t D, const double* Xs, con
       std::memcpy(mean_out + (long long)o * m + s0, src + o * cl, (size_t)mc * sizeof(double));
       std::memcpy(var_out + (long long)o * m + s0, src + (p + o) * cl, (size_t)mc * sizeof(double));
     }
+  };
+  return chunk_pipeline(
+      m, CH, dev,
+      [&](int slot) -> int {
+        HM_HIPCHK(h, hipEventSynchronize(h->ev_pipe[slot]));
+        return GPE_OK;
+      },
+      host, [&] { (void)hipStreamSynchronize(h->stream); });
+}
+
+int gpe_hm_implausibility_mv(gpe_hm* h, int32_t member, int64_t m, int32_t D, const double* Xs, const double* z,
+                             const double* V, double* i2_out, double* mean_out, double* c_out) {
+  if (!h) return GPE_ERR_ARG;
+  h->err.clear();
+  if (member < 0 || member >= (int)h->em.size() || h->em[member].p == 0)
+    return hm_fail(h, GPE_ERR_ARG, "member must be a multi-output member of the set (gpe_hm_add_multi)");
+  if (m <= 0 || !Xs || !z || !V || !i2_out)
+    return hm_fail(h, GPE_ERR_ARG, "bad hm_implausibility_mv args (m >= 1; Xs, z, V and i2_out not NULL)");
+  const HmEmul& e = h->em[member];
+  if (D <= e.maxact) return hm_fail(h, GPE_ERR_ARG, "D is smaller than the member's largest active index + 1");
+  if ((mean_out == nullptr) != (c_out == nullptr))
+    return hm_fail(h, GPE_ERR_ARG, "mean_out and c_out go together (both or neither)");
+  const int p = e.p;
+  // W^T V W = I, W^T Sigma W = Lambda: [W (p x p), lambda (p)] behind the chunk's buffers
+  std::vector<double> wl((size_t)p * p + p);
+  if (hm_mv_prepare(p, e.Sigma.data(), V, wl.data(), wl.data() + (size_t)p * p))
+    return hm_fail(h, GPE_NOT_PD, "V is not positive definite");
+  HM_HIPCHK(h, hipSetDevice(h->device));
+  const bool parts = mean_out != nullptr;
+  const long long CH = h->chunk, cl = std::min<long long>(CH, m);
+  const HmWork w = hm_work_mv(cl, D, p, parts);
+  if (int rc = hm_workspace(h, (size_t)w.dev() + wl.size(), 2 * (size_t)(w.pin_in() + w.pin_out()))) return rc;
+  double* dX = h->dwork;
+  double* dparts = dX + w.pts;       // mean (p x cl), then c (cl)
+  double* dI2 = dparts + w.parts;
+  double* dW = dI2 + w.sel;
+  // (every earlier call has ended: a blocking copy, once per call)
+  HM_HIPCHK(h, hipMemcpy(dW, wl.data(), wl.size() * sizeof(double), hipMemcpyHostToDevice));
+  double* pin_in[2] = {h->hpin, h->hpin + w.pin_in()};
+  double* pin_out[2] = {pin_in[1] + w.pin_in(), pin_in[1] + w.pin_in() + w.pin_out()};
+  auto dev = [&](long long s0, int slot) -> int {
+    const long long mc = std::min(CH, m - s0);
+    std::memcpy(pin_in[slot], Xs + s0 * D, (size_t)mc * D * sizeof(double));
+    HM_HIPCHK(h, hipMemcpyAsync(dX, pin_in[slot], (size_t)mc * D * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HmPostMultiArgs a = {};
+    hm_post_args(e, dX, D, mc, a);
+    hm_multi_args(e, a);
+    a.Wj = dW; a.lam = dW + (size_t)p * p; a.joint = 1;
+    a.i2 = dI2; a.ldo = cl;
+    a.mean = parts ? dparts : nullptr;
+    a.var = parts ? dparts + (long long)p * cl : nullptr;
+    for (int j = 0; j < p; ++j) a.zs[j] = z[j];
+    hm_launch_post(e, dim3((unsigned)hm_tiles(mc, e.pt)), (size_t)hm_lds_doubles(e.n, e.pt) * sizeof(double), h->stream,
+                   a);
+    HM_HIPCHK(h, hipGetLastError());
+    HM_HIPCHK(h, hipMemcpyAsync(pin_out[slot], dI2, (size_t)mc * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (parts)
+      HM_HIPCHK(h, hipMemcpyAsync(pin_out[slot] + w.sel, dparts, (size_t)w.parts * sizeof(double), hipMemcpyDeviceToHost,
+                                  h->stream));
+    HM_HIPCHK(h, hipEventRecord(h->ev_pipe[slot], h->stream));
+    return GPE_OK;
+  };
+  auto host = [&](long long s0, int slot) {
+    const long long mc = std::min(CH, m - s0);
+    std::memcpy(i2_out + s0, pin_out[slot], (size_t)mc * sizeof(double));
+    if (!parts) return;
+    const double* src = pin_out[slot] + w.sel;
+    for (int o = 0; o < p; ++o) std::memcpy(mean_out + (long long)o * m + s0, src + o * cl, (size_t)mc * sizeof(double));
+    std::memcpy(c_out + s0, src + (long long)p * cl, (size_t)mc * sizeof(double));
   };
   return chunk_pipeline(
       m, CH, dev,

@@ -16,6 +16,8 @@
 // atomics.  Layouts and sizes: gpemu_hm_plan.hpp.
 #pragma once
 
+#include <type_traits>
+
 #include "gpemu_hm_plan.hpp"
 #include "gpemu_postmean.hpp"
 
@@ -24,11 +26,13 @@ namespace gpe {
 typedef double hm_d4 __attribute__((ext_vector_type(4)));
 
 // One workgroup per block of the packed matrix.  Linv: the context's L^-1 (column-major, ld;
-// only entries on and below the diagonal are read), Wa: [gamma, G] = A^-1 [f - H beta, H]
-// (column-major, ld).  Rows from n on, columns from n on and everything above the diagonal are
-// written as zeros.
-static __global__ void __launch_bounds__(256) k_hm_pack(const double* Linv, const double* Wa, long long ld, int n,
-                                                       int q, double* W) {
+// only entries on and below the diagonal are read).  The blocks behind L^-1's hold p + q rows:
+// rows [0, p) the columns of Gam, rows [p, p + q) those of G (both column-major, ld).  A single
+// emulator has p = 1, Gam = gamma and G behind it in [gamma, G] = A^-1 [f - H beta, H]; a
+// multi-output member Gam = Gamma = A^-1 (F - H B).  Rows from n on, columns from n on, rows
+// from p + q on and everything above the diagonal are written as zeros.
+static __global__ void __launch_bounds__(256) k_hm_pack(const double* Linv, const double* Gam, const double* G,
+                                                       long long ld, int n, int p, int q, double* W) {
   const int nrb = hm_nrb(n), b = (int)blockIdx.x;
   const int cnt = hm_block_steps(nrb, b) * HM_STEP;
   double* dst = W + hm_block_first(nrb, b) * HM_STEP;
@@ -40,7 +44,10 @@ static __global__ void __launch_bounds__(256) k_hm_pack(const double* Linv, cons
       if (i < n && k <= i) v = Linv[i + (long long)k * ld];
     } else {
       const int j = (b - nrb) * HM_RB + r;
-      if (j <= q && k < n) v = Wa[k + (long long)j * ld];
+      if (k < n) {
+        if (j < p) v = Gam[k + (long long)j * ld];
+        else if (j < p + q) v = G[k + (long long)(j - p) * ld];
+      }
     }
     dst[e] = v;
   }
@@ -93,6 +100,73 @@ __device__ inline void hm_point(const HmPostArgs& a, double* yb, const double* s
   if (a.var) a.var[s] = var;
 }
 
+// A member of p outputs (gpe_hm_add_multi): the packed matrix holds [Gamma, G] behind L^-1, so yb
+// has rows [0, p) Gamma^T K* and rows [p, p + q) G^T K*.  beta, z, ve, s2 of HmPostArgs are not
+// read.  Univariate mode (gpe_hm_implausibility): output a goes to row a of i2, mean and var
+// (leading dimension ldo).  Joint mode (gpe_hm_implausibility_mv): i2 one value per point, mean
+// p rows, var one row (c).
+struct HmPostMultiArgs : HmPostArgs {
+  const double* B;       // q x p row-major
+  const double* sdiag;   // p: Sigma_aa
+  const double* Wj;      // joint: p x p row-major, W^T V W = I, W^T Sigma W = Lambda (gpemu_hm_mv.hpp)
+  const double* lam;     // joint: p
+  long long ldo;
+  int p, joint;
+  double zs[HM_MAX_ROWS], ves[HM_MAX_ROWS];   // p: the observations; univariate: var_extra
+};
+
+// The tail of a multi-output member for one point: c is hm_point's variance at sigma = 1 in its
+// order of operations; the means and the residuals live in rows [0, p) of yb, in this thread's
+// column, so nothing of length p is held in registers.
+//   t_i = h_i - yb[p + i] (in place), tq = |t Kq^-T|^2, c = cdiag - nrm + tq
+//   mu_a = yb[a] + sum_i h_i B[i, a], i = 0 .. q - 1 in order
+//   univariate: I^2_a = (mu_a - z_a)^2 / (Sigma_aa c + ve_a)
+//   joint: r_a = mu_a - z_a, y_j = sum_a W[a, j] r_a (a in order), I^2 = sum_j y_j^2 / (c lam_j + 1)
+// No contraction, as hm_point: NumPy restates every line on the returned parts.
+__device__ inline void hm_point_multi(const HmPostMultiArgs& a, double* yb, const double* ssb, int PT, int pt,
+                                      long long s) {
+#pragma clang fp contract(off)
+  const int q = a.q, p = a.p;
+  double nrm = ssb[pt];
+  for (int j = 1; j < 16; ++j) nrm += ssb[j * PT + pt];
+  const double* xrow = a.Xs + s * a.D;
+  for (int i = 0; i < q; ++i) {
+    const double h = a.hdim[i] < 0 ? a.hval[i] : xrow[a.active[a.hdim[i]]];
+    yb[(p + i) * PT + pt] = h - yb[(p + i) * PT + pt];
+    for (int o = 0; o < p; ++o) yb[o * PT + pt] += h * a.B[i * p + o];
+  }
+  double tq = 0.0;
+  for (int o = 0; o < q; ++o) {
+    double acc = 0.0;
+    for (int i = 0; i < q; ++i) acc += yb[(p + i) * PT + pt] * a.kinv[o * q + i];
+    tq += acc * acc;
+  }
+  const double c = a.cdiag - nrm + tq;
+  if (!a.joint) {
+    for (int o = 0; o < p; ++o) {
+      const double mu = yb[o * PT + pt], var = a.sdiag[o] * c;
+      const double dz = mu - a.zs[o];
+      a.i2[o * a.ldo + s] = dz * dz / (var + a.ves[o]);
+      if (a.mean) a.mean[o * a.ldo + s] = mu;
+      if (a.var) a.var[o * a.ldo + s] = var;
+    }
+    return;
+  }
+  for (int o = 0; o < p; ++o) {
+    const double mu = yb[o * PT + pt];
+    if (a.mean) a.mean[o * a.ldo + s] = mu;
+    yb[o * PT + pt] = mu - a.zs[o];
+  }
+  double i2 = 0.0;
+  for (int j = 0; j < p; ++j) {
+    double y = 0.0;
+    for (int o = 0; o < p; ++o) y += a.Wj[o * p + j] * yb[o * PT + pt];
+    i2 += y * y / (c * a.lam[j] + 1.0);
+  }
+  a.i2[s] = i2;
+  if (a.var) a.var[s] = c;
+}
+
 // PT points per workgroup of HM_WAVES waves.  LDS: kst, the tile's K* (n16 x PT, rows from n on
 // zero); behind it 48 PT doubles: first the tile's scaled points (PT x (d | 1): the odd pitch
 // keeps the points of a wave in different banks), then yb (32 x PT: [gamma, G]^T K*) and ssb
@@ -107,9 +181,12 @@ __device__ inline void hm_point(const HmPostArgs& a, double* yb, const double* s
 // [gamma, G] is stored to yb.  The tail, one thread per point, adds the 16 sums of a point in
 // the order wave 0 .. 3, lane group 0 .. 3.
 // Points from mc on enter with zero coordinates, are computed and never stored.
-template <int FAM, int PT>
-static __global__ void __launch_bounds__(HM_LANES) k_hm_post(HmPostArgs a) {
+// Args = HmPostMultiArgs: the instances of a multi-output member, which differ in the number of
+// blocks behind L^-1's (p + q rows in place of 1 + q) and in the tail alone.
+template <int FAM, int PT, class Args = HmPostArgs>
+static __global__ void __launch_bounds__(HM_LANES) k_hm_post(Args a) {
   constexpr int NG = PT / 16;
+  constexpr bool MULTI = std::is_same<Args, HmPostMultiArgs>::value;
   extern __shared__ __attribute__((aligned(16))) double hm_lds[];
   const int n = a.n, d = a.d, q = a.q, n16 = hm_n16(n), nrb = hm_nrb(n);
   double* kst = hm_lds;
@@ -144,7 +221,9 @@ static __global__ void __launch_bounds__(HM_LANES) k_hm_post(HmPostArgs a) {
   double ss[NG];
 #pragma unroll
   for (int g = 0; g < NG; ++g) ss[g] = 0.0;
-  const int nb = nrb + hm_nxb(q);
+  int nb;
+  if constexpr (MULTI) nb = nrb + hm_nxb_rows(a.p + q);
+  else nb = nrb + hm_nxb(q);
   for (int i = 0; i < nb; ++i) {
     // the blocks from the longest down, dealt to the waves back and forth (0 1 2 3 3 2 1 0 ...)
     const int pos = i & (2 * HM_WAVES - 1);
@@ -188,7 +267,10 @@ static __global__ void __launch_bounds__(HM_LANES) k_hm_post(HmPostArgs a) {
 #pragma unroll
   for (int g = 0; g < NG; ++g) ssb[(wave * 4 + lr) * PT + 16 * g + lc] = ss[g];
   __syncthreads();
-  if (tid < PT && s0 + tid < a.mc) hm_point(a, yb, ssb, PT, tid, s0 + tid);
+  if (tid < PT && s0 + tid < a.mc) {
+    if constexpr (MULTI) hm_point_multi(a, yb, ssb, PT, tid, s0 + tid);
+    else hm_point(a, yb, ssb, PT, tid, s0 + tid);
+  }
 }
 
 // a < b with a NaN above every number (np.sort's order)

@@ -29,6 +29,11 @@ GPE_HM_HD inline int hm_nrb(int n) { return (n + HM_RB - 1) / HM_RB; }
 // the blocks of 16 rows [gamma^T; G^T] takes (1 + q rows: two blocks at q = 16)
 GPE_HM_HD inline int hm_nxb(int q) { return (1 + q + HM_RB - 1) / HM_RB; }
 GPE_HM_HD inline int hm_nblocks(int n, int q) { return hm_nrb(n) + hm_nxb(q); }
+// the same for `rows` rows behind L^-1's: 1 + q of a single emulator ([gamma, G]), p + q of a
+// multi-output one ([Gamma, G]); at most HM_MAX_ROWS, the rows of yb
+constexpr int HM_MAX_ROWS = 32;
+GPE_HM_HD inline int hm_nxb_rows(int rows) { return (rows + HM_RB - 1) / HM_RB; }
+GPE_HM_HD inline int hm_nblocks_rows(int n, int rows) { return hm_nrb(n) + hm_nxb_rows(rows); }
 
 // The packed matrix, block by block.  Block b < nrb holds rows [16 b, 16 b + 16) of L^-1 over
 // the columns [0, 16 (b + 1)): the lower blocks only, 4 (b + 1) steps.  Block nrb + x holds
@@ -48,6 +53,10 @@ GPE_HM_HD inline long long hm_packed_index(int nrb, int b, int r, int k) {
 GPE_HM_HD inline long long hm_packed_size(int n, int q) {
   const int nrb = hm_nrb(n);
   return hm_block_first(nrb, nrb + hm_nxb(q)) * HM_STEP;
+}
+GPE_HM_HD inline long long hm_packed_size_rows(int n, int rows) {
+  const int nrb = hm_nrb(n);
+  return hm_block_first(nrb, nrb + hm_nxb_rows(rows)) * HM_STEP;
 }
 
 // Points per workgroup.  The tile's K* (16 nrb rows x PT) stays in LDS with 48 PT doubles of
@@ -89,6 +98,11 @@ struct HmWork {
 };
 inline HmWork hm_work(long long cl, int D, int p, int maxno, bool parts) {
   return HmWork{cl * D, cl * p, parts ? 2 * cl * p : 0, cl * maxno};
+}
+// The joint measure of one member of p outputs (gpe_hm_implausibility_mv): I^2 per point takes
+// the selection's place (one column, copied out as it is); the parts are p means and c per point.
+inline HmWork hm_work_mv(long long cl, int D, int p, bool parts) {
+  return HmWork{cl * D, 0, parts ? (p + 1) * cl : 0, cl};
 }
 
 }  // namespace gpe

@@ -26,9 +26,10 @@ import numpy as _np
 
 from . import design_inputs as _gd
 from . import model as _model
+from . import multioutput as _mo
 
 __all__ = ["imp_plot", "imp_plot_recon", "nonimp_data", "new_wave_design", "EmulatorSet", "implausibility",
-           "nonimp_sample"]
+           "implausibility_mv", "nonimp_sample"]
 
 
 # ----------------------------------------------------------------- helpers (_hmutilfunctions.py)
@@ -312,17 +313,53 @@ class EmulatorSet:
     emulator falls outside that path -- the library refuses it (n > 512, more than 32 inputs,
     16 basis columns or 32 emulators), a basis expression is neither the constant nor ``x``,
     or ``model.Posterior`` would add a host-side term to its variance -- and the whole set then
-    computes through the ``_posterior_diag`` loop, with that loop's results."""
+    computes through the ``_posterior_diag`` loop, with that loop's results.
+
+    An item may be a trained ``multioutput.MultiEmulator``: one member of the set with one copy
+    of L^-1 for its p outputs (gpe_hm_add_multi), which take p consecutive places in ``zs`` and
+    ``var_extra``; output a has variance Sigma[a, a] c(x).  The limits then count outputs (32 per
+    set, p + q <= 32 per item), and the route outside the fused path is
+    ``multioutput.posterior``.  Where its beliefs carry no ``active_index`` / ``input_minmax``
+    (``multioutput.train`` writes no beliefs file) the active inputs are ``beliefs.active``
+    (``[]``: all) and the ranges ``all_data.input_minmax``.  ``implausibility_mv`` is the joint
+    measure of such an item."""
 
     def __init__(self, emuls):
         self.emuls = list(emuls)
-        _, minmax, _ = emulsetup(self.emuls)
+        self._multi = [isinstance(E, _mo.MultiEmulator) for E in self.emuls]
+        for E, multi in zip(self.emuls, self._multi):
+            if multi and E.Sigma is None:
+                raise RuntimeError("train() the MultiEmulator first")
+        views = [self._multi_view(E) if multi else E for E, multi in zip(self.emuls, self._multi)]
+        _, minmax, _ = emulsetup(views)
         self.minmax = minmax
         self.act_ref = ref_act(minmax)
         self.D = len(minmax)
-        self._cols = [[self.act_ref[str(l)] for l in E.beliefs.active_index] for E in self.emuls]
+        self._cols = [[self.act_ref[str(l)] for l in E.beliefs.active_index] for E in views]
+        # the items' places among the outputs: item i owns [_first[i], _first[i] + its outputs)
+        counts = [E.p if multi else 1 for E, multi in zip(self.emuls, self._multi)]
+        self._first = [int(v) for v in _np.concatenate([[0], _np.cumsum(counts)[:-1]])] if counts else []
+        self.outputs = int(sum(counts))
         self._set = None
         self.fused = self._make_fused()
+
+    @staticmethod
+    def _multi_view(M):
+        """What emulsetup reads of an item, for a MultiEmulator: its beliefs' ``active_index`` and
+        ``input_minmax`` where a beliefs file gave them, else ``beliefs.active`` (all inputs
+        when empty) and the ranges its inputs were scaled by."""
+        from types import SimpleNamespace
+        d = M.training.inputs.shape[1]
+        ai = getattr(M.beliefs, "active_index", None)
+        if not isinstance(ai, list) or len(ai) != d:
+            ai = list(M.beliefs.active) if M.beliefs.active != [] else list(range(d))
+        mm = M.beliefs.input_minmax
+        if mm is None or len(mm) != d:
+            mm = M.all_data.input_minmax
+        if mm is None or len(mm) != d:
+            mm = M.all_data.minmax
+        mm = [[float(a), float(b)] for a, b in mm]
+        return SimpleNamespace(beliefs=SimpleNamespace(active_index=[int(i) for i in ai], input_minmax=mm))
 
     @staticmethod
     def _basis_forms(E):
@@ -352,12 +389,18 @@ class EmulatorSet:
             return False
         nset = None
         try:
-            for E, cols, (hdim, hval) in zip(self.emuls, self._cols, forms):
-                ctx = _model.upload_training(E.training)
-                ctx.ensure_factor(E.K.kind, E.K.d, float(E.K.n), 1.0, E.training.r_scale())
+            for E, multi, cols, (hdim, hval) in zip(self.emuls, self._multi, self._cols, forms):
+                if multi:
+                    ctx = _mo._resident(E)
+                else:
+                    ctx = _model.upload_training(E.training)
+                    ctx.ensure_factor(E.K.kind, E.K.d, float(E.K.n), 1.0, E.training.r_scale())
                 if nset is None:
                     nset = _native.EmulatorSet(ctx.device)
-                nset.add(ctx, cols, hdim, hval, E.par.beta, float(E.par.sigma))
+                if multi:
+                    nset.add_multi(ctx, cols, hdim, hval, E.B, E.Sigma)
+                else:
+                    nset.add(ctx, cols, hdim, hval, E.par.beta, float(E.par.sigma))
         except RuntimeError as err:
             if nset is not None:
                 nset.close()
@@ -376,11 +419,52 @@ class EmulatorSet:
         maxno = int(maxno)
         if self.fused:
             return self._set.implausibility(x, zs, var_extra, maxno=maxno)
-        I2 = _np.zeros((x.shape[0], len(self.emuls)))
-        for o, (E, cols) in enumerate(zip(self.emuls, self._cols)):
-            mean, var = _posterior_diag(E, x[:, cols])
-            I2[:, o] = (mean - zs[o]) ** 2 / (var + var_extra[o])
+        I2 = _np.zeros((x.shape[0], self.outputs))
+        for E, multi, cols, o in zip(self.emuls, self._multi, self._cols, self._first):
+            if multi:
+                mean, c, Sigma = _mo.posterior(E, x[:, cols])
+                for a in range(E.p):
+                    I2[:, o + a] = (mean[:, a] - zs[o + a]) ** 2 / (Sigma[a, a] * c + var_extra[o + a])
+            else:
+                mean, var = _posterior_diag(E, x[:, cols])
+                I2[:, o] = (mean - zs[o]) ** 2 / (var + var_extra[o])
         return _imaxes(I2, maxno)
+
+    def implausibility_mv(self, item, z, V, x, parts=False):
+        """The joint (multivariate) implausibility of item ``item``, a MultiEmulator of p outputs,
+        at the m points of x (m x D, scaled):
+
+            I(x) = sqrt((z - mean(x))^T (c(x) Sigma + V)^-1 (z - mean(x)))
+
+        with Sigma the between-output covariance, c the emulator's variance at sigma = 1 and V
+        (p x p, or a length-p vector of variances: its diagonal) the observation error plus the
+        model discrepancy (Vernon, Goldstein & Bower 2010).  The usual cut-off compares I^2 with
+        a quantile of chi^2 with p degrees of freedom (0.995: 7.88 at p = 1, 10.6 at p = 2, 21.95
+        at p = 8) where the maximum of univariate measures is compared with 3.  ``parts``: also
+        the mean (m x p) and c (m)."""
+        item = int(item)
+        if not 0 <= item < len(self.emuls) or not self._multi[item]:
+            raise ValueError("implausibility_mv takes an item that is a MultiEmulator")
+        M, cols = self.emuls[item], self._cols[item]
+        x = _np.ascontiguousarray(x, dtype=float)
+        if x.ndim == 1:
+            x = x.reshape(-1, 1)
+        z = _np.asarray(z, dtype=float).ravel()
+        V = _np.asarray(V, dtype=float)
+        if V.ndim == 1:
+            V = _np.diag(V)
+        if z.size != M.p or V.shape != (M.p, M.p):
+            raise ValueError("z has one entry per output of the item, and V is p x p (or its diagonal)")
+        if self.fused:
+            I2, mean, c = self._set.implausibility_mv(item, x, z, V, parts=True)
+            mean = _np.ascontiguousarray(mean.T)
+        else:
+            mean, c, Sigma = _mo.posterior(M, x[:, cols])
+            r = mean - z
+            A = c[:, None, None] * Sigma[None, :, :] + V[None, :, :]
+            I2 = _np.einsum("sa,sa->s", r, _np.linalg.solve(A, r[:, :, None])[:, :, 0])
+        I = _np.sqrt(I2)
+        return (I, mean, c) if parts else I
 
     def close(self):
         if self._set is not None:
@@ -392,7 +476,20 @@ class EmulatorSet:
 def _as_set(emuls_or_set):
     if isinstance(emuls_or_set, EmulatorSet):
         return emuls_or_set, False
+    if isinstance(emuls_or_set, _mo.MultiEmulator):
+        return EmulatorSet([emuls_or_set]), True
     return EmulatorSet(emuls_or_set), True
+
+
+def implausibility_mv(M_or_set, z, V, x, item=0, parts=False):
+    """The joint implausibility of a ``MultiEmulator`` (or of item ``item`` of a list or an
+    ``EmulatorSet``) at every point of x: ``EmulatorSet.implausibility_mv``."""
+    S, mine = _as_set(M_or_set)
+    try:
+        return S.implausibility_mv(item, z, V, x, parts)
+    finally:
+        if mine:
+            S.close()
 
 
 def implausibility(emuls_or_set, zs, var_extra, x, maxno=1):

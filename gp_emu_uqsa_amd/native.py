@@ -111,6 +111,11 @@ SIGNATURES = {
                                _ct.POINTER(_ct.c_int32), _D, _D, _ct.c_double]),
     "gpe_hm_count": (_ct.c_int, [_VP]),
     "gpe_hm_implausibility": (_ct.c_int, [_VP, _ct.c_int64, _ct.c_int32, _D, _D, _D, _ct.c_int32, _D, _D, _D]),
+    "gpe_hm_add_multi": (_ct.c_int, [_VP, _VP, _ct.c_int32, _ct.POINTER(_ct.c_int32), _ct.c_int32,
+                                     _ct.POINTER(_ct.c_int32), _D, _ct.c_int32, _D, _D]),
+    "gpe_hm_outputs": (_ct.c_int, [_VP]),
+    "gpe_hm_member_outputs": (_ct.c_int, [_VP, _ct.c_int32]),
+    "gpe_hm_implausibility_mv": (_ct.c_int, [_VP, _ct.c_int32, _ct.c_int64, _ct.c_int32, _D, _D, _D, _D, _D, _D]),
     "gpe_solve": (_ct.c_int, [_VP, _ct.c_int32, _D, _D]),
     "gpe_sense_pairs": (_ct.c_int, [_VP, _ct.c_int32, _D, _D, _ct.c_int32, _D, _D, _D]),
     "gpe_gauss_transform": (_ct.c_int, [_VP, _ct.c_int64, _ct.c_int32, _ct.POINTER(_ct.c_int32), _D, _D, _D,
@@ -897,15 +902,66 @@ class EmulatorSet:
             self._check(rc, "gpe_hm_add")
         return rc
 
-    def implausibility(self, Xs, z, var_extra, maxno=1, parts=False):
-        """imax (m x maxno): per candidate the maxno largest implausibilities over the
-        emulators, ascending, NaN last.  parts=True: (imax, mean, var) with mean and var
-        p x m.  Xs is m x D in the scaled coordinates posterior() takes."""
+    def add_multi(self, ctx, active, hdim, hval, B, Sigma):
+        """Snapshot ctx's resident factor and outputs (set_outputs, p of them) as one member of
+        p outputs; returns the member's number.  B (q x p, beta_multi's) and Sigma (p x p);
+        active, hdim and hval as ``add``.  The member takes p consecutive places among the
+        set's outputs."""
+        i32 = _ct.POINTER(_ct.c_int32)
+        active = _np.ascontiguousarray(active, dtype=_np.int32).ravel()
+        hdim = _np.ascontiguousarray(hdim, dtype=_np.int32).ravel()
+        hval = _f64(hval).ravel()
+        B = _f64(B)
+        Sigma = _f64(Sigma)
+        if B.ndim != 2 or B.shape[0] != hdim.size or hval.size != hdim.size:
+            raise ValueError("hdim, hval and B have one entry (row) per basis column")
+        p = B.shape[1]
+        if Sigma.shape != (p, p):
+            raise ValueError("Sigma is p x p for the p columns of B")
+        rc = self.lib.gpe_hm_add_multi(self._h, ctx._h, active.size, active.ctypes.data_as(i32), hdim.size,
+                                       hdim.ctypes.data_as(i32), _ptr(hval), p, _ptr(B), _ptr(Sigma))
+        if rc < 0 or (rc == GPE_NOT_PD and self.lib.gpe_hm_last_error(self._h)):
+            self._check(rc, "gpe_hm_add_multi")
+        return rc
+
+    @property
+    def outputs(self):
+        """The members' outputs together: 1 per ``add`` member, p per ``add_multi`` member."""
+        return int(self.lib.gpe_hm_outputs(self._h))
+
+    def member_outputs(self, member):
+        return int(self.lib.gpe_hm_member_outputs(self._h, int(member)))
+
+    def implausibility_mv(self, member, Xs, z, V, parts=False):
+        """I^2 (m): the joint implausibility (z - mean)^T (c Sigma + V)^-1 (z - mean) of one
+        multi-output member, no square root.  z (p), V (p x p, symmetric positive definite).
+        parts=True: (I^2, mean p x m, c m)."""
         Xs = _f64(Xs)
         if Xs.ndim == 1:
             Xs = Xs.reshape(-1, 1)
         m, D = Xs.shape
-        p = len(self)
+        p = self.member_outputs(member)
+        z = _f64(z).ravel()
+        V = _f64(V)
+        if p > 0 and (z.size != p or V.shape != (p, p)):
+            raise ValueError("z has one entry per output of the member, and V is p x p")
+        i2 = _np.zeros(m)
+        mean = _np.zeros((max(p, 1), m)) if parts else None
+        c = _np.zeros(m) if parts else None
+        self._check(self.lib.gpe_hm_implausibility_mv(self._h, int(member), m, D, _ptr(Xs), _ptr(z), _ptr(V), _ptr(i2),
+                                                      _ptr(mean), _ptr(c)), "gpe_hm_implausibility_mv")
+        return (i2, mean, c) if parts else i2
+
+    def implausibility(self, Xs, z, var_extra, maxno=1, parts=False):
+        """imax (m x maxno): per candidate the maxno largest implausibilities over the
+        set's outputs (its emulators, and every output of a multi-output member), ascending,
+        NaN last.  parts=True: (imax, mean, var) with mean and var p x m, p = ``outputs``.
+        Xs is m x D in the scaled coordinates posterior() takes."""
+        Xs = _f64(Xs)
+        if Xs.ndim == 1:
+            Xs = Xs.reshape(-1, 1)
+        m, D = Xs.shape
+        p = self.outputs
         z = _f64(z).ravel()
         ve = _f64(var_extra).ravel()
         if z.size != p or ve.size != p:

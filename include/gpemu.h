@@ -37,7 +37,8 @@ extern "C" {
                                 9: gpe_dist_local_rows takes the basis width q;
                                 10: gpe_ozaki_stats (gpe_loo, gpe_posterior_pivchol,
                                 gpe_posterior_imse, gpe_posterior_grad, gpe_posterior_mean, gpe_posterior_groups,
-                                gpe_set_outputs, gpe_objective_multi, gpe_beta_multi, gpe_posterior_mean_multi, the gpe_hm_* set and the test
+                                gpe_set_outputs, gpe_objective_multi, gpe_beta_multi, gpe_posterior_mean_multi, the gpe_hm_* set (with gpe_hm_add_multi, gpe_hm_outputs,
+                                gpe_hm_member_outputs and gpe_hm_implausibility_mv) and the test
                                 hooks gpe_test_oz_product, gpe_test_oz_planes and gpe_test_gemm_group were
                                 added within 10: additions, nothing existing changed) */
 
@@ -355,6 +356,48 @@ int gpe_hm_count(const gpe_hm* set);
 int gpe_hm_implausibility(gpe_hm* set, int64_t m, int32_t D, const double* Xs, const double* z,
                           const double* var_extra, int32_t maxno, double* imax_out,
                           double* mean_out, double* var_out);
+
+/* A member of p outputs: the separable multi-output emulator (gpe_set_outputs) as one member,
+ * with one copy of L^-1 and one pass over K* and L^-1 K* for all p outputs.
+ * ctx: data, outputs (gpe_set_outputs, p of them) and the factor gpe_factor(kernel, delta, nu, 1,
+ * r_scale) resident.  B q x p row-major (gpe_beta_multi's), Sigma p x p row-major (symmetric).
+ * The member contributes p outputs to the set, in order; returns the member's number.  It
+ * snapshots what gpe_hm_add snapshots, with [Gamma (p columns), G (q columns)],
+ * Gamma = A^-1 (F - H B) by gpe_posterior_mean_multi's route, in place of [gamma, G], and B,
+ * Sigma and p besides; the context keeps its factor, its outputs and every bit other entries
+ * return.  active, hdim, hval as gpe_hm_add.
+ * In gpe_hm_implausibility "p" is then gpe_hm_outputs: z and var_extra have that many values,
+ * maxno lies in [1, outputs], mean_out / var_out have one row per output, and output a of this
+ * member has mean mu_a = h . B[:, a] + sum_i Gamma_ia K*_i and variance Sigma_aa c, with
+ *   c = cdiag - |L^-1 K*|^2 + |(h - G^T K*) Kq^-T|^2   (gpe_posterior's variance at sigma = 1).
+ * gpe_hm_count still counts members; a set of gpe_hm_add members behaves as before.
+ * Limits: n <= 512, d <= 32, q <= 16, 1 <= p, p + q <= 32, and 32 outputs per set in all (a
+ * gpe_hm_add member counts 1); beyond, GPE_ERR_UNSUPPORTED and the set is unchanged.
+ * GPE_ERR_STATE without a resident factor or without outputs; GPE_ERR_ARG for a NULL pointer, p
+ * other than the context's, a d or q other than the context's, a negative active index, hdim[j]
+ * outside [-1, d) or a context on another device; GPE_NOT_PD as gpe_hm_add. */
+int gpe_hm_add_multi(gpe_hm* set, gpe_ctx* ctx, int32_t d, const int32_t* active, int32_t q,
+                     const int32_t* hdim, const double* hval, int32_t p, const double* B,
+                     const double* Sigma);
+int gpe_hm_outputs(const gpe_hm* set);      /* sum of the members' outputs (a gpe_hm_add member: 1) */
+int gpe_hm_member_outputs(const gpe_hm* set, int32_t member);
+
+/* Joint (multivariate) implausibility of one multi-output member (Vernon, Goldstein & Bower
+ * 2010): z (p), V (p x p row-major, symmetric positive definite: observation error + model
+ * discrepancy),
+ *   I^2 = (z - mu)^T (c Sigma + V)^-1 (z - mu)
+ * per candidate, with the between-output covariance Sigma of gpe_hm_add_multi.  W with
+ * W^T V W = I and W^T Sigma W = Lambda is found once per call on the host (a Cholesky of V and a
+ * Jacobi eigendecomposition; exact algebra), so that per candidate
+ *   I^2 = sum_j (W^T (mu - z))_j^2 / (c lambda_j + 1).
+ * i2_out (m) = I^2, no square root, no clamping; mean_out (p x m, row a output a) and c_out (m):
+ * both or neither.  Chunks, order of the sums and repeatability as gpe_hm_implausibility.
+ * GPE_ERR_ARG for a member that is not multi-output, m <= 0, a NULL among Xs, z, V and i2_out,
+ * one of mean_out / c_out without the other, or D smaller than the member's largest active
+ * index + 1; GPE_NOT_PD (with text in gpe_hm_last_error) when V is not positive definite. */
+int gpe_hm_implausibility_mv(gpe_hm* set, int32_t member, int64_t m, int32_t D, const double* Xs,
+                             const double* z, const double* V, double* i2_out, double* mean_out,
+                             double* c_out);
 
 /* ---- Sensitivity / UQ building blocks, resident factor --------
  * Replace the O(n^2) parts of sensitivity/_sensitivityclasses.py (case2): the
