@@ -41,6 +41,7 @@
 #include "gpemu_postgroup.hpp"
 #include "gpemu_hm.hpp"
 #include "gpemu_hm_mv.hpp"
+#include "gpemu_hm_cand.hpp"
 #include "gpemu_host_alloc.hpp"
 
 using namespace gpe;
@@ -4438,6 +4439,40 @@ void hm_multi_args(const HmEmul& e, HmPostMultiArgs& a) {
   a.B = e.beta; a.sdiag = e.sdiag; a.Wj = nullptr; a.lam = nullptr; a.p = e.p;
 }
 
+// The univariate post kernels of one chunk of mc candidates at dX: every member whose bit of `use`
+// is set (a member's bit is its first output's) writes its outputs' I^2 to dI2 (p x cl) and, where
+// dparts is given, its means and variances to dparts (mean p x cl, then var p x cl).
+int hm_post_all(gpe_hm* h, const double* dX, int D, long long mc, long long cl, const double* z, const double* var_extra,
+                unsigned use, double* dI2, double* dparts) {
+  const int p = h->outputs;
+  for (const HmEmul& e : h->em) {
+    const int o = e.first;
+    if (!((use >> o) & 1u)) continue;
+    const dim3 grid((unsigned)hm_tiles(mc, e.pt));
+    const size_t lds = (size_t)hm_lds_doubles(e.n, e.pt) * sizeof(double);
+    if (e.p) {
+      HmPostMultiArgs a = {};
+      hm_post_args(e, dX, D, mc, a);
+      hm_multi_args(e, a);
+      a.i2 = dI2 + o * cl; a.ldo = cl; a.joint = 0;
+      a.mean = dparts ? dparts + o * cl : nullptr;
+      a.var = dparts ? dparts + (p + o) * cl : nullptr;
+      for (int j = 0; j < e.p; ++j) a.zs[j] = z[o + j], a.ves[j] = var_extra[o + j];
+      hm_launch_post(e, grid, lds, h->stream, a);
+    } else {
+      HmPostArgs a;
+      hm_post_args(e, dX, D, mc, a);
+      a.i2 = dI2 + o * cl;
+      a.mean = dparts ? dparts + o * cl : nullptr;
+      a.var = dparts ? dparts + (p + o) * cl : nullptr;
+      a.z = z[o]; a.ve = var_extra[o];
+      hm_launch_post(e, grid, lds, h->stream, a);
+    }
+    HM_HIPCHK(h, hipGetLastError());
+  }
+  return GPE_OK;
+}
+
 // The set's chunk buffers: dev doubles on the device, pin pinned doubles, grown when too small
 int hm_workspace(gpe_hm* h, size_t dev, size_t pin) {
   if (dev > h->work_cap) {
@@ -4665,30 +4700,7 @@ int gpe_hm_implausibility(gpe_hm* h, int64_t m, int32_t D, const double* Xs, con
     const long long mc = std::min(CH, m - s0);
     std::memcpy(pin_in[slot], Xs + s0 * D, (size_t)mc * D * sizeof(double));
     HM_HIPCHK(h, hipMemcpyAsync(dX, pin_in[slot], (size_t)mc * D * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    for (const HmEmul& e : h->em) {
-      const int o = e.first;
-      const dim3 grid((unsigned)hm_tiles(mc, e.pt));
-      const size_t lds = (size_t)hm_lds_doubles(e.n, e.pt) * sizeof(double);
-      if (e.p) {
-        HmPostMultiArgs a = {};
-        hm_post_args(e, dX, D, mc, a);
-        hm_multi_args(e, a);
-        a.i2 = dI2 + o * cl; a.ldo = cl; a.joint = 0;
-        a.mean = parts ? dparts + o * cl : nullptr;
-        a.var = parts ? dparts + (p + o) * cl : nullptr;
-        for (int j = 0; j < e.p; ++j) a.zs[j] = z[o + j], a.ves[j] = var_extra[o + j];
-        hm_launch_post(e, grid, lds, h->stream, a);
-      } else {
-        HmPostArgs a;
-        hm_post_args(e, dX, D, mc, a);
-        a.i2 = dI2 + o * cl;
-        a.mean = parts ? dparts + o * cl : nullptr;
-        a.var = parts ? dparts + (p + o) * cl : nullptr;
-        a.z = z[o]; a.ve = var_extra[o];
-        hm_launch_post(e, grid, lds, h->stream, a);
-      }
-      HM_HIPCHK(h, hipGetLastError());
-    }
+    if (int rc = hm_post_all(h, dX, D, mc, cl, z, var_extra, ~0u, dI2, parts ? dparts : nullptr)) return rc;
     hipLaunchKernelGGL(k_hm_select, dim3((unsigned)((mc + 255) / 256)), dim3(256), 0, h->stream, dI2, cl, p, (int)maxno,
                        (int)mc, dsel);
     HM_HIPCHK(h, hipGetLastError());
@@ -4787,6 +4799,219 @@ int gpe_hm_implausibility_mv(gpe_hm* h, int32_t member, int64_t m, int32_t D, co
         return GPE_OK;
       },
       host, [&] { (void)hipStreamSynchronize(h->stream); });
+}
+
+}  // extern "C"
+
+// ---- candidates made and reduced on the device (kernels in gpemu_hm_cand.hpp) ----
+namespace {
+
+struct HmMesh {
+  int32_t D, ca, cb, g1, g2;
+  const double *x1, *x2, *others;
+  int64_t ns;
+};
+
+// what gpe_hm_cells and gpe_hm_cells_mv check of the mesh, before any device work
+int hm_mesh_check(gpe_hm* h, const HmMesh& m, const double* imp_out, const int64_t* below_out) {
+  if (m.g1 < 1 || m.g2 < 1 || m.ns < 1) return hm_fail(h, GPE_ERR_ARG, "g1, g2 and ns must be at least 1");
+  if (m.D < 2 || m.ca < 0 || m.cb < 0 || m.ca >= m.D || m.cb >= m.D || m.ca == m.cb)
+    return hm_fail(h, GPE_ERR_ARG, "ca and cb must be two different columns in [0, D), D >= 2");
+  if (!m.x1 || !m.x2 || !imp_out || !below_out || (m.D > 2 && !m.others))
+    return hm_fail(h, GPE_ERR_ARG, "bad hm_cells args (a NULL pointer)");
+  if ((double)m.g1 * (double)m.g2 * (double)m.ns >= (double)HM_CELLS_MAX)
+    return hm_fail(h, GPE_ERR_ARG, "g1 g2 ns must be below 2^40");
+  return GPE_OK;
+}
+
+// The chunks of a mesh: generator, `post` (the caller's post kernels: dX, mc -> dI2), reducer,
+// queued one after the other with no synchronisation; then the accumulators come back.
+// p outputs in dI2 (leading dimension cl; p = 0: the one row of the joint measure), `use` their
+// flags; extra: words behind the workspace
+// for the caller (their place is returned in *dextra before the first chunk).
+template <class Post>
+int hm_cells_run(gpe_hm* h, const HmMesh& m, int p, int maxno, unsigned use, double cm, long long extra,
+                 const double* extra_host, double** dextra, double* imp_out, int64_t* below_out, Post post) {
+  HM_HIPCHK(h, hipSetDevice(h->device));
+  const long long cells = (long long)m.g1 * m.g2, M = cells * m.ns;
+  const long long CH = h->chunk, cl = std::min<long long>(CH, M);
+  const HmCellsWork w = hm_work_cells(cl, m.D, p, maxno, m.g1, m.g2, m.ns, extra);
+  if (int rc = hm_workspace(h, (size_t)w.dev(), 0)) return rc;
+  double* dX = h->dwork;
+  double* dI2 = dX + w.pts;
+  double* dx1 = dI2 + w.i2;
+  double* dx2 = dx1 + m.g1;
+  double* doth = dx2 + m.g2;
+  double* dimp = dx1 + w.mesh;
+  long long* dbelow = reinterpret_cast<long long*>(dimp + w.acc);
+  *dextra = dimp + 2 * w.acc;
+  // (every earlier call has ended: blocking copies, once per call)
+  HM_HIPCHK(h, hipMemcpy(dx1, m.x1, (size_t)m.g1 * sizeof(double), hipMemcpyHostToDevice));
+  HM_HIPCHK(h, hipMemcpy(dx2, m.x2, (size_t)m.g2 * sizeof(double), hipMemcpyHostToDevice));
+  if (m.D > 2)
+    HM_HIPCHK(h, hipMemcpy(doth, m.others, (size_t)m.ns * (m.D - 2) * sizeof(double), hipMemcpyHostToDevice));
+  if (extra) HM_HIPCHK(h, hipMemcpy(*dextra, extra_host, (size_t)extra * sizeof(double), hipMemcpyHostToDevice));
+  int rc = GPE_OK;
+  for (long long s0 = 0; s0 < M && rc == GPE_OK; s0 += CH) {
+    const long long mc = std::min(CH, M - s0);
+    hipLaunchKernelGGL(k_hm_mesh, dim3((unsigned)((mc * m.D + 255) / 256)), dim3(256), 0, h->stream, dx1, dx2, doth,
+                       (int)m.D, (int)m.ca, (int)m.cb, (long long)m.g2, (long long)m.ns, s0, mc, dX);
+    rc = post(dX, dI2, cl, mc);
+    if (rc != GPE_OK) break;
+    const dim3 pieces((unsigned)hm_pieces(s0, mc, m.ns));
+    if (hm_top_slots(maxno) == HM_TOP_FEW)
+      hipLaunchKernelGGL(k_hm_cells<HM_TOP_FEW>, pieces, dim3(HM_LANES), 0, h->stream, dI2, cl, p ? p : 1, maxno, use, cm,
+                         s0, mc, (long long)m.ns, cells, dimp, dbelow);
+    else
+      hipLaunchKernelGGL(k_hm_cells<HM_MAX_EMUL>, pieces, dim3(HM_LANES), 0, h->stream, dI2, cl, p ? p : 1, maxno, use, cm,
+                         s0, mc, (long long)m.ns, cells, dimp, dbelow);
+    if (hipGetLastError() != hipSuccess) rc = hm_fail(h, GPE_ERR_HIP, "a launch of gpe_hm_cells failed");
+  }
+  hipError_t e = hipStreamSynchronize(h->stream);
+  if (rc != GPE_OK) return rc;
+  HM_HIPCHK(h, e);
+  HM_HIPCHK(h, hipMemcpy(imp_out, dimp, (size_t)w.acc * sizeof(double), hipMemcpyDeviceToHost));
+  HM_HIPCHK(h, hipMemcpy(below_out, dbelow, (size_t)w.acc * sizeof(long long), hipMemcpyDeviceToHost));
+  return GPE_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gpe_hm_cells(gpe_hm* h, int32_t D, int32_t ca, int32_t cb, int32_t g1, const double* x1, int32_t g2, const double* x2,
+                 int64_t ns, const double* others, const int32_t* use, const double* z, const double* var_extra,
+                 int32_t maxno, double cm, double* imp_out, int64_t* below_out) {
+  if (!h) return GPE_ERR_ARG;
+  h->err.clear();
+  const int p = h->outputs;
+  if (p == 0) return hm_fail(h, GPE_ERR_STATE, "the set is empty (call gpe_hm_add)");
+  const HmMesh m{D, ca, cb, g1, g2, x1, x2, others, ns};
+  if (int rc = hm_mesh_check(h, m, imp_out, below_out)) return rc;
+  if (!z || !var_extra) return hm_fail(h, GPE_ERR_ARG, "bad hm_cells args (z and var_extra not NULL)");
+  if (maxno < 1 || maxno > p) return hm_fail(h, GPE_ERR_ARG, "maxno must be in [1, outputs of the set]");
+  for (const HmEmul& e : h->em)
+    if (D <= e.maxact) return hm_fail(h, GPE_ERR_ARG, "D is smaller than an emulator's largest active index + 1");
+  // a member's flag is its first output's, for all its outputs
+  unsigned mask = 0;
+  for (const HmEmul& e : h->em)
+    if (!use || use[e.first])
+      for (int j = 0; j < e.outputs(); ++j) mask |= 1u << (e.first + j);
+  double* dextra = nullptr;
+  return hm_cells_run(h, m, p, (int)maxno, mask, cm, 0, nullptr, &dextra, imp_out, below_out,
+                      [&](const double* dX, double* dI2, long long cl, long long mc) {
+                        return hm_post_all(h, dX, D, mc, cl, z, var_extra, mask, dI2, nullptr);
+                      });
+}
+
+int gpe_hm_cells_mv(gpe_hm* h, int32_t member, int32_t D, int32_t ca, int32_t cb, int32_t g1, const double* x1,
+                    int32_t g2, const double* x2, int64_t ns, const double* others, const double* z, const double* V,
+                    double cm, double* imp_out, int64_t* below_out) {
+  if (!h) return GPE_ERR_ARG;
+  h->err.clear();
+  if (h->outputs == 0) return hm_fail(h, GPE_ERR_STATE, "the set is empty (call gpe_hm_add)");
+  if (member < 0 || member >= (int)h->em.size() || h->em[member].p == 0)
+    return hm_fail(h, GPE_ERR_ARG, "member must be a multi-output member of the set (gpe_hm_add_multi)");
+  const HmMesh m{D, ca, cb, g1, g2, x1, x2, others, ns};
+  if (int rc = hm_mesh_check(h, m, imp_out, below_out)) return rc;
+  if (!z || !V) return hm_fail(h, GPE_ERR_ARG, "bad hm_cells_mv args (z and V not NULL)");
+  const HmEmul& e = h->em[member];
+  if (D <= e.maxact) return hm_fail(h, GPE_ERR_ARG, "D is smaller than the member's largest active index + 1");
+  const int p = e.p;
+  std::vector<double> wl((size_t)p * p + p);
+  if (hm_mv_prepare(p, e.Sigma.data(), V, wl.data(), wl.data() + (size_t)p * p))
+    return hm_fail(h, GPE_NOT_PD, "V is not positive definite");
+  double* dW = nullptr;
+  return hm_cells_run(h, m, 0, 1, 1u, cm, (long long)wl.size(), wl.data(), &dW, imp_out, below_out,
+                      [&](const double* dX, double* dI2, long long cl, long long mc) -> int {
+                        HmPostMultiArgs a = {};
+                        hm_post_args(e, dX, D, mc, a);
+                        hm_multi_args(e, a);
+                        a.Wj = dW; a.lam = dW + (size_t)p * p; a.joint = 1;
+                        a.i2 = dI2; a.ldo = cl; a.mean = nullptr; a.var = nullptr;
+                        for (int j = 0; j < p; ++j) a.zs[j] = z[j];
+                        hm_launch_post(e, dim3((unsigned)hm_tiles(mc, e.pt)),
+                                       (size_t)hm_lds_doubles(e.n, e.pt) * sizeof(double), h->stream, a);
+                        HM_HIPCHK(h, hipGetLastError());
+                        return GPE_OK;
+                      });
+}
+
+int gpe_hm_sample(gpe_hm* h, int32_t D, const double* lo, const double* hi, const uint64_t state[2],
+                  const uint64_t inc[2], int64_t first, int64_t m, const double* z, const double* var_extra,
+                  int32_t maxno, double cm, int64_t cap, double* pts_out, int64_t* idx_out, int64_t* accepted_out) {
+  if (!h) return GPE_ERR_ARG;
+  h->err.clear();
+  const int p = h->outputs;
+  if (p == 0) return hm_fail(h, GPE_ERR_STATE, "the set is empty (call gpe_hm_add)");
+  if (m < 1 || first < 0 || cap < 0 || D < 1) return hm_fail(h, GPE_ERR_ARG, "bad hm_sample args (m >= 1, first >= 0, cap >= 0)");
+  if (!lo || !hi || !state || !inc || !z || !var_extra || !accepted_out || (cap > 0 && (!pts_out || !idx_out)))
+    return hm_fail(h, GPE_ERR_ARG, "bad hm_sample args (a NULL pointer)");
+  if (((hm_u128)first + (hm_u128)m) * (hm_u128)D >= (hm_u128)1 << 63)
+    return hm_fail(h, GPE_ERR_ARG, "(first + m) D must be below 2^63");
+  if (maxno < 1 || maxno > p) return hm_fail(h, GPE_ERR_ARG, "maxno must be in [1, outputs of the set]");
+  for (const HmEmul& e : h->em)
+    if (D <= e.maxact) return hm_fail(h, GPE_ERR_ARG, "D is smaller than an emulator's largest active index + 1");
+  HM_HIPCHK(h, hipSetDevice(h->device));
+  const long long CH = h->chunk, cl = std::min<long long>(CH, m), rows = std::min<long long>(cap, m);
+  const HmSampleWork w = hm_work_sample(cl, D, p, rows);
+  if (int rc = hm_workspace(h, (size_t)w.dev(), 0)) return rc;
+  double* dX = h->dwork;
+  double* dI2 = dX + w.pts;
+  long long* dranks = reinterpret_cast<long long*>(dI2 + w.i2);
+  long long* dtotal = dranks + (w.ranks - 1);
+  uint64_t* dtable = reinterpret_cast<uint64_t*>(dranks + w.ranks);
+  double* dbox = reinterpret_cast<double*>(dtable + w.table);
+  double* dpts = dbox + w.box;
+  long long* didx = reinterpret_cast<long long*>(dpts + w.out_pts);
+  const hm_u128 s128 = hm_u128_of(state[0], state[1]), i128 = hm_u128_of(inc[0], inc[1]);
+  const int digits = hm_digits(cl);
+  std::vector<uint64_t> table((size_t)w.table);
+  hm_jump_table(D, i128, digits, table.data());
+  std::vector<double> box((size_t)2 * D);
+  for (int k = 0; k < D; ++k) box[k] = lo[k], box[D + k] = hi[k];
+  // (every earlier call has ended: blocking copies, once per call)
+  HM_HIPCHK(h, hipMemcpy(dtable, table.data(), table.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
+  HM_HIPCHK(h, hipMemcpy(dbox, box.data(), box.size() * sizeof(double), hipMemcpyHostToDevice));
+  HM_HIPCHK(h, hipMemsetAsync(dtotal, 0, sizeof(long long), h->stream));
+  const unsigned all = ~0u;
+  int rc = GPE_OK;
+  for (long long s0 = 0; s0 < m && rc == GPE_OK; s0 += CH) {
+    const long long mc = std::min(CH, m - s0);
+    const hm_u128 start = hm_pcg_apply(hm_jump((uint64_t)(first + s0) * (uint64_t)D, i128), s128);
+    const unsigned nb = (unsigned)hm_acc_blocks(mc);
+    hipLaunchKernelGGL(k_hm_draw, dim3((unsigned)((mc + 255) / 256)), dim3(256), 0, h->stream, dtable, digits,
+                       (uint64_t)(start >> 64), (uint64_t)start, inc[0], inc[1], dbox, (int)D, mc, dX);
+    rc = hm_post_all(h, dX, D, mc, cl, z, var_extra, all, dI2, nullptr);
+    if (rc != GPE_OK) break;
+    const bool few = hm_top_slots(maxno) == HM_TOP_FEW;
+    if (few)
+      hipLaunchKernelGGL(k_hm_count<HM_TOP_FEW>, dim3(nb), dim3(HM_ACC_BLOCK), 0, h->stream, dI2, cl, p, (int)maxno, cm, mc,
+                         dranks);
+    else
+      hipLaunchKernelGGL(k_hm_count<HM_MAX_EMUL>, dim3(nb), dim3(HM_ACC_BLOCK), 0, h->stream, dI2, cl, p, (int)maxno, cm, mc,
+                         dranks);
+    hipLaunchKernelGGL(k_hm_ranks, dim3(1), dim3(256), 0, h->stream, dranks, (long long)nb, dtotal);
+    if (few)
+      hipLaunchKernelGGL(k_hm_scatter<HM_TOP_FEW>, dim3(nb), dim3(HM_ACC_BLOCK), 0, h->stream, dI2, cl, p, (int)maxno, cm,
+                         mc, dX, (int)D, (long long)(first + s0), dranks, (long long)rows, dpts, didx);
+    else
+      hipLaunchKernelGGL(k_hm_scatter<HM_MAX_EMUL>, dim3(nb), dim3(HM_ACC_BLOCK), 0, h->stream, dI2, cl, p, (int)maxno, cm,
+                         mc, dX, (int)D, (long long)(first + s0), dranks, (long long)rows, dpts, didx);
+    if (hipGetLastError() != hipSuccess) rc = hm_fail(h, GPE_ERR_HIP, "a launch of gpe_hm_sample failed");
+  }
+  hipError_t e = hipStreamSynchronize(h->stream);
+  if (rc != GPE_OK) return rc;
+  HM_HIPCHK(h, e);
+  long long total = 0;
+  HM_HIPCHK(h, hipMemcpy(&total, dtotal, sizeof(long long), hipMemcpyDeviceToHost));
+  *accepted_out = total;
+  const long long got = std::min(total, rows);
+  if (got > 0) {
+    HM_HIPCHK(h, hipMemcpy(pts_out, dpts, (size_t)got * D * sizeof(double), hipMemcpyDeviceToHost));
+    HM_HIPCHK(h, hipMemcpy(idx_out, didx, (size_t)got * sizeof(long long), hipMemcpyDeviceToHost));
+  }
+  return GPE_OK;
 }
 
 }  // extern "C"

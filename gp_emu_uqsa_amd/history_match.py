@@ -29,7 +29,7 @@ from . import model as _model
 from . import multioutput as _mo
 
 __all__ = ["imp_plot", "imp_plot_recon", "nonimp_data", "new_wave_design", "EmulatorSet", "implausibility",
-           "implausibility_mv", "nonimp_sample"]
+           "implausibility_mv", "nonimp_sample", "imp_maps"]
 
 
 # ----------------------------------------------------------------- helpers (_hmutilfunctions.py)
@@ -147,11 +147,26 @@ def plot_options(plt_ref, ax, fig, minmax=None):
     _plt.tight_layout()
 
 
+def _save_maps(fileStr, s, maxno, IMP, ODP):
+    nfileStr = fileStr + "_" if fileStr != "" else fileStr
+    for m in range(maxno):
+        _np.savetxt(nfileStr + str(m + 1) + "_" + "IMP_" + str(s[0]) + '_' + str(s[1]), IMP[m])
+        _np.savetxt(nfileStr + str(m + 1) + "_" + "ODP_" + str(s[0]) + '_' + str(s[1]), ODP[m])
+
+
 # ----------------------------------------------------------------- API (history_match.py)
 def imp_plot(emuls, zs, cm, var_extra, maxno=1, olhcmult=100, grid=10, act=[], fileStr="", plot=True):
     """Implausibility (lower triangle) and optical depth (upper triangle) per pair of
     active inputs over a grid x grid mesh, each cell sampled by an oLHC design of the
-    other inputs (reference :7-150).  Writes <m>_IMP_<i>_<j> / <m>_ODP_<i>_<j>."""
+    other inputs (reference :7-150).  Writes <m>_IMP_<i>_<j> / <m>_ODP_<i>_<j>.
+
+    ``emuls`` may be an ``EmulatorSet``: every pair's maps then come from ``EmulatorSet.maps``
+    (on a fused set: candidates made and reduced on the device), with the same
+    optLatinHyperCube call per pair, the same prints and the same files.  A list keeps the
+    ``_posterior_diag`` route below."""
+    hset = emuls if isinstance(emuls, EmulatorSet) else None
+    if hset is not None:
+        emuls = hset._views
     sets, minmax, orig_minmax = emulsetup(emuls)
     check_act(act, sets)
     act_ref = ref_act(minmax)
@@ -188,6 +203,18 @@ def imp_plot(emuls, zs, cm, var_extra, maxno=1, olhcmult=100, grid=10, act=[], f
         filename = "imp_input_" + str(s[0]) + '_' + str(s[1])
         _gd.optLatinHyperCube(dim, n, N, olhc_range, filename)
         x_other = _np.loadtxt(filename)
+        if hset is not None:
+            xo = x_other.reshape(n, -1) if x_other.ndim > 1 else x_other.reshape(n, 1)
+            print("\nCalculating Implausibilities...")
+            imp, odp = hset.maps(zs, var_extra, cm, (act_ref[str(s[0])], act_ref[str(s[1])]), X1, X2, xo,
+                                 maxno=maxno, use=hset.pair_flags(s))
+            for m in range(maxno):
+                IMP[m][:, :] = imp[m]
+                ODP[m][:, :] = odp[m]
+            _save_maps(fileStr, s, maxno, IMP, ODP)
+            if plot:
+                make_plots(s, plt_ref, cm, maxno, ax, IMP, ODP, minmax=minmax)
+            continue
         # every grid cell at once: cell c = i*grid + j owns rows [c n, (c+1) n)
         cells = grid * grid
         x = _np.empty((cells * n, num_inputs))
@@ -212,10 +239,7 @@ def imp_plot(emuls, zs, cm, var_extra, maxno=1, olhcmult=100, grid=10, act=[], f
             col = Imaxes[:, :, -(m + 1)]
             IMP[m][:, :] = col.min(axis=1).reshape(grid, grid)
             ODP[m][:, :] = (col < cm).sum(axis=1).reshape(grid, grid) / float(n)
-        nfileStr = fileStr + "_" if fileStr != "" else fileStr
-        for m in range(maxno):
-            _np.savetxt(nfileStr + str(m + 1) + "_" + "IMP_" + str(s[0]) + '_' + str(s[1]), IMP[m])
-            _np.savetxt(nfileStr + str(m + 1) + "_" + "ODP_" + str(s[0]) + '_' + str(s[1]), ODP[m])
+        _save_maps(fileStr, s, maxno, IMP, ODP)
         if plot:
             make_plots(s, plt_ref, cm, maxno, ax, IMP, ODP, minmax=minmax)
     if plot:
@@ -248,6 +272,8 @@ def imp_plot_recon(cm, maxno=1, act=[], fileStr=""):
 
 
 def _implausible_rows(emuls, zs, var_extra, x, act_ref, maxno, cm):
+    if isinstance(emuls, EmulatorSet):
+        return emuls.implausibility(zs, var_extra, x, maxno)[:, -maxno] < cm
     I2 = _np.zeros((x.shape[0], len(emuls)))
     for o in range(len(emuls)):
         E, z, var_e = emuls[o], zs[o], var_extra[o]
@@ -260,8 +286,9 @@ def _implausible_rows(emuls, zs, var_extra, x, act_ref, maxno, cm):
 
 def nonimp_data(emuls, zs, cm, var_extra, datafiles, maxno=1, act=[], fileStr=""):
     """Keep the non-implausible rows of a data set (reference :195-256).  Writes
-    `nonimp_<inputs file>` (scaled inputs, as the reference) and `noninp_<outputs file>`."""
-    sets, minmax, orig_minmax = emulsetup(emuls)
+    `nonimp_<inputs file>` (scaled inputs, as the reference) and `noninp_<outputs file>`.
+    ``emuls``: a list (the ``_posterior_diag`` loop) or an ``EmulatorSet`` (its ``implausibility``)."""
+    sets, minmax, orig_minmax = emulsetup(emuls._views if isinstance(emuls, EmulatorSet) else emuls)
     act_ref = ref_act(minmax)
     check_act(act, sets)
     maxno = int(maxno)
@@ -278,8 +305,9 @@ def nonimp_data(emuls, zs, cm, var_extra, datafiles, maxno=1, act=[], fileStr=""
 
 def new_wave_design(emuls, zs, cm, var_extra, datafiles, maxno=1, olhcmult=100, act=[], fileStr=""):
     """Non-implausible points of a new oLHC design optimised against the given
-    (non-implausible) data (reference :259-339).  Writes `<fileStr_><inputs file>`."""
-    sets, minmax, orig_minmax = emulsetup(emuls)
+    (non-implausible) data (reference :259-339).  Writes `<fileStr_><inputs file>`.
+    ``emuls``: a list or an ``EmulatorSet``, as ``nonimp_data``."""
+    sets, minmax, orig_minmax = emulsetup(emuls._views if isinstance(emuls, EmulatorSet) else emuls)
     act_ref = ref_act(minmax)
     check_act(act, sets)
     dim = len(minmax)
@@ -335,6 +363,8 @@ class EmulatorSet:
         self.minmax = minmax
         self.act_ref = ref_act(minmax)
         self.D = len(minmax)
+        self._views = views
+        self._active = [list(E.beliefs.active_index) for E in views]
         self._cols = [[self.act_ref[str(l)] for l in E.beliefs.active_index] for E in views]
         # the items' places among the outputs: item i owns [_first[i], _first[i] + its outputs)
         counts = [E.p if multi else 1 for E, multi in zip(self.emuls, self._multi)]
@@ -419,8 +449,15 @@ class EmulatorSet:
         maxno = int(maxno)
         if self.fused:
             return self._set.implausibility(x, zs, var_extra, maxno=maxno)
+        return _imaxes(self._loop_i2(zs, var_extra, x), maxno)
+
+    def _loop_i2(self, zs, var_extra, x, use=None):
+        """I^2 (m x outputs) by the route outside the fused path; an item whose flag of ``use``
+        (one per item) is off keeps its zero columns, as imp_plot's loop leaves them."""
         I2 = _np.zeros((x.shape[0], self.outputs))
-        for E, multi, cols, o in zip(self.emuls, self._multi, self._cols, self._first):
+        for i, (E, multi, cols, o) in enumerate(zip(self.emuls, self._multi, self._cols, self._first)):
+            if use is not None and not use[i]:
+                continue
             if multi:
                 mean, c, Sigma = _mo.posterior(E, x[:, cols])
                 for a in range(E.p):
@@ -428,7 +465,70 @@ class EmulatorSet:
             else:
                 mean, var = _posterior_diag(E, x[:, cols])
                 I2[:, o] = (mean - zs[o]) ** 2 / (var + var_extra[o])
-        return _imaxes(I2, maxno)
+        return I2
+
+    def pair_flags(self, s):
+        """imp_plot's rule for the input pair s = [i, j] (active indices): one flag per item, on
+        where the item reads both inputs."""
+        return [s[0] in ai and s[1] in ai for ai in self._active]
+
+    def maps(self, zs, var_extra, cm, pair, x1, x2, others, maxno=1, use=None, joint=None):
+        """The maps of imp_plot over the mesh x1 x x2 of the columns ``pair`` = (ca, cb) of the
+        D-wide rows: (IMP, ODP), each maxno x g1 x g2.  Cell (i, j) has the ns candidates with
+        x1[i] in column ca, x2[j] in column cb and ``others`` (ns x (D - 2)) in the remaining
+        columns in ascending order.  Level l is the (l + 1)-th largest implausibility over the
+        outputs (``Imaxes[:, :, -(l + 1)]`` of imp_plot); IMP is its minimum over a cell's
+        candidates (NaN if one is NaN), ODP the fraction of them below cm.  ``use``: one flag per
+        item (None: all on); an item switched off enters with I^2 = 0, imp_plot's untouched
+        column.  ``joint`` = (item, V): the joint measure of that MultiEmulator in place of the
+        univariate ones, one level; zs is then the item's z.
+
+        A fused set makes the candidates and reduces them on the device (gpe_hm_cells): only
+        the maps come back.  Any other set forms the explicit rows and reduces in NumPy."""
+        ca, cb = int(pair[0]), int(pair[1])
+        x1, x2 = _np.asarray(x1, dtype=float).ravel(), _np.asarray(x2, dtype=float).ravel()
+        others = _np.asarray(others, dtype=float)
+        if others.ndim == 1:
+            others = others.reshape(-1, 1) if self.D != 2 else _np.zeros((others.size, 0))
+        ns, maxno = others.shape[0], int(maxno)
+        if joint is not None:
+            item, V = int(joint[0]), _np.asarray(joint[1], dtype=float)
+            if not 0 <= item < len(self.emuls) or not self._multi[item]:
+                raise ValueError("joint takes an item that is a MultiEmulator")
+            if V.ndim == 1:
+                V = _np.diag(V)
+            maxno = 1
+        if self.fused:
+            if joint is not None:
+                imp, below = self._set.cells_mv(item, self.D, (ca, cb), x1, x2, others, zs, V, cm)
+                imp, below = imp[None], below[None]
+            else:
+                flags = None
+                if use is not None:
+                    counts = [E.p if multi else 1 for E, multi in zip(self.emuls, self._multi)]
+                    flags = _np.repeat(_np.asarray(use, dtype=bool), counts)
+                imp, below = self._set.cells(self.D, (ca, cb), x1, x2, others, zs, var_extra, cm, maxno=maxno,
+                                             use=flags)
+            return imp, below / float(ns)
+        g1, g2 = x1.size, x2.size
+        cells = g1 * g2
+        x = _np.empty((cells * ns, self.D))
+        x[:, ca] = _np.repeat(_np.repeat(x1, g2), ns)
+        x[:, cb] = _np.repeat(_np.tile(x2, g1), ns)
+        x[:, [k for k in range(self.D) if k not in (ca, cb)]] = _np.tile(others, (cells, 1))
+        if joint is not None:
+            top = self.implausibility_mv(item, zs, V, x).reshape(-1, 1)
+        elif use is None:
+            top = self.implausibility(zs, var_extra, x, maxno)
+        else:
+            top = _imaxes(self._loop_i2(zs, var_extra, x, use), maxno)
+        top = top.reshape(cells, ns, maxno)
+        IMP, ODP = _np.empty((maxno, g1, g2)), _np.empty((maxno, g1, g2))
+        for l in range(maxno):
+            col = top[:, :, -(l + 1)]
+            IMP[l] = col.min(axis=1).reshape(g1, g2)
+            ODP[l] = (col < cm).sum(axis=1).reshape(g1, g2) / float(ns)
+        return IMP, ODP
 
     def implausibility_mv(self, item, z, V, x, parts=False):
         """The joint (multivariate) implausibility of item ``item``, a MultiEmulator of p outputs,
@@ -505,20 +605,58 @@ def implausibility(emuls_or_set, zs, var_extra, x, maxno=1):
             S.close()
 
 
-def nonimp_sample(emuls_or_set, zs, cm, var_extra, count, maxno=1, seed=0, batch=2 ** 20, max_tried=None):
+def imp_maps(emuls_or_set, zs, var_extra, cm, pair, x1, x2, others, maxno=1, use=None, joint=None):
+    """(IMP, ODP), each maxno x g1 x g2: imp_plot's two maps over the mesh x1 x x2 of the columns
+    ``pair`` of the scaled D-wide rows, ``others`` (ns x (D - 2)) sampling every cell:
+    ``EmulatorSet.maps``.  Takes a list of emulators or an ``EmulatorSet``."""
+    S, mine = _as_set(emuls_or_set)
+    try:
+        return S.maps(zs, var_extra, cm, pair, x1, x2, others, maxno=maxno, use=use, joint=joint)
+    finally:
+        if mine:
+            S.close()
+
+
+def nonimp_sample(emuls_or_set, zs, cm, var_extra, count, maxno=1, seed=0, batch=2 ** 20, max_tried=None,
+                  generator=None):
     """Rejection sampling of the non-implausible region: uniform candidates in the scaled box,
     ``np.random.default_rng(seed).random((batch, D))`` batch after batch, kept where the
     maxno-th largest implausibility is below cm.  Returns (points, tried): the first ``count``
     accepted candidates in stream order (fewer if ``max_tried`` candidates did not yield them)
     and the number of candidates drawn up to and including the last one returned, or all that
-    were tried if fewer than ``count`` were found.  The result does not depend on ``batch``."""
+    were tried if fewer than ``count`` were found.  The result does not depend on ``batch``.
+
+    ``generator``: ``"host"`` draws and maps the candidates in NumPy and uploads them;
+    ``"device"`` (a fused set) reproduces the same PCG64 stream in a kernel from the generator's
+    state and increment, so that nothing is uploaded and only accepted rows come back
+    (gpe_hm_sample): the same points and the same ``tried``, bit for bit.  ``None``: ``"device"``
+    where the set is fused, else ``"host"``."""
     S, mine = _as_set(emuls_or_set)
     try:
         rng = _np.random.default_rng(seed)
         lo = _np.array([S.minmax[k][0] for k in sorted(S.minmax, key=int)], dtype=float)
         hi = _np.array([S.minmax[k][1] for k in sorted(S.minmax, key=int)], dtype=float)
         maxno, count, batch = int(maxno), int(count), int(batch)
+        on_device = getattr(S, "fused", False) and getattr(S, "_set", None) is not None
+        if generator is None:
+            generator = "device" if on_device else "host"
+        if generator not in ("host", "device"):
+            raise ValueError("generator is 'host', 'device' or None")
+        if generator == "device" and not on_device:
+            raise RuntimeError("generator='device' needs a fused EmulatorSet")
         kept, have, tried = [], 0, 0
+        if generator == "device":
+            st = rng.bit_generator.state["state"]
+            while have < count and (max_tried is None or tried < max_tried):
+                k = batch if max_tried is None else min(batch, int(max_tried) - tried)
+                pts, idx, accepted = S._set.sample(lo, hi, st["state"], st["inc"], tried, k, zs, var_extra, cm,
+                                                   maxno=maxno, cap=count - have)
+                kept.append(pts)
+                if have + accepted >= count:
+                    return _np.concatenate(kept), int(idx[-1]) + 1
+                have += accepted
+                tried += k
+            return (_np.concatenate(kept) if kept else _np.zeros((0, S.D))), tried
         while have < count and (max_tried is None or tried < max_tried):
             k = batch if max_tried is None else min(batch, int(max_tried) - tried)
             x = lo + rng.random((k, S.D)) * (hi - lo)

@@ -116,6 +116,15 @@ SIGNATURES = {
     "gpe_hm_outputs": (_ct.c_int, [_VP]),
     "gpe_hm_member_outputs": (_ct.c_int, [_VP, _ct.c_int32]),
     "gpe_hm_implausibility_mv": (_ct.c_int, [_VP, _ct.c_int32, _ct.c_int64, _ct.c_int32, _D, _D, _D, _D, _D, _D]),
+    "gpe_hm_cells": (_ct.c_int, [_VP, _ct.c_int32, _ct.c_int32, _ct.c_int32, _ct.c_int32, _D, _ct.c_int32, _D,
+                                 _ct.c_int64, _D, _ct.POINTER(_ct.c_int32), _D, _D, _ct.c_int32, _ct.c_double, _D,
+                                 _ct.POINTER(_ct.c_int64)]),
+    "gpe_hm_cells_mv": (_ct.c_int, [_VP, _ct.c_int32, _ct.c_int32, _ct.c_int32, _ct.c_int32, _ct.c_int32, _D,
+                                    _ct.c_int32, _D, _ct.c_int64, _D, _D, _D, _ct.c_double, _D,
+                                    _ct.POINTER(_ct.c_int64)]),
+    "gpe_hm_sample": (_ct.c_int, [_VP, _ct.c_int32, _D, _D, _ct.POINTER(_ct.c_uint64), _ct.POINTER(_ct.c_uint64),
+                                  _ct.c_int64, _ct.c_int64, _D, _D, _ct.c_int32, _ct.c_double, _ct.c_int64, _D,
+                                  _ct.POINTER(_ct.c_int64), _ct.POINTER(_ct.c_int64)]),
     "gpe_solve": (_ct.c_int, [_VP, _ct.c_int32, _D, _D]),
     "gpe_sense_pairs": (_ct.c_int, [_VP, _ct.c_int32, _D, _D, _ct.c_int32, _D, _D, _D]),
     "gpe_gauss_transform": (_ct.c_int, [_VP, _ct.c_int64, _ct.c_int32, _ct.POINTER(_ct.c_int32), _D, _D, _D,
@@ -973,6 +982,92 @@ class EmulatorSet:
         self._check(self.lib.gpe_hm_implausibility(self._h, m, D, _ptr(Xs), _ptr(z), _ptr(ve), maxno, _ptr(imax),
                                                    _ptr(mean), _ptr(var)), "gpe_hm_implausibility")
         return (imax, mean, var) if parts else imax
+
+    @staticmethod
+    def _mesh(D, pair, x1, x2, others):
+        D, ca, cb = int(D), int(pair[0]), int(pair[1])
+        x1, x2 = _f64(x1).ravel(), _f64(x2).ravel()
+        others = _f64(others)
+        if others.ndim == 1:
+            others = others.reshape(-1, 1) if D != 2 else _np.zeros((others.size, 0))
+        if others.ndim != 2 or others.shape[1] != max(D - 2, 0):
+            raise ValueError("others is ns x (D - 2): one row per sample of a cell")
+        return D, ca, cb, x1, x2, others
+
+    def cells(self, D, pair, x1, x2, others, z, var_extra, cm, maxno=1, use=None):
+        """Minimum-implausibility and count maps over the mesh x1 x x2 of the input pair
+        ``pair`` = (ca, cb), the candidates made and reduced on the device (gpe_hm_cells).
+        Candidate (i, j, t) has x1[i] in column ca, x2[j] in column cb and others[t] (ns x
+        (D - 2)) in the other columns in ascending order.  Returns (imp, below), each maxno x
+        g1 x g2: per level l (the (l + 1)-th largest implausibility over the outputs) the minimum
+        over a cell's ns samples (NaN if any is NaN) and the number of samples below cm.
+        use: one flag per output (None: all); an output switched off enters with I^2 = 0."""
+        D, ca, cb, x1, x2, others = self._mesh(D, pair, x1, x2, others)
+        p = self.outputs
+        z, ve = _f64(z).ravel(), _f64(var_extra).ravel()
+        if z.size != p or ve.size != p:
+            raise ValueError("z and var_extra have one entry per output of the set")
+        flags = None
+        if use is not None:
+            flags = _np.ascontiguousarray(_np.asarray(use) != 0, dtype=_np.int32).ravel()
+            if flags.size != p:
+                raise ValueError("use has one flag per output of the set")
+        maxno = int(maxno)
+        g1, g2 = x1.size, x2.size
+        imp = _np.zeros((max(maxno, 1), g1, g2))
+        below = _np.zeros((max(maxno, 1), g1, g2), dtype=_np.int64)
+        self._check(self.lib.gpe_hm_cells(
+            self._h, D, ca, cb, g1, _ptr(x1), g2, _ptr(x2), others.shape[0], _ptr(others) if D > 2 else None,
+            flags.ctypes.data_as(_ct.POINTER(_ct.c_int32)) if flags is not None else None, _ptr(z), _ptr(ve), maxno,
+            float(cm), _ptr(imp), below.ctypes.data_as(_ct.POINTER(_ct.c_int64))), "gpe_hm_cells")
+        return imp, below
+
+    def cells_mv(self, member, D, pair, x1, x2, others, z, V, cm):
+        """``cells`` for the joint measure of one multi-output member (gpe_hm_cells_mv): one
+        level, I = sqrt(I^2) of ``implausibility_mv``.  Returns (imp, below), each g1 x g2."""
+        D, ca, cb, x1, x2, others = self._mesh(D, pair, x1, x2, others)
+        p = self.member_outputs(member)
+        z, V = _f64(z).ravel(), _f64(V)
+        if p > 0 and (z.size != p or V.shape != (p, p)):
+            raise ValueError("z has one entry per output of the member, and V is p x p")
+        g1, g2 = x1.size, x2.size
+        imp = _np.zeros((g1, g2))
+        below = _np.zeros((g1, g2), dtype=_np.int64)
+        self._check(self.lib.gpe_hm_cells_mv(
+            self._h, int(member), D, ca, cb, g1, _ptr(x1), g2, _ptr(x2), others.shape[0],
+            _ptr(others) if D > 2 else None, _ptr(z), _ptr(V), float(cm), _ptr(imp),
+            below.ctypes.data_as(_ct.POINTER(_ct.c_int64))), "gpe_hm_cells_mv")
+        return imp, below
+
+    def sample(self, lo, hi, state, inc, first, m, z, var_extra, cm, maxno=1, cap=None):
+        """Rejection sampling on the device (gpe_hm_sample): candidates number first ..
+        first + m - 1 of the PCG64 stream with 128-bit ``state`` and ``inc`` (Python ints:
+        ``default_rng(seed).bit_generator.state["state"]``), mapped into the box [lo, hi) as
+        ``lo + rng.random((., D)) * (hi - lo)``, accepted where the maxno-th largest
+        implausibility is below cm.  Returns (points, idx, accepted): the first ``cap`` (None: m)
+        accepted rows in stream order, their candidate numbers, and the count of all accepted."""
+        lo, hi = _f64(lo).ravel(), _f64(hi).ravel()
+        if lo.size != hi.size:
+            raise ValueError("lo and hi have one entry per input")
+        D, p = lo.size, self.outputs
+        z, ve = _f64(z).ravel(), _f64(var_extra).ravel()
+        if z.size != p or ve.size != p:
+            raise ValueError("z and var_extra have one entry per output of the set")
+        m = int(m)
+        cap = m if cap is None else int(cap)
+        rows = max(0, min(cap, m))
+        pts = _np.zeros((rows, D))
+        idx = _np.zeros(rows, dtype=_np.int64)
+        mask = (1 << 64) - 1
+        st = (_ct.c_uint64 * 2)((int(state) >> 64) & mask, int(state) & mask)
+        ic = (_ct.c_uint64 * 2)((int(inc) >> 64) & mask, int(inc) & mask)
+        acc = _ct.c_int64(0)
+        self._check(self.lib.gpe_hm_sample(
+            self._h, D, _ptr(lo), _ptr(hi), st, ic, int(first), m, _ptr(z), _ptr(ve), int(maxno), float(cm), cap,
+            _ptr(pts) if rows else None, idx.ctypes.data_as(_ct.POINTER(_ct.c_int64)) if rows else None,
+            _ct.byref(acc)), "gpe_hm_sample")
+        got = min(int(acc.value), rows)
+        return pts[:got], idx[:got], int(acc.value)
 
 
 def default_context() -> Context:

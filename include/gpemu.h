@@ -38,7 +38,8 @@ extern "C" {
                                 10: gpe_ozaki_stats (gpe_loo, gpe_posterior_pivchol,
                                 gpe_posterior_imse, gpe_posterior_grad, gpe_posterior_mean, gpe_posterior_groups,
                                 gpe_set_outputs, gpe_objective_multi, gpe_beta_multi, gpe_posterior_mean_multi, the gpe_hm_* set (with gpe_hm_add_multi, gpe_hm_outputs,
-                                gpe_hm_member_outputs and gpe_hm_implausibility_mv) and the test
+                                gpe_hm_member_outputs, gpe_hm_implausibility_mv, gpe_hm_cells, gpe_hm_cells_mv
+                                and gpe_hm_sample) and the test
                                 hooks gpe_test_oz_product, gpe_test_oz_planes and gpe_test_gemm_group were
                                 added within 10: additions, nothing existing changed) */
 
@@ -398,6 +399,63 @@ int gpe_hm_member_outputs(const gpe_hm* set, int32_t member);
 int gpe_hm_implausibility_mv(gpe_hm* set, int32_t member, int64_t m, int32_t D, const double* Xs,
                              const double* z, const double* V, double* i2_out, double* mean_out,
                              double* c_out);
+
+/* ---- Candidates made and reduced on the device (additions within ABI 10; kernels in
+ * gpemu_hm_cand.hpp).  The entries above take every candidate row from the host and return a
+ * value per candidate; these write the chunk's rows into the same device buffer by a kernel,
+ * run the same post kernels on it, and reduce I^2 on the device, so that the arguments go up
+ * and only the answer comes back.  A candidate's I^2 has the bits gpe_hm_implausibility gives
+ * for the same row.
+ *
+ * Maps over a mesh of two inputs.  Candidate s = (i g2 + j) ns + t is the row with x1[i] in
+ * column ca, x2[j] in column cb and others[t, :] (ns x (D - 2) row-major; NULL iff D == 2) in
+ * the remaining columns in ascending order; the values are copied.  use (one flag per output, or
+ * NULL: all on): an output switched off has no kernel launched and enters the selection with
+ * I^2 = 0 exactly; a multi-output member has one flag, its first output's.  Level l (0-based)
+ * of a candidate is the (l + 1)-th largest sqrt(I^2) over the outputs, a NaN above every number.
+ * imp_out[l, c] (maxno x g1 g2, cell c = i g2 + j): the minimum of level l over the cell's ns
+ * samples, NaN if any of them is NaN (numpy's min); below_out[l, c]: the samples with level
+ * l < cm (a NaN is not below).  The candidate index is cut into chunks of GPEMU_HM_CHUNK; a
+ * cell may lie across any number of them.  Minima and integer counts do not depend on the order
+ * of combination and the launches are ordered on the set's stream: no atomics, the chunk length
+ * does not show, repeated calls return the same bits.
+ * GPE_ERR_STATE for an empty set; GPE_ERR_ARG, before any device work, for g1, g2 or ns < 1,
+ * ca == cb or either outside [0, D), D < 2, D not above every member's largest active index,
+ * others NULL with D > 2, a NULL among x1, x2, z, var_extra, imp_out and below_out, maxno
+ * outside [1, outputs], or g1 g2 ns >= 2^40. */
+int gpe_hm_cells(gpe_hm* set, int32_t D, int32_t ca, int32_t cb, int32_t g1, const double* x1,
+                 int32_t g2, const double* x2, int64_t ns, const double* others,
+                 const int32_t* use, const double* z, const double* var_extra, int32_t maxno,
+                 double cm, double* imp_out, int64_t* below_out);
+
+/* The same maps for the joint measure of one multi-output member: one level, I = sqrt(I^2) with
+ * I^2 as gpe_hm_implausibility_mv forms it; imp_out and below_out have g1 g2 entries.  Errors as
+ * gpe_hm_cells and gpe_hm_implausibility_mv (GPE_NOT_PD for V). */
+int gpe_hm_cells_mv(gpe_hm* set, int32_t member, int32_t D, int32_t ca, int32_t cb, int32_t g1,
+                    const double* x1, int32_t g2, const double* x2, int64_t ns,
+                    const double* others, const double* z, const double* V, double cm,
+                    double* imp_out, int64_t* below_out);
+
+/* Rejection sampling from numpy's PCG64 stream.  state and inc are the generator's 128-bit state
+ * and increment (numpy's bit_generator.state), high word first.  Candidates number
+ * c in [first, first + m) are tried: coordinate k of candidate c comes from element e = c D + k,
+ * the output after e + 1 steps from state (state <- state * 0x2360ED051FC65DA44385DF649FCCF645
+ * + inc mod 2^128; output rotr64(hi ^ lo, hi >> 58) of the new state; u = (output >> 11) 2^-53),
+ * x_k = lo_k + u (hi_k - lo_k) with the difference, the product and the sum each rounded: the
+ * bits of lo + default_rng(seed).random((., D)) * (hi - lo).  A thread reaches its row through a
+ * host-made table of jumps, one 128-bit product per 8 bits of the row's number in the chunk.
+ * A candidate is accepted when the maxno-th largest sqrt(I^2) over the outputs is < cm (a NaN
+ * is not).  The accepted rows and their candidate numbers go to pts_out (cap x D) and idx_out
+ * (cap) in stream order, by a scan; storing stops at cap rows and *accepted_out counts all
+ * accepted.  Nothing is uploaded but the arguments, and only accepted rows come back.
+ * GPE_ERR_STATE for an empty set; GPE_ERR_ARG for m < 1, first < 0, (first + m) D >= 2^63,
+ * cap < 0, a NULL among lo, hi, state, inc, z, var_extra and accepted_out (and pts_out,
+ * idx_out when cap > 0), D not above every member's largest active index, or maxno outside
+ * [1, outputs]. */
+int gpe_hm_sample(gpe_hm* set, int32_t D, const double* lo, const double* hi,
+                  const uint64_t state[2], const uint64_t inc[2], int64_t first, int64_t m,
+                  const double* z, const double* var_extra, int32_t maxno, double cm, int64_t cap,
+                  double* pts_out, int64_t* idx_out, int64_t* accepted_out);
 
 /* ---- Sensitivity / UQ building blocks, resident factor --------
  * Replace the O(n^2) parts of sensitivity/_sensitivityclasses.py (case2): the
